@@ -10,10 +10,13 @@ The local map is static during the timed region unless --map-update (map_increme
 cycled and every step starts from that scan's propagated state (all of this is stated in `config.workload`).
 
 Contract: python bench.py --gpus N --steps K --warmup W ; rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.  Everything
+else the line can carry - value_long, roofline, the per-launch profile, parity, the CPU baseline, the calibration record, the complete
+pipeline, the other transports and partitions of a sharded job - is measured only with --full (the --no-* switches apply there).
 N > 1 (launched by torch.distributed.run): every rank holds the map and receives the whole scan; the de-skew and the
 voxel filter run replicated (their output is bit-identical on every rank), the down-sampled cloud - voxel-key ordered -
 is split into contiguous blocks inside the library, and each IEKF iteration sums the 91 normal-equation scalars over
-the ranks ("strong" scaling: the per-scan work is fixed).  The line also carries `parity`: the final state of every
+the ranks ("strong" scaling: the per-scan work is fixed).  With --full the line also carries `parity`: the final state of every
 distinct scan of the stream against the CPU oracle (computed in the cpu_baseline leg, outside the timed region).
 """
 import argparse
@@ -212,6 +215,11 @@ def main():
     ap.add_argument("--cell-size", type=float, default=0.0, help="k-NN grid cell edge [m]; 0 = 2 x filter_size_map")
     ap.add_argument("--edge", action="store_true", help="every scan looks past the edge of the map (a floor patch in view of every pose is missing from it)")
     ap.add_argument("--edge-wide", action="store_true", help="--edge with a patch of six times the area: more unfinished queries per search pass than the completion workgroups take (256)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure as well: value_long, roofline and the per-launch profile, parity, the CPU "
+                         "baseline, the calibration record, the complete pipeline, the other transports / partitions of a sharded job")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the final state of the last timed step (what the caller of lii_scan_register receives) as DIR/<field>.npy, float64")
     ap.add_argument("--cpu-sweep-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_sweep_worker:  # (cpu_baseline's thread sweep, in a process of its own: see there)
@@ -432,6 +440,8 @@ def main():
         dt = None
         primed = False
         for n_run, t in enumerate([first] + others):
+            if dt is not None and not args.full:  # (a plain run: the transport that carries `value` only)
+                break
             try:
                 if n_run > 0:
                     attach(t)
@@ -446,42 +456,45 @@ def main():
                                                      "describe": reg.comm_describe()}
             if dt is None:  # the first transport that ran carries `value` (RCCL on distinct devices unless it failed: see transports)
                 dt, value_transport, value_rccl_ranks, first = d, used, reg.comm_rccl_ranks(), t
-                last_pose_value = np.array(last.pod[:12]) if last is not None else None
+                last_state_value = np.array(last.pod) if last is not None else None
         if dt is None:
             raise SystemExit(f"no transport of the 91-scalar exchange ran: {transports}")
         # ... and once more on the first transport with the OTHER split of the cloud
-        partitions = {args.partition: {"value": args.steps / dt, "ms_per_step": 1e3 * dt / args.steps, "describe": transports[value_transport].get("describe")}}
-        other = "voxel" if args.partition == "index" else "index"
-        try:
-            if os.environ.get("LII_BENCH_ONE_PARTITION") == "1":
-                raise RuntimeError("not timed (LII_BENCH_ONE_PARTITION=1)")
-            partition_now[0] = other
-            attach(first)
-            d = timed_region(0)
-            partitions[other] = {"value": args.steps / d, "ms_per_step": 1e3 * d / args.steps, "describe": reg.comm_describe(),
-                                 "avg_iterations": iters_total[0] / args.steps}
-        except Exception as e:
-            partitions[other] = {"error": str(e)[:200]}
-        partition_now[0] = args.partition
-        attach(first)  # the rest of the run (parity calls) on the transport and split `value` was measured with
+        partitions = None
+        if args.full:
+            partitions = {args.partition: {"value": args.steps / dt, "ms_per_step": 1e3 * dt / args.steps, "describe": transports[value_transport].get("describe")}}
+            other = "voxel" if args.partition == "index" else "index"
+            try:
+                if os.environ.get("LII_BENCH_ONE_PARTITION") == "1":
+                    raise RuntimeError("not timed (LII_BENCH_ONE_PARTITION=1)")
+                partition_now[0] = other
+                attach(first)
+                d = timed_region(0)
+                partitions[other] = {"value": args.steps / d, "ms_per_step": 1e3 * d / args.steps, "describe": reg.comm_describe(),
+                                     "avg_iterations": iters_total[0] / args.steps}
+            except Exception as e:
+                partitions[other] = {"error": str(e)[:200]}
+            partition_now[0] = args.partition
+            attach(first)  # the rest of the run (parity calls) on the transport and split `value` was measured with
     else:
         dt = timed_region(args.prime)
         value_transport, value_rccl_ranks = "none", 0
-        last_pose_value = np.array(last.pod[:12]) if last is not None else None
+        last_state_value = np.array(last.pod) if last is not None else None
+    last_pose_value = last_state_value[:12] if last_state_value is not None else None
     tm = reg.timings()
     iters_value, searches_value = iters_total[0], search_total[0]
     slowest_value = dict(slowest_step)
     # The driver's form of this command times 20 steps (~3 ms): a second, longer region of the same steps right behind it gives the
     # line a figure to check `value` against (never `value` itself).
     value_long = None
-    if args.long_steps > 0 and args.long_steps > args.steps:
+    if args.full and args.long_steps > 0 and args.long_steps > args.steps:
         dt_long = timed_region(0, n_steps=args.long_steps, n_warmup=0)
         value_long = {"value": args.long_steps / dt_long, "ms_per_step": 1e3 * dt_long / args.long_steps, "steps": args.long_steps,
                       "what": "the same steps, timed the same way (barrier + synchronize on both sides), right behind the region of `value`"}
     # Where the scan's time goes: a third pass with an event in front of EVERY launch (lii_set_profiling(h, 3); each event is a
     # barrier packet, so this pass is slower than the timed ones and is only used for the SHARES and per-launch durations).
     kernel_profile = None
-    if world == 1 and args.kernel_profile_steps > 0 and not (args.separate_calls or args.upload):
+    if args.full and world == 1 and args.kernel_profile_steps > 0 and not (args.separate_calls or args.upload):
         reg.set_profiling(1)
         if native:
             native(0, args.kernel_profile_steps, -1)
@@ -496,7 +509,7 @@ def main():
     # size of the down-sampled cloud (the k-NN kernel's query count) and, on one GPU, the final state of every distinct scan
     # for the parity record: one untimed call per distinct scan, on every rank (a sharded call needs all of them)
     n_ds, gpu_results, n_short = [], [], []
-    for j in range(len(dev_scans)):
+    for j in range(len(dev_scans) if args.full else 0):
         st = states0[j].copy()
         rep = reg.scan_register(st, states0[j], imu_poses=tables[j], leaf=0.0 if args.no_downsample else wl["fs_surf"],
                                 max_iterations=wl["max_it"], imu_en=True, scan_dev=dev_scans[j], scan_sorted=True)
@@ -507,7 +520,7 @@ def main():
     # the GPU's neighbour lists of the first scan at its start state (one host-driven search pass, the map as timed): compared
     # with the unmodified reference ikd-Tree in the cpu_baseline leg
     gpu_lists = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         s0 = states0[0]
         reg.scan_set_device(dev_scans[0])
         reg.undistort_imu(tables[0], s0.rot_end, s0.pos_end, s0.offset_R_L_I, s0.offset_T_L_I)
@@ -522,7 +535,7 @@ def main():
     # memory (lii_scan_upload: PCIe inside the region), registered, and inserted into the map (lii_map_incremental: device-side
     # Add_Points semantics + index update), so the map grows as in a live run.  Measured last: it changes the map.
     pipeline = None
-    if world == 1 and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_pipeline:
         n_pipe = max(10, min(args.steps, 120))
         leaf = 0.0 if args.no_downsample else float(wl["fs_surf"])
 
@@ -588,8 +601,11 @@ def main():
 
     if rank == 0:
         scans_per_s = args.steps / dt
-        n_d = float(np.mean(n_ds)) / world
         M = len(wl["map"])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_state_value)
+    if rank == 0 and args.full:
+        n_d = float(np.mean(n_ds)) / world
         n_search = max(tm[5], 1.0)
         avg_search_ms = tm[7] / n_search      # the k-NN kernel alone (dominant kernel)
         # algorithmic bytes of one k-NN launch: read query 16 B + write 5 neighbours 80 B per point,
@@ -614,6 +630,7 @@ def main():
                     break
             except Exception:
                 pass
+    if rank == 0:
         out = {
             "metric": "ICP+ESKF scans/sec @100k pts/scan", "value": scans_per_s, "unit": "scans/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -624,21 +641,24 @@ def main():
                                    f"{'voxel-grid leaf %.2f' % wl['fs_surf'] if not args.no_downsample else 'no voxel-grid'}; "
                                    f"{'every scan handed over from host memory (PCIe inside the timed region)' if args.upload else 'scans resident in HBM'}, "
                                    f"{len(dev_scans)} distinct scans cycled, the state reset to the scan's propagated state every step",
-                       "points_per_scan": n_full, "downsampled_points": float(np.mean(n_ds)), "map_points": M,
+                       "points_per_scan": n_full, "map_points": M,
                        "params": f"harness/launch/{WORKLOADS[args.workload][2]} (reference-format yaml + launch)",
                        "avg_iterations": iters_total[0] / args.steps,
                        "avg_knn_passes": search_total[0] / args.steps,
                        "host_loop": "C++ (harness/stream_driver.cpp)" if native else "Python (ctypes)", "parallelism": f"points sharded x{world}" + (f", 91-scalar exchange over {value_transport}"
                                                                     + (f" (ncclCommCount {value_rccl_ranks})" if value_rccl_ranks else "") if world > 1 else ""),
                        "transport": value_transport, "rccl_ranks": value_rccl_ranks},
-            "roofline": {"bound": "hbm", "kernel": knn_kernel_name(),
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": avg_search_ms, "alg_bytes_per_launch": alg_bytes,
-                         "launches": int(tm[5]),
-                         "peak_measured_copy": 6290.0, "frac_of_measured_copy": achieved / 6290.0},
         }
+        if args.full:
+            out["config"]["downsampled_points"] = float(np.mean(n_ds))
+            out["roofline"] = {"bound": "hbm", "kernel": knn_kernel_name(),
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": avg_search_ms, "alg_bytes_per_launch": alg_bytes,
+                               "launches": int(tm[5]),
+                               "peak_measured_copy": 6290.0, "frac_of_measured_copy": achieved / 6290.0}
         if args.edge:
             out["config"]["workload"] = out["config"]["workload"].replace(args.workload + ":", args.workload + "_edge:", 1)
+        if args.edge and args.full:
             out["edge"] = {"patch_missing_from_the_map_m": EDGE_PATCH_WIDE if args.edge == "wide" else EDGE_PATCH,
                            "queries_with_fewer_than_5_neighbours_per_scan": [a for a, _ in n_short],
                            "queries_left_unfinished_by_the_last_search_pass_per_scan": [b for _, b in n_short],
@@ -652,6 +672,7 @@ def main():
             out["last_state_pose"] = [float(v) for v in last_pose_value]
         if world > 1:
             out["config"]["transport_why"] = reg.comm_describe()
+    if rank == 0 and args.full:
         # bytes(scan) = 32 N + S (96 N_d + 16 M) + I (32 N_d + 728), achieved = bytes(scan) x scans/s
         I_avg, S_avg = iters_value / args.steps, searches_value / args.steps
         n_in = float(n_full) / 1.0
@@ -685,15 +706,17 @@ def main():
                                                "time = kernel + dispatch, in a pass that runs slower than the timed region (every event is a barrier "
                                                f"packet: {1e3 * tot_ms / max(kp_scans, 1):.1f} us per scan here against ms_per_step); rocprofv3 durations of the same "
                                                "kernels: profiles/r05_timeline.md")
+    if rank == 0:
         if transports is not None:
             out["transports"] = transports
-            out["partitions"] = partitions
+            if partitions is not None:
+                out["partitions"] = partitions
             out["config"]["partition"] = args.partition
         if pipeline is not None:
             out["complete_pipeline"] = pipeline
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             out["cpu_baseline"], out["parity"] = cpu_baseline(wl, states0, tables, args.no_downsample, gpu_results, gpu_lists)
-        if args.gpus == 1 and not args.no_calibration:
+        if args.full and args.gpus == 1 and not args.no_calibration:
             # the metric's second half: calibration outputs of the GPU path against the oracle, the reference's result file and
             # ground truth (harness/calibration_bench.py)
             try:
@@ -705,6 +728,19 @@ def main():
     reg.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+STATE_FIELDS = ("rot_end", "pos_end", "offset_R_L_I", "offset_T_L_I", "vel_end", "bias_g", "bias_a", "gravity", "cov")
+
+
+def dump_outputs(directory, state_pod):
+    """--dump-outputs: the final lii_state of the last timed step - what lii_scan_register hands its caller - one float64 array per
+    field of lidar_imu_init_amd.State (the inputs are seeded: the same arguments give the same scans, map and start states)."""
+    import lidar_imu_init_amd as lii
+    os.makedirs(directory, exist_ok=True)
+    st = lii.State(state_pod)
+    for name in STATE_FIELDS:
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(getattr(st, name), np.float64))
 
 
 def from_wire_record(args, wl, reg, drv, stream, n_stream, n_pipe):
@@ -841,7 +877,7 @@ def measure_traffic_live(args):
     try:
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", os.path.join(tmp, ctr), "-o", "pmc", "--",
-                   sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", "8", "--warmup", "2", "--prime", "0",
+                   sys.executable, os.path.abspath(__file__), "--full", "--workload", args.workload, "--steps", "8", "--warmup", "2", "--prime", "0",
                    "--profile-every", "0", "--no-cpu-baseline", "--no-pipeline", "--no-calibration", "--kernel-profile-steps", "0",
                    "--long-steps", "0", "--no-live-traffic"] + (["--no-downsample"] if args.no_downsample else []) + (["--edge-wide"] if args.edge == "wide" else (["--edge"] if args.edge else []))
             subprocess.run(cmd, env={**os.environ, "TMPDIR": "/tmp", "LII_BENCH_CHILD": "1"}, cwd="/tmp", timeout=150,

@@ -14,7 +14,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "20", "--warmup", "5", "--prime", "10", "--long-steps", "0", "--no-cpu-baseline", "--no-pipeline", "--no-calibration",
+# --full: the other transports and partitions, roofline.scan and the live traffic passes are measured only there
+COMMON = ["--full", "--steps", "20", "--warmup", "5", "--prime", "10", "--long-steps", "0", "--no-cpu-baseline", "--no-pipeline", "--no-calibration",
           "--no-live-traffic", "--workload", "vlp16"]
 
 

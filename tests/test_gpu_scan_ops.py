@@ -182,7 +182,9 @@ def test_next_scan_travels_while_the_current_one_is_in_use(reg):
     pinned memory (read by the copy engine), and from 48-byte PointXYZINormal records - and the current scan is untouched
     until the swap."""
     import ctypes as C
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself uses: pinned host memory for the direct path
+    # the runtime the library itself uses (symbols looked up through its own handle: where another copy of the HIP runtime was
+    # loaded first - torch's - the library is bound to that one, and a second runtime opened by name sees no device)
+    hip = C.CDLL(reg.L._name)
     rng = np.random.default_rng(11)
     a = rng.normal(size=(30_000, 4)).astype(np.float32)
     b = rng.normal(size=(41_000, 4)).astype(np.float32)

@@ -1,7 +1,7 @@
 """The parameter surface (config/*.yaml + launch/*.launch, src/laserMapping.cpp:767-799) through the C-ABI loader
-(lii_params_*): defaults = the nh.param<> defaults, every file of the harness and - where the reference tree is present -
-every yaml and launch file the reference ships round-trips into lii_config / lii_ingest_opts / lii_iekf_opts; an independent
-parse of the same files (PyYAML) is the checker.  Host code only: runs without a GPU."""
+(lii_params_*): defaults = the nh.param<> defaults, every file of the harness and every yaml and launch file the reference
+ships (kept verbatim under tests/golden/reference_params) round-trips into lii_config / lii_ingest_opts / lii_iekf_opts; an
+independent parse of the same files (PyYAML) is the checker.  Host code only: runs without a GPU."""
 import ctypes as C
 import glob
 import os
@@ -13,7 +13,7 @@ from lidar_imu_init_amd import api
 from lidar_imu_init_amd.params import Params, lii_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.path.join(ROOT, "tests", "golden", "reference_params")  # the reference's config/ and launch/, unmodified
 
 # nh.param name -> (field, default) exactly as src/laserMapping.cpp:770-799 lists them
 NAMES = {
@@ -132,7 +132,6 @@ def test_overrides_and_errors(tmp_path):
         Params(launch=str(tmp_path / "sub" / "y.launch"))  # the yaml cannot be resolved
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "config")), reason="reference tree not present")
 def test_every_shipped_reference_file_loads():
     yamls = sorted(glob.glob(os.path.join(REF, "config", "*.yaml")))
     launches = sorted(glob.glob(os.path.join(REF, "launch", "*.launch")))

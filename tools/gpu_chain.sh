@@ -9,4 +9,4 @@ AB_TAG=win0_ bash tools/ab.sh $1 "tree" "stream100k dense500k vlp16" LII_WINDOW=
 AB_TAG=win1_ bash tools/ab.sh $1 "tree" "stream100k dense500k vlp16" LII_WINDOW=1
 bash tools/ab.sh $1 "gap noprefix" "stream100k"
 grep -h "gap trace" $O/*.err | tail -3
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err; cut -c1-200 $O/bench_driver_form.json
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err; cut -c1-200 $O/bench_driver_form.json

@@ -12,8 +12,8 @@ AB_ARGS=--edge AB_TAG=edge_win1_ bash tools/ab.sh $1 "tree" "stream100k" LII_WIN
 COMMON="--no-cpu-baseline --no-pipeline --no-calibration --no-live-traffic --kernel-profile-steps 0 --long-steps 0"
 for w in 0 1; do for e in "" "--edge"; do
   echo "--- completion trace, window $w $e"
-  LII_WINDOW=$w LII_LIB=$PWD/build_ab/fbtrace/libliinit_hip.so LD_LIBRARY_PATH=$PWD/build_ab/fbtrace:$LD_LIBRARY_PATH timeout 200 python bench.py --steps 200 --warmup 20 $e $COMMON 2>&1 >/dev/null | grep -a "completion trace"
+  LII_WINDOW=$w LII_LIB=$PWD/build_ab/fbtrace/libliinit_hip.so LD_LIBRARY_PATH=$PWD/build_ab/fbtrace:$LD_LIBRARY_PATH timeout 200 python bench.py --full --steps 200 --warmup 20 $e $COMMON 2>&1 >/dev/null | grep -a "completion trace"
 done; done
-timeout 300 python bench.py --edge --no-cpu-baseline --no-pipeline --no-calibration --no-live-traffic > $O/bench_edge.json 2> $O/bench_edge.err
+timeout 300 python bench.py --full --edge --no-cpu-baseline --no-pipeline --no-calibration --no-live-traffic > $O/bench_edge.json 2> $O/bench_edge.err
 python -c "
 import json; d=json.loads(open('$O/bench_edge.json').readline()); print('edge line', round(d['value']), d['ms_per_step'], d['edge'])"

@@ -7,5 +7,5 @@ AB_TAG=win1_ bash tools/ab.sh $1 "tree" "stream100k" LII_WINDOW=1
 COMMON="--no-cpu-baseline --no-pipeline --no-calibration --no-live-traffic --kernel-profile-steps 0 --long-steps 0"
 for w in 0 1; do
   echo "--- completion trace, window $w"
-  LII_WINDOW=$w LII_LIB=$PWD/build_ab/fbtrace/libliinit_hip.so LD_LIBRARY_PATH=$PWD/build_ab/fbtrace:$LD_LIBRARY_PATH timeout 200 python bench.py --steps 200 --warmup 20 $COMMON 2>&1 >/dev/null | grep -a "completion trace"
+  LII_WINDOW=$w LII_LIB=$PWD/build_ab/fbtrace/libliinit_hip.so LD_LIBRARY_PATH=$PWD/build_ab/fbtrace:$LD_LIBRARY_PATH timeout 200 python bench.py --full --steps 200 --warmup 20 $COMMON 2>&1 >/dev/null | grep -a "completion trace"
 done

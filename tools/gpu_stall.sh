@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$1; mkdir -p $O
 F="--no-cpu-baseline --no-pipeline --no-calibration --no-live-traffic --kernel-profile-steps 0 --long-steps 0"
 for r in 1 2 3; do
-  LII_STREAM_TRACE=1 timeout 300 python bench.py $F > $O/run$r.json 2> $O/run$r.err
+  LII_STREAM_TRACE=1 timeout 300 python bench.py --full $F > $O/run$r.json 2> $O/run$r.err
   python - $O/run$r.err $O/run$r.json <<'PY'
 import sys, json, re
 txt = open(sys.argv[1]).read()
@@ -19,6 +19,6 @@ for l in rows:
     base += len(v)
 PY
 done
-timeout 300 python bench.py > $O/default.json 2> $O/default.err; python -c "
+timeout 300 python bench.py --full > $O/default.json 2> $O/default.err; python -c "
 import json; d=json.loads(open('$O/default.json').readline()); print('default', round(d['value']), d.get('slowest_step'), d['complete_pipeline']['value'])"
 timeout 300 python tools/perscan.py 2>&1 | tail -8

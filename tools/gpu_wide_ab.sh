@@ -7,7 +7,7 @@ for rep in 1 2; do
 for w in "--edge-wide" "--edge" ""; do
 for v in 1 0; do
   l=$(echo "x$w" | tr -d ' -')_$v
-  LII_WIDE_COMPLETION=$v LII_DIAG=1 timeout 300 python bench.py $X $w ${PAR:-} > $O/$l.json 2> $O/$l.err
+  LII_WIDE_COMPLETION=$v LII_DIAG=1 timeout 300 python bench.py --full $X $w ${PAR:-} > $O/$l.json 2> $O/$l.err
   python - <<PY
 import json
 d=json.loads(open('$O/$l.json').readline())

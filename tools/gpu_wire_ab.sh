@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$1; mkdir -p $O
 run() {  # label, env...
   local l=$1; shift
-  env "$@" timeout 300 python bench.py --workload ${W:-stream100k} --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-live-traffic --kernel-profile-steps 0 --long-steps 0 > $O/wire_$l.json 2> $O/wire_$l.err
+  env "$@" timeout 300 python bench.py --full --workload ${W:-stream100k} --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-live-traffic --kernel-profile-steps 0 --long-steps 0 > $O/wire_$l.json 2> $O/wire_$l.err
   python - <<PY
 import json
 d=json.loads(open('$O/wire_$l.json').readline()); p=d['complete_pipeline']; w=p.get('from_wire',{})

@@ -13,7 +13,7 @@ for w in $WLS; do
              "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TA_DATA_STALL_CYCLES_sum TCP_GATE_EN1_sum" \
              "TCP_TOTAL_ACCESSES_sum TCP_TOTAL_READ_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_TA_TCP_STATE_READ_sum TCP_TCC_READ_REQ_LATENCY_sum"; do
     i=$((i + 1))
-    env "$@" timeout 300 rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$O/${w}_p$i" -o pmc -- python bench.py --workload $w $CMDT > "$O/${w}_p$i.log" 2>&1 || echo "$w pass $i failed: $(tail -2 $O/${w}_p$i.log | head -1 | cut -c1-200)"
+    env "$@" timeout 300 rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$O/${w}_p$i" -o pmc -- python bench.py --full --workload $w $CMDT > "$O/${w}_p$i.log" 2>&1 || echo "$w pass $i failed: $(tail -2 $O/${w}_p$i.log | head -1 | cut -c1-200)"
   done
   python tools/pmc_table.py $O $w
 done
