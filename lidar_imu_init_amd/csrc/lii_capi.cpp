@@ -15,10 +15,7 @@ thread_local std::string g_err;
 // The profiling events only bracket kernels of ONE stream for hipEventElapsedTime: nothing those kernels wrote has to become visible to the
 // host or to another device when an event is recorded, so the system-scope release a default event performs there - an L2 write-back
 // between the search launch and the fit launch that reads its lists, on the timed path of every profiled step - is left out.
-#ifndef LII_PROF_EVENT_FLAGS
-#define LII_PROF_EVENT_FLAGS hipEventDisableSystemFence
-#endif
-static constexpr unsigned kProfEventFlags = LII_PROF_EVENT_FLAGS;
+static constexpr unsigned kProfEventFlags = hipEventDisableSystemFence;
 
 // The k-NN launches of the last profiled update: their events are read here, not behind the update (see update_on_device).
 void harvest_knn_events(lii_handle h) {
@@ -201,6 +198,63 @@ MailboxView mailbox_view(lii_handle h) {
   return v;
 }
 
+// The environment switches, all read here, once, when the handle is created: the only getenv of the
+// library.  A switch set later is not seen by this handle.
+static void read_switches(lii_handle h) {
+  if (const char* v = std::getenv("LII_DIAG")) h->diag = std::atoi(v) != 0;
+  if (const char* v = std::getenv("LII_VOXEL_FILTER")) {
+    h->voxel_sort = std::string(v) == "sort";
+    if (std::string(v) == "hash") { h->vh_pinned = true; h->vh_mode = 1; }
+  }
+  if (const char* v = std::getenv("LII_KNN_PLAN")) h->knn_plan = std::atoi(v) != 0;
+  if (const char* v = std::getenv("LII_WINDOW_KEEP")) h->win_keep = std::atoi(v) != 0;
+  if (const char* v = std::getenv("LII_MAP_FUSE")) h->map_fuse = v[0] != '0';
+  if (const char* v = std::getenv("LII_WIDE_COMPLETION")) h->wide_enabled = v[0] != '0';
+  if (const char* v = std::getenv("LII_INGEST_SORT")) h->ingest_sort_always = v[0] == 'a';
+  if (const char* v = std::getenv("LII_PREARM")) h->pre.enabled = std::atoi(v) != 0;
+  if (const char* v = std::getenv("LII_PREARM_TIMEOUT_MS")) h->pre.timeout_ticks = std::max(1ll, (long long)(std::atof(v) * 1e5));
+  if (const char* v = std::getenv("LII_MAILBOX_TIMEOUT_S")) {  // <exchange>[,<set-up>]
+    h->net.mailbox_timeout_ticks = (long long)(std::atof(v) * 1e8);
+    if (const char* c = std::strchr(v, ',')) h->net.mailbox_wait_s = std::atof(c + 1);
+  }
+  if (const char* v = std::getenv("LII_TEST")) {
+    // arrangements the test-suite and the A/B measurements ask for, comma-separated: "map_tight" (an in-place map update without
+    // spare room), "plan_force=<mask>" (a launch plan that is wrong on purpose), "host_solve" (the iteration loop driven from the
+    // host around lii_iekf_iterate with the literal two-inversion algebra), "sync_result" (every update ends with
+    // hipStreamSynchronize instead of polling the result word), "pred_small" (lii_map_incremental predicts list sizes that are
+    // always too small), "fold_sort" (lii_map_incremental folds its list through the batch sort, as lii_map_add_points does,
+    // instead of the hash table), "no_fuse" (lii_scan_register keeps the de-skew and the insert of the hashed voxel filter in
+    // separate launches), "no_fast" (a time-sorted scan takes the general path of lii_scan_register too: k_time_extent in front of
+    // the de-skew), "force_rebuild" (every in-place map update takes the branch that rebuilds the index first), "no_gather" (a
+    // sharded job sets up no gather areas: its map update repeats the search instead of exchanging the lists), "solo_share=<N>" /
+    // "solo_share=-<N>" (kernel-timing rehearsal: ONE process works on rank 0's share of an N-rank job split by voxel / by index,
+    // nothing is exchanged - the durations of a rank's launches without N devices; the result is that of a part of the cloud),
+    // "emit_late" (every seventh workgroup of the voxel filter's emit and of the map update's decision launch publishes its count
+    // only when it is done: the workgroups above it take the path of a launch whose workgroups are not all resident and count its
+    // block themselves), "sum_lost" (one summing workgroup of k_reduce_solve never publishes its sum: the solver's wait ends the
+    // update with LII_ERR_COMM, after 0.2 s)
+    const std::string t(v);
+    for (size_t b = 0, e; b < t.size(); b = e + 1) {
+      e = std::min(t.find(',', b), t.size());
+      const std::string k = t.substr(b, e - b);
+      if (k == "map_tight") h->map_tight = true;
+      else if (k.compare(0, 11, "plan_force=") == 0) h->knn_plan_force = int(std::strtol(k.c_str() + 11, nullptr, 0) & 0x7FFFFFFF);
+      else if (k == "host_solve") h->host_solve = true;
+      else if (k == "sync_result") h->poll_result = false;
+      else if (k == "pred_small") h->test_pred_small = true;
+      else if (k == "fold_sort") h->fold_sorted = true;
+      else if (k == "no_fuse") h->no_fuse = true;
+      else if (k == "no_fast") h->no_fast_prologue = true;
+      else if (k == "force_rebuild") h->test_force_rebuild = true;
+      else if (k == "no_gather") h->no_gather = true;
+      else if (k == "emit_late") h->test_emit_late = true;
+      else if (k == "sum_lost") h->test_sum_lost = true;
+      else if (k.compare(0, 11, "solo_share=") == 0) h->solo_share = int(std::strtol(k.c_str() + 11, nullptr, 0));
+      else if (!k.empty()) std::fprintf(stderr, "[libliinit_hip] LII_TEST: unknown token '%s' ignored\n", k.c_str());
+    }
+  }
+}
+
 }  // namespace lii_impl
 
 int lii_internal_fail(lii_context* h, int code, const std::string& msg) { return fail(h, code, msg); }
@@ -229,6 +283,7 @@ int lii_internal_scan_defer(lii_handle h, const void* dev_float4, int32_t n) {
 int lii_internal_li_init_on_device(lii_context* h) { return h && h->cal.li_init_device ? 1 : 0; }
 hipStream_t lii_internal_stream(lii_context* h) { return h->stream; }
 void** lii_internal_ingest_slot(lii_context* h) { return &h->ingest; }
+void lii_internal_ingest_switches(lii_context* h, bool* diag, bool* sort_always) { *diag = h->diag; *sort_always = h->ingest_sort_always; }
 
 extern "C" {
 
@@ -273,50 +328,7 @@ int lii_create(const lii_config* cfg, lii_handle* out) {
   h->cell_size = cfg->map_cell_size > 0 ? cfg->map_cell_size : 3.0f * h->cfg.map_downsample_size;
   // the 3x3x3 neighbourhood of 8x8x8-cell blocks must cover the acceptance radius sqrt(max_match_dist2)
   h->cell_size = std::max(h->cell_size, std::sqrt(h->cfg.max_match_dist2) / 8.0f * 1.001f);
-  if (const char* v = std::getenv("LII_DIAG")) h->diag = std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_PROF_BRACKET")) h->prof.bracket_events = std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_VOXEL_FILTER")) {
-    h->voxel_sort = std::string(v) == "sort";
-    if (std::string(v) == "hash") { h->vh_pinned = true; h->vh_mode = 1; }
-  }
-  if (const char* v = std::getenv("LII_KNN_PLAN")) h->knn_plan = std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_WINDOW")) h->use_window = std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_WINDOW_KEEP")) h->win_keep = std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_TEST")) {
-    // arrangements the test-suite and the A/B measurements ask for, comma-separated: "map_tight" (an in-place map update without
-    // spare room), "plan_force=<mask>" (a launch plan that is wrong on purpose), "host_solve" (the iteration loop driven from the
-    // host around lii_iekf_iterate with the literal two-inversion algebra), "sync_result" (every update ends with
-    // hipStreamSynchronize instead of polling the result word), "graph" (the enqueued passes of an update replayed from a
-    // captured hipGraph), "pred_small" (lii_map_incremental predicts list sizes that are always too small), "fold_sort"
-    // (lii_map_incremental folds its list through the batch sort, as lii_map_add_points does, instead of the hash table), "no_fuse"
-    // (lii_scan_register keeps the de-skew and the insert of the hashed voxel filter in separate launches), "no_fast" (a
-    // time-sorted scan takes the general path of lii_scan_register too: k_time_extent in front of the de-skew), "force_rebuild"
-    // (every in-place map update takes the branch that rebuilds the index first), "no_gather" (a sharded job sets up no gather areas:
-    // its map update repeats the search instead of exchanging the lists), "solo_share=<N>" / "solo_share=-<N>" (kernel-timing
-    // rehearsal: ONE process works on rank 0's share of an N-rank job split by voxel / by index, nothing is exchanged - the
-    // durations of a rank's launches without N devices; the result is that of a part of the cloud), "emit_late" (every seventh
-    // workgroup of the voxel filter's emit and of the map update's decision launch publishes its count only when it is done: the
-    // workgroups above it take the path of a launch whose workgroups are not all resident and count its block themselves)
-    const std::string t(v);
-    h->map_tight = t.find("map_tight") != std::string::npos;
-    const size_t q = t.find("plan_force=");
-    if (q != std::string::npos) h->knn_plan_force = int(std::strtol(t.c_str() + q + 11, nullptr, 0) & 0x7FFFFFFF);
-    h->host_solve = t.find("host_solve") != std::string::npos;
-    h->poll_result = t.find("sync_result") == std::string::npos;
-    h->use_graph = t.find("graph") != std::string::npos;
-    h->test_pred_small = t.find("pred_small") != std::string::npos;
-    h->fold_sorted = t.find("fold_sort") != std::string::npos;
-    h->no_fuse = t.find("no_fuse") != std::string::npos;
-    h->no_fast_prologue = t.find("no_fast") != std::string::npos;
-    h->test_force_rebuild = t.find("force_rebuild") != std::string::npos;
-    h->no_gather = t.find("no_gather") != std::string::npos;
-    h->test_emit_late = t.find("emit_late") != std::string::npos;
-    h->test_sum_lost = t.find("sum_lost") != std::string::npos;
-    const size_t qs = t.find("solo_share=");
-    if (qs != std::string::npos) h->solo_share = int(std::strtol(t.c_str() + qs + 11, nullptr, 0));
-  }
-  if (const char* mf = std::getenv("LII_MAP_FUSE")) h->map_fuse = mf[0] != '0';
-  if (const char* wc = std::getenv("LII_WIDE_COMPLETION")) h->wide_enabled = wc[0] != '0';
+  read_switches(h);
   h->ds = h->cfg.map_downsample_size;
   h->device = cfg->device;
 #define CK(call)                                                                  \
@@ -418,10 +430,8 @@ int lii_create(const lii_config* cfg, lii_handle* out) {
   {  // the host writes the record straight into device memory: only where the whole of it is visible to the host (large BAR)
     int large_bar = 0;
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) large_bar = 0;
-    h->pre.enabled = large_bar != 0;
+    h->pre.enabled = h->pre.enabled && large_bar != 0;
   }
-  if (const char* v = std::getenv("LII_PREARM")) h->pre.enabled = h->pre.enabled && std::atoi(v) != 0;
-  if (const char* v = std::getenv("LII_PREARM_TIMEOUT_MS")) h->pre.timeout_ticks = std::max(1ll, (long long)(std::atof(v) * 1e5));
   CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_res), sizeof(IekfResult), hipHostMallocMapped));
   std::memset(h->h_res, 0, sizeof(IekfResult));
   partition_refresh(h);
@@ -532,8 +542,6 @@ int lii_destroy(lii_handle h) {
   if (h->diag && h->prof.host_us[4] > 0 && (h->prof.host_map_us[0] > 0 || h->prof.host_map_us[1] > 0))
     std::fprintf(stderr, "[libliinit_hip] map update, host us per scan: waited for the update in flight %.1f, enqueued behind the passes %.1f\n",
                  h->prof.host_map_us[0] / h->prof.host_us[4], h->prof.host_map_us[1] / h->prof.host_us[4]);
-  for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.second);
-  h->graphs.clear();
   mailbox_close(&h->net.mailbox);
   if (h->net.d_mb_seq) (void)hipFree(h->net.d_mb_seq);
   if (h->net.d_gather_ticket) (void)hipFree(h->net.d_gather_ticket);

@@ -140,15 +140,8 @@ int comm_init(lii_handle h, int32_t n_ranks, int32_t rank, const uint8_t id_in[1
     if (!h->net.d_gather_ticket) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_gather_ticket), sizeof(unsigned int)));
     HIPCHK(h, hipMemset(h->net.d_gather_ticket, 0, sizeof(unsigned int)));
     h->net.gather_seq = 0;
-    // LII_MAILBOX_TIMEOUT_S=<exchange>[,<set-up>]: how long a reduce+solve kernel waits for a peer's sums (30 s), how long this
-    // call waits for all ranks in the node-local segment (20 s)
-    double wait_s = 20.0;
-    if (const char* t = std::getenv("LII_MAILBOX_TIMEOUT_S")) {
-      h->net.mailbox_timeout_ticks = (long long)(std::atof(t) * 1e8);
-      if (const char* c = std::strchr(t, ',')) wait_s = std::atof(c + 1);
-    }
     std::string why;
-    if (mailbox_open(id_in, n_ranks, rank, wait_s, transport != LII_COMM_MAILBOX_HOST, h->no_gather ? 0 : h->cfg.max_scan_points, &h->net.mailbox, &why) == 0) {
+    if (mailbox_open(id_in, n_ranks, rank, h->net.mailbox_wait_s, transport != LII_COMM_MAILBOX_HOST, h->no_gather ? 0 : h->cfg.max_scan_points, &h->net.mailbox, &why) == 0) {
       if (transport == LII_COMM_MAILBOX && !h->net.mailbox.d_peers) {  // asked for by name: no silent change of the transport
         mailbox_close(&h->net.mailbox);
         h->net.n_ranks = 1; h->net.rank = 0;

@@ -83,7 +83,7 @@ int build_index(lii_handle h, int n, int extra_blocks) {
   }
   HIPCHK(h, hipGetLastError());
   h->win_valid = false;
-  if (h->use_window && n > 0) {
+  if (n > 0) {
     // the dense cell window: the box of the occupied blocks, one block of margin on every side (queries at the map's edge look one
     // cell out), if it fits 64 MiB of entries
     unsigned int* box = reinterpret_cast<unsigned int*>(h->d_cs_a);  // (free again)

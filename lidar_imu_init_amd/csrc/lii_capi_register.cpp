@@ -10,9 +10,8 @@ namespace {
 
 
 // (every enqueued search launch has a number, which the fit launch behind it shares: the list of unfinished queries the one leaves
-// and the other consumes - RegistrationBuffers::flag_*; 0 = no list: launches captured into a hipGraph, whose arguments are frozen)
-int next_knn_epoch(lii_handle h, bool listed) {
-  if (!listed) return 0;
+// and the other consumes - RegistrationBuffers::flag_*)
+int next_knn_epoch(lii_handle h) {
   h->knn_epoch = h->knn_epoch >= 0x3FFFFFFE ? 1 : h->knn_epoch + 1;  // (consecutive numbers alternate between the two slots, across the wrap as well)
   return h->knn_epoch;
 }
@@ -38,7 +37,7 @@ int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double*
     HIPCHK(h, hipMemcpyAsync(h->d_pose, stage, sizeof(PoseArg), hipMemcpyHostToDevice, h->stream));
   }
   if (search) h->unfinished_known = false;  // (a search pass of this host-driven call: lii_last_unfinished_queries reads the device again)
-  const int epoch = search ? next_knn_epoch(h, true) : 0;
+  const int epoch = search ? next_knn_epoch(h) : 0;
   if (search) launch_knn(h, g, rb, h->d_pose, 1, epoch);
   if (prof) HIPCHK(h, hipEventRecord(h->prof.ev[3], h->stream));
   launch_fit_reduce(g, rb, h->d_pose, h->d_ctrl, search ? 1 : 0, imu_en ? 1 : 0, h->cfg.plane_threshold,
@@ -131,26 +130,22 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   const unsigned int plan0 = plan;
   // (profiling = HIP events around the k-NN launches only - the dominant kernel, lii_last_timings [5] / [7]; every event is a
   // barrier packet on the stream, so the rest of the loop is left alone: launch plan and result polling work as always)
-  const bool graph_mode = h->use_graph && !h->net.comm && !h->prof.profiling;
   auto enqueue_pass = [&](int it) -> int {
     const bool knn = it >= 16 || ((plan >> it) & 1u);
     // (a fit launch that is not behind a search launch never runs as a search pass - the plan parks the loop instead - and needs no number)
-    const int epoch = knn ? next_knn_epoch(h, !graph_mode) : 0;
+    const int epoch = knn ? next_knn_epoch(h) : 0;
     if (knn) {
       // (the k-NN launches of a profiled update carry their two events IN the dispatch: the kernel's own start and end stamps.  Rounds
       // 1 - 5 recorded an event in front of and behind the launch - two barrier packets each, + 22 us on a profiled scan, and the
-      // bracket held the dispatch as well as the kernel; LII_PROF_BRACKET=1 keeps that form for comparison)
-      const bool in_dispatch = prof && it < 16 && !h->prof.bracket_events;
-      if (prof && it < 16 && !in_dispatch) HIPCHK(h, hipEventRecord(h->prof.ev_it[2 * it], s));
+      // bracket held the dispatch as well as the kernel)
       if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_KNN, it); if (r != LII_OK) return r; }
-      if (in_dispatch) launch_knn(h, g, rb, pose, -1, epoch, h->prof.ev_it[2 * it], h->prof.ev_it[2 * it + 1]);
+      if (prof && it < 16) launch_knn(h, g, rb, pose, -1, epoch, h->prof.ev_it[2 * it], h->prof.ev_it[2 * it + 1]);
       else launch_knn(h, g, rb, pose, -1, epoch);
-      if (prof && it < 16 && !in_dispatch) HIPCHK(h, hipEventRecord(h->prof.ev_it[2 * it + 1], s));
     }
     if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_FIT, it); if (r != LII_OK) return r; }
     // the scan before left more unfinished queries per search pass than the fit launch's completion workgroups take: this one's
     // are finished by a launch of their own, one wavefront per listed query (k_complete_listed; nothing to do -> it returns at once)
-    if (knn && h->wide_listed && !graph_mode && !h->net.comm && h->net.n_ranks <= 1) launch_complete_listed(g, rb, h->d_ctrl, -1, s, epoch);
+    if (knn && h->wide_listed && !h->net.comm && h->net.n_ranks <= 1) launch_complete_listed(g, rb, h->d_ctrl, -1, s, epoch);
     launch_fit_reduce(g, rb, pose, h->d_ctrl, -1, opts->imu_en ? 1 : 0, h->cfg.plane_threshold, h->cfg.laser_point_cov_inv, s, epoch);
     if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_SOLVE, it); if (r != LII_OK) return r; }
     if (!h->net.comm) {  // single GPU or node-local mailbox: final sum (+ exchange) and solve in one launch
@@ -166,47 +161,9 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     return LII_OK;
   };
   const auto t_loop0 = std::chrono::steady_clock::now();
-  auto enqueue_planned = [&]() -> int {
-    for (int it = 0; it < opts->max_iterations; it++) {
-      if (it < 16 && !((plan >> (16 + it)) & 1u)) break;  // the plan ends here
-      const int r = enqueue_pass(it);
-      if (r != LII_OK) return r;
-    }
-    return LII_OK;
-  };
-  if (graph_mode) {
-    // The same launches, captured once and replayed (hipGraphLaunch): every kernel argument of the loop is a device pointer or
-    // a constant of the configuration, except the bound of the cloud size (rounded up here: the kernels take the exact size
-    // from the device), the plan and the view of the map - the key of the cache.  Measured against the plain launches in
-    // profiles/r03_hipgraph_ab.md.
-    if (rb.n_dev) rb.n = std::min(rb.cap, (rb.n + 4095) & ~4095);
-    struct { const void* p[4]; unsigned int mask; int n_pts, n, plan, max_it, imu_en, shard; float cs; } kv;
-    std::memset(&kv, 0, sizeof(kv));
-    kv.p[0] = g.pts; kv.p[1] = g.blocks; kv.p[2] = g.cells; kv.p[3] = rb.n_dev;
-    kv.mask = g.block_mask; kv.n_pts = g.n_pts; kv.n = rb.n; kv.plan = (int)plan; kv.max_it = opts->max_iterations;
-    kv.imu_en = opts->imu_en ? 1 : 0;
-    kv.shard = rb.shard_world * 4096 + rb.shard_rank; kv.cs = g.cs;
-    const std::string key(reinterpret_cast<const char*>(&kv), sizeof(kv));
-    auto f = h->graphs.find(key);
-    if (f == h->graphs.end()) {
-      if (h->graphs.size() >= 64) {
-        for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.second);
-        h->graphs.clear();
-      }
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      HIPCHK(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      rc = enqueue_planned();
-      const hipError_t e_end = hipStreamEndCapture(s, &graph);
-      if (rc != LII_OK) return rc;
-      HIPCHK(h, e_end);
-      HIPCHK(h, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      HIPCHK(h, hipGraphDestroy(graph));
-      f = h->graphs.emplace(key, exec).first;
-    }
-    HIPCHK(h, hipGraphLaunch(f->second, s));
-  } else {
-    rc = enqueue_planned();
+  for (int it = 0; it < opts->max_iterations; it++) {
+    if (it < 16 && !((plan >> (16 + it)) & 1u)) break;  // the plan ends here
+    rc = enqueue_pass(it);
     if (rc != LII_OK) return rc;
   }
   // The iteration that stops the loop writes the result block (mapped host memory) and then its sequence number.  Polling
@@ -254,7 +211,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   // THE NEXT SCAN'S PROLOGUE, pre-armed (lii_launch.h: DeskewGate): the job announced the scan the next call will bring - its de-skew +
   // filter-insert launch goes out now, behind this update's passes (and its map update), and waits on the device for the record
   // the next lii_scan_register writes.
-  if (h->pre.want_dev && !h->net.comm && h->net.n_ranks <= 1 && h->prof.prof_mode != 3 && !graph_mode && !h->map_async && h->poll_result) {  // (poll_result: a caller that ends its updates with a stream synchronise - LII_TEST=sync_result - would wait for the waiting launch)  // (mode 3 puts an event in front of every launch: not in front of one that waits)
+  if (h->pre.want_dev && !h->net.comm && h->net.n_ranks <= 1 && h->prof.prof_mode != 3 && !h->map_async && h->poll_result) {  // (poll_result: a caller that ends its updates with a stream synchronise - LII_TEST=sync_result - would wait for the waiting launch)  // (mode 3 puts an event in front of every launch: not in front of one that waits)
     lii::GateState* gst = h->pre.state;
     h->pre.seq = (h->pre.seq + 1) & 0x003FFFFFFFFFFFFFull;  // (seq << 2 stays below the tag's top byte)
     __atomic_store_n(&gst->word, (h->pre.seq << 2) | lii::kGateArmed, __ATOMIC_RELEASE);

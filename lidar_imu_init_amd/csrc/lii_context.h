@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -38,8 +37,7 @@ struct lii_context {
   float4* d_batch = nullptr;    // a host-provided Add_Points batch (M)
   float4* d_dropped = nullptr;  // inserts an in-place update found no room for (kMapCtrDropped of them): re-inserted after a rebuild
   unsigned int drop_cap = 0;
-  // dense cell window over the map's box (GridView::win; LII_WINDOW=0 turns it off): filled by build_index, dropped by whatever changes a cell entry
-  bool use_window = true;
+  // dense cell window over the map's box (GridView::win): filled by build_index, dropped by whatever changes a cell entry
   uint2* d_win = nullptr;
   size_t win_cap = 0;            // entries allocated
   int win_org[3] = {0, 0, 0}, win_dim[3] = {0, 0, 0};
@@ -149,8 +147,6 @@ struct lii_context {
   bool no_fuse = false;        // LII_TEST=no_fuse: lii_scan_register keeps the de-skew and the voxel filter's insert in separate launches
   bool test_sum_lost = false;  // LII_TEST=sum_lost: one summing workgroup of k_reduce_solve never publishes - the solver's wait must end in LII_ERR_COMM
   bool test_emit_late = false; // LII_TEST=emit_late: every seventh workgroup of k_vhash_emit / k_map_decide publishes its count late: the others count its block themselves (prefix_below)
-  bool use_graph = false;      // LII_TEST=graph: the passes of an update are captured once per (cloud bound, plan, map view) and replayed
-  std::map<std::string, hipGraphExec_t> graphs;
   int plan_passes_prev = 32;   // passes the update before the last one ran (the plan enqueues the larger of the last two)
   int knn_plan_force = -1;     // LII_TEST=plan_force=<mask>: use this plan for every update (tests: forces the parked path)
   unsigned int plan_next = 0xFFFFFFFFu, plan_cur = 0xFFFFFFFFu;
@@ -248,6 +244,7 @@ struct lii_context {
     bool li_init_device = false;  // lii_li_init_set_device: zero-phase filter + cross-correlation of lii_li_init_run on the device
   } cal;
   void* ingest = nullptr;  // lii_ingest.hip state (frames of the last driver message)
+  bool ingest_sort_always = false;  // LII_INGEST_SORT=always: the ingest never leaves the time sort out (IngestRing::never_predict)
 
   // ---- comm
   struct CommState {  // lii_capi_comm.cpp: the communicator of a sharded job
@@ -259,6 +256,7 @@ struct lii_context {
     size_t gx_block = 0; int gx_ranks = 0;    // ... laid out for this block size (64 + 16 max_scan_points) and this many ranks
     unsigned long long gather_seq = 0;        // ... and the exchanges enqueued so far (the ranks call in lock-step: the same on all)
     long long mailbox_timeout_ticks = 3000000000ll;  // 30 s (LII_MAILBOX_TIMEOUT_S): ranks may start a scan seconds apart
+    double mailbox_wait_s = 20.0;   // how long lii_comm_init waits for all ranks in the node-local segment (LII_MAILBOX_TIMEOUT_S=<exchange>,<set-up>)
     int n_ranks = 1, rank = 0;
     std::string comm_why;           // which transport this rank ended up with and why (lii_comm_describe)
     bool library_partition = true;  // lii_comm_set_partition: the library splits the down-sampled cloud over the ranks (every rank
@@ -277,7 +275,6 @@ struct lii_context {
     lii_kernel_profile kprof{};
     bool profiling = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool bracket_events = false;       // LII_PROF_BRACKET=1: events recorded around the k-NN launches instead of inside their dispatch
     hipEvent_t ev_it[32] = {};
     unsigned int ev_it_due = 0u;       // iterations whose pair of ev_it holds a k-NN launch that has not been read yet (harvest_knn_events)  // per-iteration brackets of the k-NN kernel in the device-driven loop
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};

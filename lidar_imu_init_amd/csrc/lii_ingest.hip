@@ -340,12 +340,13 @@ struct IngestRing {
   // check is done again with the sort before its frames are handed out.  LII_INGEST_SORT=always: never predicted.
   bool predict_sorted = false;
   bool never_predict = false;
+  bool diag = false;  // LII_DIAG (the handle's switches, taken when the ring is created)
   long long n_unsorted_skipped = 0, n_redone = 0;
 };
 
 void ingest_free(IngestRing* r) {
   if (!r) return;
-  if (getenv("LII_DIAG") && (r->n_unsorted_skipped || r->n_redone))
+  if (r->diag && (r->n_unsorted_skipped || r->n_redone))
     fprintf(stderr, "[libliinit_hip] ingest: messages cut without their time sort (they arrived in time order): %lld, done again with it: %lld\n",
             r->n_unsorted_skipped, r->n_redone);
   if (r->s_copy) { (void)hipStreamSynchronize(r->s_copy); (void)hipStreamDestroy(r->s_copy); }
@@ -405,8 +406,7 @@ IngestRing* ring_of(lii_handle h) {
   void** slot = lii_internal_ingest_slot(h);
   if (!*slot) {
     IngestRing* r = new IngestRing();
-    const char* e = getenv("LII_INGEST_SORT");
-    r->never_predict = e && e[0] == 'a';
+    lii_internal_ingest_switches(h, &r->diag, &r->never_predict);
     *slot = r;
   }
   return static_cast<IngestRing*>(*slot);
@@ -415,17 +415,9 @@ IngestRing* ring_of(lii_handle h) {
 // The overlapped forms' streams, at the DEFAULT priority: a low-priority stream was measured first (a registration launch ahead of a
 // message that is not due yet, the idea went) and made the whole loop 2.4 x SLOWER than the serial form - 1 904 against 4 454 scans/s
 // at the default priority, 2 541 serial (profiles/r06_ingest_overlap.md): queues of unequal priority are time-sliced on this device.
-// LII_INGEST_PRIO=low brings that form back for measurements.
 int ring_streams(lii_handle h, IngestRing* r) {
   if (r->s_kern) return LII_OK;
-  const char* ep = getenv("LII_INGEST_PRIO");
-  if (ep && ep[0] == 'l') {
-    int least = 0, greatest = 0;
-    ICHK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    ICHK(h, hipStreamCreateWithPriority(&r->s_kern, hipStreamNonBlocking, least));
-  } else {
-    ICHK(h, hipStreamCreateWithFlags(&r->s_kern, hipStreamNonBlocking));
-  }
+  ICHK(h, hipStreamCreateWithFlags(&r->s_kern, hipStreamNonBlocking));
   ICHK(h, hipStreamCreateWithFlags(&r->s_copy, hipStreamNonBlocking));
   for (int k = 0; k < IngestRing::kSlots; k++) {
     ICHK(h, hipEventCreateWithFlags(&r->ev_copied[k], hipEventDisableTiming));

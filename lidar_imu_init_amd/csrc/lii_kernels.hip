@@ -2061,28 +2061,20 @@ static inline int shard_bound(const RegistrationBuffers& rb) {
 // 128 lanes per workgroup, 6 loads in flight per lane, 7 wavefronts per SIMD (69 VGPRs): measured on the per-lane form of rounds 3 - 4
 // against 64 / 256 lanes, 4 .. 12 loads, 6 / 8 wavefronts per SIMD (within 1 - 2 %: profiles/r03_knn_ab.md), and 2 / 1 lanes per query
 // (slower at every cloud size: profiles/r05_knn_lpq.md).
-#ifndef LII_KNN_BS  // (experiment builds: tools/ab_build.sh ... -DLII_KNN_BS=256 -DLII_KNN_NB=4 -DLII_KNN_WPE=8)
-#define LII_KNN_BS 128
-#endif
-#ifndef LII_KNN_NB
-#define LII_KNN_NB 6
-#endif
-#ifndef LII_KNN_WPE
-#define LII_KNN_WPE 7
-#endif
+constexpr int kKnnBs = 128, kKnnNb = 6, kKnnWpe = 7;
 // epoch: the number of this search launch (> 0; the fit launch behind it gets the same) - or 0: no list of unfinished queries, every
-// workgroup of the fit launch finishes its own (hipGraph replays, whose arguments are frozen)
+// workgroup of the fit launch finishes its own (the map update's repeated search)
 void launch_knn(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
                 const IekfCtrl* ctrl, int forced, double* search_pose_out, hipStream_t s, int epoch, hipEvent_t ev_start, hipEvent_t ev_stop) {
-  int nq = nblk(shard_bound(rb), LII_KNN_BS / 4);
+  int nq = nblk(shard_bound(rb), kKnnBs / 4);
   if (nq < 1) nq = 1;
   const int nq_pad = ((nq + 7) / 8) * 8;
   if (ev_start && ev_stop) {  // (measurement: the dispatch's own time stamps, no barrier packets around it)
-    hipExtLaunchKernelGGL((k_knn_ck<4, LII_KNN_BS, LII_KNN_NB, LII_KNN_WPE>), dim3(nq_pad), dim3(LII_KNN_BS), 0, s, ev_start, ev_stop, 0u, g, rb, pose, ctrl, forced, nq,
+    hipExtLaunchKernelGGL((k_knn_ck<4, kKnnBs, kKnnNb, kKnnWpe>), dim3(nq_pad), dim3(kKnnBs), 0, s, ev_start, ev_stop, 0u, g, rb, pose, ctrl, forced, nq,
                           search_pose_out, epoch);
     return;
   }
-  hipLaunchKernelGGL((k_knn_ck<4, LII_KNN_BS, LII_KNN_NB, LII_KNN_WPE>), dim3(nq_pad), dim3(LII_KNN_BS), 0, s, g, rb, pose, ctrl, forced, nq, search_pose_out, epoch);
+  hipLaunchKernelGGL((k_knn_ck<4, kKnnBs, kKnnNb, kKnnWpe>), dim3(nq_pad), dim3(kKnnBs), 0, s, g, rb, pose, ctrl, forced, nq, search_pose_out, epoch);
 }
 void launch_knn_complete(const GridView& g, const RegistrationBuffers& rb, hipStream_t s) {
   int nb = nblk(shard_bound(rb), kBlock);

@@ -17,6 +17,7 @@ int lii_internal_scan_is_deferred(lii_context* h);  // (lii_capi.cpp) 1: a selec
 void lii_internal_prearm_cancel(lii_context* h);  // (lii_capi.cpp) see lii_impl::prearm_cancel  // (lii_capi.cpp) a selected frame nobody has read yet -> the handle's own scan buffer
 hipStream_t lii_internal_stream(lii_context* h);
 void** lii_internal_ingest_slot(lii_context* h);
+void lii_internal_ingest_switches(lii_context* h, bool* diag, bool* sort_always);  // (lii_capi.cpp) LII_DIAG, LII_INGEST_SORT=always
 
 namespace lii {
 void ingest_destroy(void* slot);  // lii_ingest.hip

@@ -814,16 +814,7 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
   // owners in the workgroups below this one; a block whose word is overdue is counted here: which of its points own their voxel
   // (one 16-byte request per point decides it, as above; a slot its owner - a point of another block - has freed already reads
   // empty: not this point's voxel any more, and it never was its owner)
-#ifdef LII_ABL_EMIT_NOPREFIX
-  // ABLATION (timing only, tools/ab_build.sh ... -DLII_ABL_EMIT_NOPREFIX): no exchange of counts inside the launch - every workgroup
-  // writes its owners to its own stretch of 256 slots and the cloud is taken to have n entries (the holes keep whatever they held).
-  // Prices what an UNCOMPACTED down-sampled cloud would save in this kernel; the results of such a build are wrong.
-  const unsigned int base_abl = blockIdx.x * 256u;
-#endif
   const unsigned int base =
-#ifdef LII_ABL_EMIT_NOPREFIX
-      true ? base_abl :
-#endif
       prefix_below(counts, epoch, (int)blockIdx.x, s_sum, test_late != 0, [&](int q) -> unsigned int {
     const int j = q * 256 + tid;
     bool f = false;
@@ -848,9 +839,6 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
   }
   if (blockIdx.x == gridDim.x - 1 && tid == 0) {  // size of the down-sampled cloud
     int n_down = (int)(base + total);
-#ifdef LII_ABL_EMIT_NOPREFIX
-    n_down = n;
-#endif
     if (ABS && tb.part_world > 1u && n_down > tb.part_bound) {  // this rank's share outgrew what the launches behind are sized for
       n_down = tb.part_bound;
       __hip_atomic_store(tb.part_overflow, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -294,17 +294,16 @@ def test_rccl_transport_on_a_one_rank_communicator(tmp_path):
         assert np.array_equal(fused[key], rccl[key]), key
 
 
-def test_missing_rank_is_an_error_not_a_hang(tmp_path):
+def test_missing_rank_is_an_error_not_a_hang(tmp_path, monkeypatch):
     import lidar_imu_init_amd as lii
+    monkeypatch.setenv("LII_MAILBOX_TIMEOUT_S", "30,1.0")  # (read when the handle is created)
     r = lii.Registrar(max_scan_points=1024, max_map_points=1024)
     uid = r.comm_unique_id()
-    os.environ["LII_MAILBOX_TIMEOUT_S"] = "30,1.0"
     try:
         with pytest.raises(lii.LIIError):
             r.comm_init(2, 0, uid, "mailbox")  # the peer never arrives: the rendezvous gives up
         assert r.comm_transport() == "none"
     finally:
-        del os.environ["LII_MAILBOX_TIMEOUT_S"]
         r.close()
 
 
