@@ -39,9 +39,9 @@ int fail(lii_handle h, int code, const std::string& msg) {
 int kp_mark(lii_handle h, int kind, int it) {
   if (h->prof.prof_mode != 3) return LII_OK;
   if (h->prof.kp_n >= (int)h->prof.kp_ev.size()) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, kProfEventFlags) != hipSuccess) return fail(h, LII_ERR_HIP, "hipEventCreate (kernel profile)");
-    h->prof.kp_ev.push_back(e);
+    lii::Event e;
+    if (e.create(kProfEventFlags) != hipSuccess) return fail(h, LII_ERR_HIP, "hipEventCreate (kernel profile)");
+    h->prof.kp_ev.push_back(std::move(e));
     h->prof.kp_kind.push_back(0);
   }
   if (hipEventRecord(h->prof.kp_ev[size_t(h->prof.kp_n)], h->stream) != hipSuccess) return fail(h, LII_ERR_HIP, "hipEventRecord (kernel profile)");
@@ -312,6 +312,164 @@ int lii_device_count(int* count) {
   return LII_OK;
 }
 
+// lii_create's device part: every resource a handle has from the start.  A failure leaves the handle to its caller, which deletes it.
+static int create_resources(lii_handle h) {
+  const lii_config* cfg = &h->cfg;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipDeviceProp_t prop;
+  HIPCHK(h, hipGetDeviceProperties(&prop, h->device));
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+    return fail(h, LII_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+  HIPCHK(h, h->stream.create(hipStreamNonBlocking));
+  const size_t N = size_t(cfg->max_scan_points), M = size_t(cfg->max_map_points);
+  const size_t NM = std::max(N, M);
+  HIPCHK(h, h->d_map_unsorted.alloc(M));
+  HIPCHK(h, h->d_map.alloc(M));
+  h->pts_cap = (unsigned int)std::min<size_t>(3 * M + 65536, 0x7FFFFFF0u);
+  HIPCHK(h, h->d_pts.alloc(size_t(h->pts_cap)));
+  HIPCHK(h, h->d_work.alloc(std::min<size_t>(10 * NM + 4096, 0x7FFFFFF0u)));
+  h->work_cap = (unsigned int)h->d_work.size();
+  HIPCHK(h, h->d_ins_e.alloc(NM));
+  HIPCHK(h, h->d_ins_e2.alloc(NM));
+  HIPCHK(h, h->d_mapctr.alloc(kMapCtrWords + 8));  // (+ the list counts of lii_map_incremental: one copy brings both to the host)
+  HIPCHK(h, hipMemset(h->d_mapctr, 0, sizeof(int) * (kMapCtrWords + 8)));
+  h->d_counts = h->d_mapctr + kMapCtrWords;
+  HIPCHK(h, h->d_keys_a.alloc(M));
+  HIPCHK(h, h->d_keys_b.alloc(M));
+  HIPCHK(h, h->d_keys_c.alloc(M));
+  HIPCHK(h, h->d_idx_a.alloc(M));
+  HIPCHK(h, h->d_idx_b.alloc(M));
+  HIPCHK(h, h->d_blocks.alloc(4096));
+  h->block_mask = (unsigned int)h->d_blocks.size() - 1;
+  const size_t cap_blocks = std::max<size_t>(4096, M / 64);
+  HIPCHK(h, h->d_cells.alloc(cap_blocks * 512));
+  HIPCHK(h, h->d_cell_cap.alloc(cap_blocks * 512));
+  HIPCHK(h, h->d_tp.alloc(cap_blocks * 512));
+  HIPCHK(h, h->d_cs_a.alloc(cap_blocks * 512));
+  HIPCHK(h, h->d_cs_b.alloc(cap_blocks * 512));
+  HIPCHK(h, h->d_block_key.alloc(cap_blocks));
+  h->cells_cap_blocks = h->d_block_key.size();
+  HIPCHK(h, hipMemset(h->d_cells, 0, sizeof(uint2) * h->cells_cap_blocks * 512));
+  HIPCHK(h, hipMemset(h->d_cell_cap, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
+  HIPCHK(h, hipMemset(h->d_tp, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
+  HIPCHK(h, h->d_counter.alloc(4));
+  HIPCHK(h, h->d_tomb.alloc(size_t(h->pts_cap)));
+  HIPCHK(h, hipMemset(h->d_tomb, 0, size_t(h->pts_cap)));
+  HIPCHK(h, h->d_ins.alloc(M));
+  HIPCHK(h, h->d_batch.alloc(M));
+  HIPCHK(h, h->d_dropped.alloc(NM));
+  h->drop_cap = (unsigned int)h->d_dropped.size();
+  HIPCHK(h, h->d_ins_c.alloc(M));
+  HIPCHK(h, h->d_u32_a.alloc(NM));
+  HIPCHK(h, h->d_u32_b.alloc(NM));
+  HIPCHK(h, hipMemset(h->d_u32_b, 0, sizeof(unsigned int) * NM));  // (k_map_decide's block words: run number 0 is never used)
+  HIPCHK(h, h->d_u32_c.alloc(NM));
+  {
+    const size_t slots = add_hash_slots(int(N));
+    HIPCHK(h, h->d_ah_key.alloc(slots)); HIPCHK(h, h->d_ah_best.alloc(slots)); HIPCHK(h, h->d_ah_slot.alloc(N));
+    HIPCHK(h, hipMemset(h->d_ah_key, 0xFF, 8 * slots)); HIPCHK(h, hipMemset(h->d_ah_best, 0xFF, 8 * slots));
+  }
+  HIPCHK(h, h->d_list_add.alloc(N));
+  HIPCHK(h, h->d_list_nodown.alloc(N));
+  HIPCHK(h, h->n_map_pinned.alloc(16, hipHostMallocDefault));
+  h->n_map_pinned[0] = 0;
+  HIPCHK(h, h->d_sort_temp.alloc(sort_temp_bytes(int(std::max<size_t>(NM, h->cells_cap_blocks * 512)))));
+  HIPCHK(h, h->d_scan.alloc(N));
+  HIPCHK(h, h->d_body.alloc(N));
+  HIPCHK(h, h->d_world.alloc(N));
+  HIPCHK(h, h->d_nbr.alloc(N * kMatch));
+  HIPCHK(h, h->d_nbr_count.alloc(N));
+  HIPCHK(h, h->d_plane.alloc(N * 4));
+  HIPCHK(h, h->d_selected.alloc(N));
+  HIPCHK(h, h->d_nbody.alloc(4));
+  {
+    // control block and pose table share one allocation so that lii_scan_register uploads both with one copy
+    HIPCHK(h, h->d_ctrl_poses.alloc(kCtrlBytes + sizeof(lii_pose6d) * 1024 + 1024));
+    h->d_ctrl = reinterpret_cast<IekfCtrl*>(h->d_ctrl_poses.get());
+    h->d_poses = reinterpret_cast<double*>(h->d_ctrl_poses + kCtrlBytes);
+  }
+  HIPCHK(h, h->d_pose.alloc(1));
+  HIPCHK(h, h->h_ctrl_poses.alloc(kCtrlBytes + sizeof(lii_pose6d) * 1024 + 1024, hipHostMallocDefault));
+  h->h_ctrl = reinterpret_cast<IekfCtrl*>(h->h_ctrl_poses.get());
+  h->h_poses = reinterpret_cast<lii_pose6d*>(h->h_ctrl_poses + kCtrlBytes);
+  static_assert(sizeof(lii::GateState) == 8, "the state word's allocation is 64 bytes");
+  HIPCHK(h, h->pre.state.alloc(8, hipHostMallocMapped));
+  std::memset(h->pre.state, 0, 64);
+  HIPCHK(h, h->pre.d_ring.alloc(size_t(lii::kGateRing) * lii::kGateLines * 8));
+  HIPCHK(h, hipMemset(h->pre.d_ring, 0, sizeof(double) * size_t(lii::kGateRing) * lii::kGateLines * 8));
+  HIPCHK(h, h->pre.d_flag.alloc(8));
+  HIPCHK(h, hipMemset(h->pre.d_flag, 0, 64));
+  {  // the host writes the record straight into device memory: only where the whole of it is visible to the host (large BAR)
+    int large_bar = 0;
+    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) large_bar = 0;
+    h->pre.enabled = h->pre.enabled && large_bar != 0;
+  }
+  HIPCHK(h, h->h_res.alloc(1, hipHostMallocMapped));
+  std::memset(h->h_res, 0, sizeof(IekfResult));
+  partition_refresh(h);
+  HIPCHK(h, h->ev_poses.create(hipEventDisableTiming));
+  HIPCHK(h, h->ev_stage.create(hipEventDisableTiming));
+  HIPCHK(h, h->ev_mapflag.create(hipEventDisableTiming));
+  HIPCHK(h, h->h_mapflag.alloc(64, hipHostMallocMapped));  // (written by k_map_publish)
+  std::memset(h->h_mapflag, 0, 256);
+  HIPCHK(h, h->ev_lists.create(hipEventDisableTiming));
+  HIPCHK(h, hipMemset(h->d_counter, 0, 16));
+  h->partial_stride = register_blocks(int(N)) + std::max(lii::kCompletionBlocks, lii::kCompletionBlocksPre) + 8;  // (+ the columns of the fit launches' completion workgroups)
+  HIPCHK(h, h->d_flags.alloc(4 + 16 * lii::kListCap));  // 2 counters (+ 2 pad), 2 x kListCap entries of two float4
+  HIPCHK(h, hipMemset(h->d_flags, 0, sizeof(int) * (4 + 16 * lii::kListCap)));
+  HIPCHK(h, h->d_partials.alloc(size_t(h->partial_stride) * kNormalEq));
+  HIPCHK(h, h->d_out91.alloc(256));  // [0,91): local sums, [128,219): all-reduced sums (sharded scans)
+  HIPCHK(h, h->d_gran.alloc(256));
+  HIPCHK(h, hipMemset(h->d_gran, 0, 8 * 256));
+  HIPCHK(h, h->d_extent.alloc(4));
+  HIPCHK(h, h->d_mm.alloc(16));
+  HIPCHK(h, h->d_bbox_rows.alloc((N / 256 + 2) * 8));
+  {
+    const unsigned long long e0[4] = {~0ull, 0ull, ~0ull, 0ull};
+    const unsigned int m0[16] = {~0u, ~0u, ~0u, 0, 0, 0, 0, 0, ~0u, ~0u, ~0u, 0, 0, 0, 0, 0};
+    HIPCHK(h, hipMemcpy(h->d_extent, e0, sizeof(e0), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_mm, m0, sizeof(m0), hipMemcpyHostToDevice));
+  }
+  HIPCHK(h, h->d_vkeys_a.alloc(N));
+  HIPCHK(h, h->d_vkeys_b.alloc(N));
+  HIPCHK(h, h->d_vidx_b.alloc(N));
+  HIPCHK(h, h->d_vcomp.alloc(N));
+  HIPCHK(h, h->d_vsplit.alloc(2048 + 4096));  // splitters | samples
+  HIPCHK(h, h->d_vhist.alloc(voxel_sort_hist_elems((int)N)));
+  HIPCHK(h, hipMemset(h->d_vhist, 0, sizeof(unsigned int) * voxel_sort_hist_elems((int)N)));
+  HIPCHK(h, h->d_vbucket.alloc(N));
+  HIPCHK(h, h->d_vpcl_in.alloc(N));
+  HIPCHK(h, h->d_vpcl_out.alloc(N));
+  {
+    const size_t slots = voxel_hash_slots((int)N);
+    HIPCHK(h, h->vh_slots.alloc(64 * slots));
+    h->vh.slots = h->vh_slots;
+    launch_voxel_hash_clear(h->vh, slots, h->stream);
+    HIPCHK(h, h->vh_slot_of.alloc(N)); HIPCHK(h, h->vh_next.alloc(N));
+    HIPCHK(h, h->vh_counts.alloc(N / 256 + 8)); HIPCHK(h, hipMemset(h->vh_counts, 0, 8 * (N / 256 + 8)));
+    HIPCHK(h, h->vh_crowded.alloc(4));
+    HIPCHK(h, hipMemset(h->vh_crowded, 0, 16));
+    h->vh.slot_of = h->vh_slot_of; h->vh.next = h->vh_next; h->vh.counts = h->vh_counts; h->vh.crowded = h->vh_crowded;
+    HIPCHK(h, h->h_vh_crowded.alloc(16, hipHostMallocDefault));
+    *h->h_vh_crowded = 0;
+    HIPCHK(h, h->ev_vh.create(hipEventDisableTiming));
+  }
+  HIPCHK(h, h->cal.d_cal_params.alloc(64));
+  HIPCHK(h, h->cal.d_cal_out.alloc(128));
+  HIPCHK(h, h->h_stage.alloc(NM * kMatch, hipHostMallocDefault));  // large enough for the neighbour download too
+  HIPCHK(h, h->h_small.alloc(32768, hipHostMallocDefault));
+  for (int i = 0; i < 4; i++) HIPCHK(h, h->prof.ev[i].create(kProfEventFlags));
+  for (int i = 0; i < 32; i++) HIPCHK(h, h->prof.ev_it[i].create(kProfEventFlags));
+  launch_table_clear(h->d_blocks, (unsigned int)h->d_blocks.size(), h->stream);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return LII_OK;
+}
+// A handle that could not be completed: its members release what had been made (the message is the thread's, lii_last_error(NULL)).
+static int fail_create(lii_handle h, int rc) {
+  delete h;
+  return rc;
+}
+
 int lii_create(const lii_config* cfg, lii_handle* out) {
   if (!cfg || !out || cfg->struct_size != (int32_t)sizeof(lii_config)) return fail(nullptr, LII_ERR_INVALID, "bad lii_config");
   if (cfg->max_scan_points <= 0 || cfg->max_map_points <= 0) return fail(nullptr, LII_ERR_INVALID, "capacities must be > 0");
@@ -331,165 +489,8 @@ int lii_create(const lii_config* cfg, lii_handle* out) {
   read_switches(h);
   h->ds = h->cfg.map_downsample_size;
   h->device = cfg->device;
-#define CK(call)                                                                  \
-  do {                                                                            \
-    hipError_t e_ = (call);                                                       \
-    if (e_ != hipSuccess) {                                                       \
-      int rc_ = fail(nullptr, LII_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-      lii_destroy(h);                                                             \
-      return rc_;                                                                 \
-    }                                                                             \
-  } while (0)
-  CK(hipSetDevice(h->device));
-  hipDeviceProp_t prop;
-  CK(hipGetDeviceProperties(&prop, h->device));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    int rc = fail(nullptr, LII_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    lii_destroy(h);
-    return rc;
-  }
-  CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  const size_t N = size_t(cfg->max_scan_points), M = size_t(cfg->max_map_points);
-  const size_t NM = std::max(N, M);
-  CK(dmalloc(&h->d_map_unsorted, M));
-  CK(dmalloc(&h->d_map, M));
-  h->pts_cap = (unsigned int)std::min<size_t>(3 * M + 65536, 0x7FFFFFF0u);
-  CK(dmalloc(&h->d_pts, size_t(h->pts_cap)));
-  h->work_cap = (unsigned int)std::min<size_t>(10 * NM + 4096, 0x7FFFFFF0u);
-  CK(dmalloc(&h->d_work, size_t(h->work_cap)));
-  CK(dmalloc(&h->d_ins_e, NM));
-  CK(dmalloc(&h->d_ins_e2, NM));
-  CK(dmalloc(&h->d_mapctr, kMapCtrWords + 8));  // (+ the list counts of lii_map_incremental: one copy brings both to the host)
-  CK(hipMemset(h->d_mapctr, 0, sizeof(int) * (kMapCtrWords + 8)));
-  h->d_counts = h->d_mapctr + kMapCtrWords;
-  CK(dmalloc(&h->d_keys_a, M));
-  CK(dmalloc(&h->d_keys_b, M));
-  CK(dmalloc(&h->d_keys_c, M));
-  CK(dmalloc(&h->d_idx_a, M));
-  CK(dmalloc(&h->d_idx_b, M));
-  h->blocks_cap = 4096;
-  h->block_mask = h->blocks_cap - 1;
-  CK(dmalloc(&h->d_blocks, size_t(h->blocks_cap)));
-  h->cells_cap_blocks = std::max<size_t>(4096, M / 64);
-  CK(dmalloc(&h->d_cells, h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_cell_cap, h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_tp, h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_cs_a, h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_cs_b, h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_block_key, h->cells_cap_blocks));
-  CK(hipMemset(h->d_cells, 0, sizeof(uint2) * h->cells_cap_blocks * 512));
-  CK(hipMemset(h->d_cell_cap, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
-  CK(hipMemset(h->d_tp, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
-  CK(dmalloc(&h->d_counter, 4));
-  CK(dmalloc(&h->d_tomb, size_t(h->pts_cap)));
-  CK(hipMemset(h->d_tomb, 0, size_t(h->pts_cap)));
-  CK(dmalloc(&h->d_ins, M));
-  CK(dmalloc(&h->d_batch, M));
-  h->drop_cap = (unsigned int)NM;
-  CK(dmalloc(&h->d_dropped, NM));
-  CK(dmalloc(&h->d_ins_c, M));
-  CK(dmalloc(&h->d_u32_a, NM));
-  CK(dmalloc(&h->d_u32_b, NM));
-  CK(hipMemset(h->d_u32_b, 0, sizeof(unsigned int) * NM));  // (k_map_decide's block words: run number 0 is never used)
-  CK(dmalloc(&h->d_u32_c, NM));
-  {
-    const size_t slots = add_hash_slots(int(N));
-    CK(dmalloc(&h->d_ah_key, slots)); CK(dmalloc(&h->d_ah_best, slots)); CK(dmalloc(&h->d_ah_slot, N));
-    CK(hipMemset(h->d_ah_key, 0xFF, 8 * slots)); CK(hipMemset(h->d_ah_best, 0xFF, 8 * slots));
-  }
-  CK(dmalloc(&h->d_list_add, N));
-  CK(dmalloc(&h->d_list_nodown, N));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->n_map_pinned), 64, hipHostMallocDefault));
-  h->n_map_pinned[0] = 0;
-  h->sort_temp_bytes = sort_temp_bytes(int(std::max<size_t>(NM, h->cells_cap_blocks * 512)));
-  CK(hipMalloc(&h->d_sort_temp, h->sort_temp_bytes));
-  CK(dmalloc(&h->d_scan, N));
-  CK(dmalloc(&h->d_body, N));
-  CK(dmalloc(&h->d_world, N));
-  CK(dmalloc(&h->d_nbr, N * kMatch));
-  CK(dmalloc(&h->d_nbr_count, N));
-  CK(dmalloc(&h->d_plane, N * 4));
-  CK(dmalloc(&h->d_selected, N));
-  CK(dmalloc(&h->d_nbody, 4));
-  {
-    // control block and pose table share one allocation so that lii_scan_register uploads both with one copy
-    void* p = nullptr;
-    CK(hipMalloc(&p, kCtrlBytes + sizeof(lii_pose6d) * 1024 + 1024));
-    h->d_ctrl = static_cast<IekfCtrl*>(p);
-    h->d_poses = reinterpret_cast<double*>(static_cast<char*>(p) + kCtrlBytes);
-  }
-  CK(dmalloc(&h->d_pose, 1));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_ctrl), kCtrlBytes + sizeof(lii_pose6d) * 1024 + 1024, hipHostMallocDefault));
-  h->h_poses = reinterpret_cast<lii_pose6d*>(reinterpret_cast<char*>(h->h_ctrl) + kCtrlBytes);
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->pre.state), 64, hipHostMallocMapped));
-  std::memset(h->pre.state, 0, 64);
-  CK(dmalloc(&h->pre.d_ring, size_t(lii::kGateRing) * lii::kGateLines * 8));
-  CK(hipMemset(h->pre.d_ring, 0, sizeof(double) * size_t(lii::kGateRing) * lii::kGateLines * 8));
-  CK(dmalloc(&h->pre.d_flag, 8));
-  CK(hipMemset(h->pre.d_flag, 0, 64));
-  {  // the host writes the record straight into device memory: only where the whole of it is visible to the host (large BAR)
-    int large_bar = 0;
-    if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) large_bar = 0;
-    h->pre.enabled = h->pre.enabled && large_bar != 0;
-  }
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_res), sizeof(IekfResult), hipHostMallocMapped));
-  std::memset(h->h_res, 0, sizeof(IekfResult));
-  partition_refresh(h);
-  CK(hipEventCreateWithFlags(&h->ev_poses, hipEventDisableTiming));
-  CK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-  CK(hipEventCreateWithFlags(&h->ev_mapflag, hipEventDisableTiming));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_mapflag), 256, hipHostMallocMapped));  // (written by k_map_publish)
-  std::memset(h->h_mapflag, 0, 256);
-  CK(hipEventCreateWithFlags(&h->ev_lists, hipEventDisableTiming));
-  CK(hipMemset(h->d_counter, 0, 16));
-  h->partial_stride = register_blocks(int(N)) + std::max(lii::kCompletionBlocks, lii::kCompletionBlocksPre) + 8;  // (+ the columns of the fit launches' completion workgroups)
-  CK(dmalloc(&h->d_flags, 4 + 16 * lii::kListCap));  // 2 counters (+ 2 pad), 2 x kListCap entries of two float4
-  CK(hipMemset(h->d_flags, 0, sizeof(int) * (4 + 16 * lii::kListCap)));
-  CK(dmalloc(&h->d_partials, size_t(h->partial_stride) * kNormalEq));
-  CK(dmalloc(&h->d_out91, 256));  // [0,91): local sums, [128,219): all-reduced sums (sharded scans)
-  CK(dmalloc(&h->d_gran, 256));
-  CK(hipMemset(h->d_gran, 0, 8 * 256));
-  CK(dmalloc(&h->d_extent, 4));
-  CK(dmalloc(&h->d_mm, 16));
-  CK(dmalloc(&h->d_bbox_rows, (N / 256 + 2) * 8));
-  {
-    const unsigned long long e0[4] = {~0ull, 0ull, ~0ull, 0ull};
-    const unsigned int m0[16] = {~0u, ~0u, ~0u, 0, 0, 0, 0, 0, ~0u, ~0u, ~0u, 0, 0, 0, 0, 0};
-    CK(hipMemcpy(h->d_extent, e0, sizeof(e0), hipMemcpyHostToDevice));
-    CK(hipMemcpy(h->d_mm, m0, sizeof(m0), hipMemcpyHostToDevice));
-  }
-  CK(dmalloc(&h->d_vkeys_a, N));
-  CK(dmalloc(&h->d_vkeys_b, N));
-  CK(dmalloc(&h->d_vidx_b, N));
-  CK(dmalloc(&h->d_vcomp, N));
-  CK(dmalloc(&h->d_vsplit, 2048 + 4096));  // splitters | samples
-  CK(dmalloc(&h->d_vhist, voxel_sort_hist_elems((int)N)));
-  CK(hipMemset(h->d_vhist, 0, sizeof(unsigned int) * voxel_sort_hist_elems((int)N)));
-  CK(dmalloc(&h->d_vbucket, N));
-  CK(dmalloc(&h->d_vpcl_in, N));
-  CK(dmalloc(&h->d_vpcl_out, N));
-  {
-    const size_t slots = voxel_hash_slots((int)N);
-    CK(hipMalloc(&h->vh.slots, 64 * slots));
-    launch_voxel_hash_clear(h->vh, slots, h->stream);
-    CK(dmalloc(&h->vh.slot_of, N)); CK(dmalloc(&h->vh.next, N));
-    CK(dmalloc(&h->vh.counts, N / 256 + 8)); CK(hipMemset(h->vh.counts, 0, 8 * (N / 256 + 8)));
-    CK(dmalloc(&h->vh.crowded, 4));
-    CK(hipMemset(h->vh.crowded, 0, 16));
-    CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_vh_crowded), 64, hipHostMallocDefault));
-    *h->h_vh_crowded = 0;
-    CK(hipEventCreateWithFlags(&h->ev_vh, hipEventDisableTiming));
-  }
-  CK(dmalloc(&h->cal.d_cal_params, 64));
-  CK(dmalloc(&h->cal.d_cal_out, 128));
-  h->h_stage_elems = NM * kMatch;  // large enough for the neighbour download too
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), sizeof(float4) * h->h_stage_elems, hipHostMallocDefault));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_small), sizeof(double) * 32768, hipHostMallocDefault));
-  for (int i = 0; i < 4; i++) CK(hipEventCreateWithFlags(&h->prof.ev[i], kProfEventFlags));
-  for (int i = 0; i < 32; i++) CK(hipEventCreateWithFlags(&h->prof.ev_it[i], kProfEventFlags));
-  launch_table_clear(h->d_blocks, h->blocks_cap, h->stream);
-  CK(hipStreamSynchronize(h->stream));
-#undef CK
+  const int rc = create_resources(h);
+  if (rc != LII_OK) return fail_create(h, rc);
   *out = h;
   return LII_OK;
 }
@@ -499,6 +500,7 @@ int lii_destroy(lii_handle h) {
   if (!h) return LII_OK;
   (void)hipSetDevice(h->device);
   if (h->net.comm) ncclCommDestroy(h->net.comm);
+  if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   if (h->map_stream) (void)hipStreamSynchronize(h->map_stream);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
 #ifdef LII_FALLBACK_TRACE
@@ -543,45 +545,8 @@ int lii_destroy(lii_handle h) {
     std::fprintf(stderr, "[libliinit_hip] map update, host us per scan: waited for the update in flight %.1f, enqueued behind the passes %.1f\n",
                  h->prof.host_map_us[0] / h->prof.host_us[4], h->prof.host_map_us[1] / h->prof.host_us[4]);
   mailbox_close(&h->net.mailbox);
-  if (h->net.d_mb_seq) (void)hipFree(h->net.d_mb_seq);
-  if (h->net.d_gather_ticket) (void)hipFree(h->net.d_gather_ticket);
-  if (h->net.d_gx) (void)hipFree(h->net.d_gx);
-  if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-  for (hipEvent_t e : h->prof.kp_ev) (void)hipEventDestroy(e);
-  if (h->ev_next) (void)hipEventDestroy(h->ev_next);
-  if (h->ev_scan_free) (void)hipEventDestroy(h->ev_scan_free);
-  if (h->h_stage_next) (void)hipHostFree(h->h_stage_next);
-  if (h->d_scan_next) (void)hipFree(h->d_scan_next);
-  void* dev[] = {h->d_dropped, h->d_pts, h->d_cell_cap, h->d_tp, h->d_cs_a, h->d_cs_b, h->d_work, h->d_ins_e, h->d_ins_e2, h->d_mapctr, h->d_map_unsorted, h->d_map, h->d_keys_a, h->d_keys_b, h->d_keys_c, h->d_idx_a, h->d_idx_b, h->d_blocks, h->d_cells, h->d_win, h->d_block_key,
-                 h->d_counter, h->d_tomb, h->d_batch, h->d_ins, h->d_ins_c, h->d_u32_a, h->d_u32_b, h->d_u32_c, h->d_list_add, h->d_list_nodown, h->d_ah_key, h->d_ah_best, h->d_ah_slot, h->d_sort_temp, h->d_scan, h->d_body, h->d_world, h->d_nbr, h->d_nbr_count, h->d_plane,
-                 h->d_selected, h->d_nbody, h->d_ctrl, h->d_pose, h->d_partials, h->d_out91, h->d_gran, h->d_extent, h->d_mm, h->d_bbox_rows, h->d_vkeys_a, h->d_vkeys_b,
-                 h->d_vidx_b, h->d_vcomp, h->d_vsplit, h->d_vhist, h->d_vbucket, h->d_vpcl_in, h->d_vpcl_out, h->vh.slots, h->vh.slot_of, h->vh.next, h->vh.counts, h->vh.crowded, h->cal.d_cal_imu, h->cal.d_cal_lidar, h->cal.d_cal_params,
-                 h->cal.d_cal_out, h->d_flags};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
   if (h->ingest) ingest_destroy(h->ingest);
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
-  if (h->h_small) (void)hipHostFree(h->h_small);
-  if (h->h_ctrl) (void)hipHostFree(h->h_ctrl);
-  if (h->h_res) (void)hipHostFree(h->h_res);
-  if (h->pre.state) (void)hipHostFree(h->pre.state);
-  if (h->pre.d_ring) (void)hipFree(h->pre.d_ring);
-  if (h->pre.d_flag) (void)hipFree(h->pre.d_flag);
-  if (h->ev_poses) (void)hipEventDestroy(h->ev_poses);
-  if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
-  if (h->ev_mapflag) (void)hipEventDestroy(h->ev_mapflag);
-  if (h->ev_vh) (void)hipEventDestroy(h->ev_vh);
-  if (h->h_vh_crowded) (void)hipHostFree(h->h_vh_crowded);
-  if (h->h_mapflag) (void)hipHostFree(h->h_mapflag);
-  if (h->ev_lists) (void)hipEventDestroy(h->ev_lists);
-  if (h->n_map_pinned) (void)hipHostFree(h->n_map_pinned);
-  for (int i = 0; i < 4; i++)
-    if (h->prof.ev[i]) (void)hipEventDestroy(h->prof.ev[i]);
-  for (int i = 0; i < 32; i++)
-    if (h->prof.ev_it[i]) (void)hipEventDestroy(h->prof.ev_it[i]);
-  if (h->map_stream) (void)hipStreamDestroy(h->map_stream);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // (the members release the buffers and events, then the streams: lii_context.h)
   return LII_OK;
 }
 
@@ -615,6 +580,19 @@ int lii_synchronize(lii_handle h) {
 }
 
 // ------------------------------------------------------------------------------------------------ scan
+// A caller's records ((x, y, z) at the head, the time at an offset, `stride_bytes` apart) -> the (x, y, z, t) records of a staging buffer.
+static void pack_scan(float4* dst, const char* src, int n, int stride_bytes, int time_offset_bytes) {
+  if (stride_bytes == 16 && time_offset_bytes == 12) {
+    if (n > 0) std::memcpy(dst, src, sizeof(float4) * size_t(n));  // already (x, y, z, t) records
+    return;
+  }
+  for (int i = 0; i < n; i++) {
+    const float* f = reinterpret_cast<const float*>(src + size_t(i) * stride_bytes);
+    float t;
+    std::memcpy(&t, src + size_t(i) * stride_bytes + time_offset_bytes, 4);
+    dst[i] = make_float4(f[0], f[1], f[2], t);
+  }
+}
 int lii_scan_upload(lii_handle h, const void* points, int32_t n, int32_t stride_bytes, int32_t time_offset_bytes) {
   if (h) h->scan_buf_idle = false;  // (work on the current scan buffer goes out)
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
@@ -623,16 +601,7 @@ int lii_scan_upload(lii_handle h, const void* points, int32_t n, int32_t stride_
   if (n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_scan_upload: n > max_scan_points");
   const char* src = static_cast<const char*>(points);
   HIPCHK(h, hipEventSynchronize(h->ev_stage));  // the previous upload has left the staging buffer
-  if (stride_bytes == 16 && time_offset_bytes == 12) {
-    if (n > 0) std::memcpy(h->h_stage, src, sizeof(float4) * size_t(n));  // already (x, y, z, t) records
-  } else {
-    for (int i = 0; i < n; i++) {
-      const float* f = reinterpret_cast<const float*>(src + size_t(i) * stride_bytes);
-      float t;
-      std::memcpy(&t, src + size_t(i) * stride_bytes + time_offset_bytes, 4);
-      h->h_stage[i] = make_float4(f[0], f[1], f[2], t);
-    }
-  }
+  pack_scan(h->h_stage, src, n, stride_bytes, time_offset_bytes);
   if (n > 0) HIPCHK(h, hipMemcpyAsync(h->d_scan, h->h_stage, sizeof(float4) * size_t(n), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(h->ev_stage, h->stream));
   h->n_scan = n;
@@ -651,10 +620,10 @@ int lii_scan_upload_next(lii_handle h, const void* points, int32_t n, int32_t st
     return fail(h, LII_ERR_INVALID, "lii_scan_upload_next: bad arguments");
   if (n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_scan_upload_next: n > max_scan_points");
   if (!h->copy_stream) {
-    HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_next, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_scan_free, hipEventDisableTiming));
-    HIPCHK(h, dmalloc(&h->d_scan_next, size_t(h->cfg.max_scan_points)));
+    HIPCHK(h, h->copy_stream.create(hipStreamNonBlocking));
+    HIPCHK(h, h->ev_next.create(hipEventDisableTiming));
+    HIPCHK(h, h->ev_scan_free.create(hipEventDisableTiming));
+    HIPCHK(h, h->d_scan_next.alloc(size_t(h->cfg.max_scan_points)));
   }
   if (h->n_scan_next >= 0) HIPCHK(h, hipEventSynchronize(h->ev_next));  // a scan that was never advanced to is replaced
   h->n_scan_next = -1;
@@ -676,18 +645,8 @@ int lii_scan_upload_next(lii_handle h, const void* points, int32_t n, int32_t st
   }
   if (n > 0 && !direct) {
     if (!h->h_stage_next)
-      HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_stage_next), sizeof(float4) * size_t(h->cfg.max_scan_points), hipHostMallocDefault));
-    const char* p = static_cast<const char*>(points);
-    if (stride_bytes == 16 && time_offset_bytes == 12) {
-      std::memcpy(h->h_stage_next, p, sizeof(float4) * size_t(n));
-    } else {
-      for (int i = 0; i < n; i++) {
-        const float* f = reinterpret_cast<const float*>(p + size_t(i) * stride_bytes);
-        float t;
-        std::memcpy(&t, p + size_t(i) * stride_bytes + time_offset_bytes, 4);
-        h->h_stage_next[i] = make_float4(f[0], f[1], f[2], t);
-      }
-    }
+      HIPCHK(h, h->h_stage_next.alloc(size_t(h->cfg.max_scan_points), hipHostMallocDefault));
+    pack_scan(h->h_stage_next, static_cast<const char*>(points), n, stride_bytes, time_offset_bytes);
     src = h->h_stage_next;
   }
   // the buffer being written was the current scan of an earlier call: whatever the compute stream still has to do with it

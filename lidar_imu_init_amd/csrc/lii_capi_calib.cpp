@@ -12,11 +12,10 @@ int lii_calib_set_buffers(lii_handle h, const lii_calib_state* imu, const lii_ca
   if (!h || !imu || !lidar || n <= 0) return fail(h, LII_ERR_INVALID, "lii_calib_set_buffers: bad arguments");
   static_assert(sizeof(lii_calib_state) == 22 * sizeof(double), "lii_calib_state layout");
   if (n > h->cal.n_cal || !h->cal.d_cal_imu) {
-    if (h->cal.d_cal_imu) (void)hipFree(h->cal.d_cal_imu);
-    if (h->cal.d_cal_lidar) (void)hipFree(h->cal.d_cal_lidar);
-    h->cal.d_cal_imu = h->cal.d_cal_lidar = nullptr;
-    HIPCHK(h, dmalloc(&h->cal.d_cal_imu, size_t(n) * 22));
-    HIPCHK(h, dmalloc(&h->cal.d_cal_lidar, size_t(n) * 22));
+    h->cal.d_cal_imu.reset();
+    h->cal.d_cal_lidar.reset();
+    HIPCHK(h, h->cal.d_cal_imu.alloc(size_t(n) * 22));
+    HIPCHK(h, h->cal.d_cal_lidar.alloc(size_t(n) * 22));
   }
   HIPCHK(h, hipMemcpyAsync(h->cal.d_cal_imu, imu, sizeof(lii_calib_state) * size_t(n), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->cal.d_cal_lidar, lidar, sizeof(lii_calib_state) * size_t(n), hipMemcpyHostToDevice, h->stream));

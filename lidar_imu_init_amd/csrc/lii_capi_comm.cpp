@@ -43,10 +43,8 @@ struct GxLayout {
 int gx_prepare(lii_handle h, int N, GxLayout* L) {
   const size_t block = size_t(kGatherHeaderBytes) + sizeof(float4) * size_t(h->cfg.max_scan_points);
   if (!h->net.d_gx || h->net.gx_block != block || h->net.gx_ranks != N) {
-    if (h->net.d_gx) HIPCHK(h, hipFree(h->net.d_gx));
-    h->net.d_gx = nullptr;
     const size_t bytes = block * (size_t(N) + 1) + size_t(N) * kGatherHeaderBytes + sizeof(void*) * (size_t(N) + 1);
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_gx), bytes));
+    HIPCHK(h, h->net.d_gx.grow(bytes));
     HIPCHK(h, hipMemset(h->net.d_gx, 0, bytes));
     h->net.gx_block = block; h->net.gx_ranks = N;
     std::vector<unsigned char*> tab(size_t(N) + 1);
@@ -54,7 +52,7 @@ int gx_prepare(lii_handle h, int N, GxLayout* L) {
     for (int r = 0; r < N; r++) tab[size_t(r) + 1] = h->net.d_gx + block;  // the gathered blocks (every entry: this rank's local area)
     HIPCHK(h, hipMemcpy(h->net.d_gx + block * (size_t(N) + 1) + size_t(N) * kGatherHeaderBytes, tab.data(), sizeof(void*) * tab.size(), hipMemcpyHostToDevice));
     if (!h->net.d_gather_ticket) {
-      HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_gather_ticket), sizeof(unsigned int)));
+      HIPCHK(h, h->net.d_gather_ticket.alloc(1));
       HIPCHK(h, hipMemset(h->net.d_gather_ticket, 0, sizeof(unsigned int)));
     }
   }
@@ -120,7 +118,7 @@ void comm_drop(lii_handle h) {
   // k_lists_collect's `v >= seq` on the fresh rank's side would never see it arrive.  The RCCL form's local areas
   // hold headers of the old numbering: dropped with it (lists_exchange_rccl lays them out again, zeroed).
   h->net.gather_seq = 0;
-  if (h->net.d_gx) { (void)hipFree(h->net.d_gx); h->net.d_gx = nullptr; h->net.gx_block = 0; h->net.gx_ranks = 0; }
+  h->net.d_gx.reset();
   if (h->net.d_gather_ticket) (void)hipMemset(h->net.d_gather_ticket, 0, sizeof(unsigned int));
   partition_refresh(h);
 }
@@ -135,9 +133,9 @@ int comm_init(lii_handle h, int32_t n_ranks, int32_t rank, const uint8_t id_in[1
   // the three-launch form of the loop - final sum, ncclAllReduce, solve - can be exercised on one device
   if (n_ranks == 1 && transport != LII_COMM_RCCL) return LII_OK;
   if (transport != LII_COMM_RCCL) {
-    if (!h->net.d_mb_seq) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_mb_seq), sizeof(unsigned long long)));
+    if (!h->net.d_mb_seq) HIPCHK(h, h->net.d_mb_seq.alloc(1));
     HIPCHK(h, hipMemset(h->net.d_mb_seq, 0, sizeof(unsigned long long)));
-    if (!h->net.d_gather_ticket) HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_gather_ticket), sizeof(unsigned int)));
+    if (!h->net.d_gather_ticket) HIPCHK(h, h->net.d_gather_ticket.alloc(1));
     HIPCHK(h, hipMemset(h->net.d_gather_ticket, 0, sizeof(unsigned int)));
     h->net.gather_seq = 0;
     std::string why;
@@ -249,7 +247,7 @@ int lii_selftest_list_exchange(lii_handle h, int32_t n_ranks, int32_t form, cons
     lii_handle h; unsigned long long seq;
     ~Restore() {
       h->net.gather_seq = seq;
-      if (h->net.d_gx) { (void)hipFree(h->net.d_gx); h->net.d_gx = nullptr; h->net.gx_block = 0; h->net.gx_ranks = 0; }
+      h->net.d_gx.reset();
     }
   } restore{h, gather_seq_at_entry};
   const int N = n_ranks, cap = h->cfg.max_scan_points;
@@ -267,8 +265,7 @@ int lii_selftest_list_exchange(lii_handle h, int32_t n_ranks, int32_t form, cons
   hipStream_t s = h->stream;
   HIPCHK(h, hipStreamSynchronize(s));
   const size_t block = size_t(kGatherHeaderBytes) + sizeof(float4) * size_t(cap);
-  std::vector<unsigned char*> bufs;  // temporaries of this call
-  auto cleanup = [&]() { for (unsigned char* b : bufs) (void)hipFree(b); };
+  DevBuf<unsigned char> base, sends;  // temporaries of this call: the gather areas of form 0 / every rank's send block, kept while the others are played
   auto upload_rank = [&](int r) -> int {  // rank r's lists and sizes into the handle's list buffers
     const int c[6] = {n_add[r], n_nodown[r], 0, 0, 0, 0};
     if (n_add[r]) HIPCHK(h, hipMemcpyAsync(h->d_list_add, add_xyzw + 4 * at_a[size_t(r)], sizeof(float4) * size_t(n_add[r]), hipMemcpyHostToDevice, s));
@@ -295,21 +292,19 @@ int lii_selftest_list_exchange(lii_handle h, int32_t n_ranks, int32_t form, cons
     return LII_OK;
   };
   if (!h->net.d_gather_ticket) {
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->net.d_gather_ticket), sizeof(unsigned int)));
+    HIPCHK(h, h->net.d_gather_ticket.alloc(1));
     HIPCHK(h, hipMemset(h->net.d_gather_ticket, 0, sizeof(unsigned int)));
   }
   const unsigned long long seq = form == 0 ? ++h->net.gather_seq : 2ull * ++h->net.gather_seq;
   if (form == 0) {
     // N gather areas (two parities x N source blocks each) and the table of them, as mailbox_open lays them out
     const size_t area = 2 * size_t(N) * block;
-    unsigned char* base = nullptr;
-    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&base), area * size_t(N) + sizeof(void*) * size_t(N)));
-    bufs.push_back(base);
-    if (hipMemset(base, 0, area * size_t(N)) != hipSuccess) { cleanup(); return fail(h, LII_ERR_HIP, "hipMemset"); }
+    HIPCHK(h, base.alloc(area * size_t(N) + sizeof(void*) * size_t(N)));
+    HIPCHK(h, hipMemset(base, 0, area * size_t(N)));
     std::vector<unsigned char*> tab(static_cast<size_t>(N));
     for (int r = 0; r < N; r++) tab[size_t(r)] = base + area * size_t(r);
     unsigned char** d_tab = reinterpret_cast<unsigned char**>(base + area * size_t(N));
-    if (hipMemcpy(d_tab, tab.data(), sizeof(void*) * size_t(N), hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(h, LII_ERR_HIP, "hipMemcpy"); }
+    HIPCHK(h, hipMemcpy(d_tab, tab.data(), sizeof(void*) * size_t(N), hipMemcpyHostToDevice));
     lii::GatherView gv;
     gv.peers = d_tab; gv.block_bytes = block; gv.cap_points = cap; gv.n_ranks = N; gv.timeout_ticks = 200000000ll;  // 2 s
     for (int r = 0; r < N && rc == LII_OK; r++) {
@@ -326,11 +321,7 @@ int lii_selftest_list_exchange(lii_handle h, int32_t n_ranks, int32_t form, cons
   } else {
     GxLayout L;
     rc = gx_prepare(h, N, &L);
-    unsigned char* sends = nullptr;  // every rank's send block, kept while the others are played
-    if (rc == LII_OK) {
-      if (hipMalloc(reinterpret_cast<void**>(&sends), block * size_t(N)) != hipSuccess) rc = fail(h, LII_ERR_HIP, "hipMalloc");
-      else bufs.push_back(sends);
-    }
+    if (rc == LII_OK && sends.alloc(block * size_t(N)) != hipSuccess) rc = fail(h, LII_ERR_HIP, "hipMalloc");
     for (int r = 0; r < N && rc == LII_OK; r++) {
       rc = upload_rank(r);
       if (rc != LII_OK) break;
@@ -350,7 +341,6 @@ int lii_selftest_list_exchange(lii_handle h, int32_t n_ranks, int32_t form, cons
       if (rc == LII_OK) rc = download_and_compare(q);
     }
   }
-  cleanup();
   if (rc != LII_OK) return rc;
   *out_n_add = ref_na; *out_n_nodown = ref_nn;
   if (ref_na) std::memcpy(out_add, ref_a.data(), sizeof(float) * ref_a.size());

@@ -19,49 +19,39 @@ int build_index(lii_handle h, int n, int extra_blocks) {
   h->n_used = 0;
   h->map_dirty = false;
   unsigned int n_blocks = 0;
-  unsigned int* ranks = reinterpret_cast<unsigned int*>(h->d_keys_a);  // free after the sort
+  unsigned int* ranks = reinterpret_cast<unsigned int*>(h->d_keys_a.get());  // free after the sort
   if (n > 0) {
     const float inv_cs = 1.0f / h->cell_size;
     launch_map_keys(h->d_map_unsorted, n, inv_cs, h->d_keys_a, h->d_idx_a, s);
-    sort_pairs_u64(h->d_sort_temp, h->sort_temp_bytes, h->d_keys_a, h->d_keys_b, h->d_idx_a, h->d_idx_b, n, s);
+    sort_pairs_u64(h->d_sort_temp, h->d_sort_temp.size(), h->d_keys_a, h->d_keys_b, h->d_idx_a, h->d_idx_b, n, s);
     launch_map_gather(h->d_map_unsorted, h->d_idx_b, n, h->d_map, s);
     unsigned int* flags = h->d_idx_a;  // free after the sort
     launch_block_flags(h->d_keys_b, n, flags, s);
-    inclusive_scan_u32(h->d_sort_temp, h->sort_temp_bytes, flags, ranks, n, s);
+    inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), flags, ranks, n, s);
     HIPCHK(h, hipMemcpyAsync(h->h_small, ranks + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     std::memcpy(&n_blocks, h->h_small, sizeof(unsigned int));
   }
   const size_t want_blocks = size_t(n_blocks) + size_t(std::max(extra_blocks, 0));
-  if (want_blocks + 1 > h->cells_cap_blocks || !h->d_cell_cap) {
-    for (void* q : {static_cast<void*>(h->d_cells), static_cast<void*>(h->d_cell_cap), static_cast<void*>(h->d_tp), static_cast<void*>(h->d_cs_a),
-                    static_cast<void*>(h->d_cs_b), static_cast<void*>(h->d_block_key)})
-      if (q) HIPCHK(h, hipFree(q));
-    h->d_cells = nullptr; h->d_cell_cap = nullptr; h->d_tp = nullptr; h->d_cs_a = nullptr; h->d_cs_b = nullptr; h->d_block_key = nullptr;
+  if (want_blocks + 1 > h->cells_cap_blocks) {
     // (+ 1: the last table of the pool is the shared all-empty one, k_ins_cells)
     const size_t want = h->map_tight ? want_blocks + 1 : std::max<size_t>(std::max<size_t>(want_blocks * 2, h->cells_cap_blocks), 4096);
-    HIPCHK(h, dmalloc(&h->d_cells, want * 512));
-    HIPCHK(h, dmalloc(&h->d_cell_cap, want * 512));
-    HIPCHK(h, dmalloc(&h->d_tp, want * 512));
-    HIPCHK(h, dmalloc(&h->d_cs_a, want * 512));
-    HIPCHK(h, dmalloc(&h->d_cs_b, want * 512));
-    HIPCHK(h, dmalloc(&h->d_block_key, want));
-    h->cells_cap_blocks = want;
-    if (want * 512 * sizeof(unsigned int) + 4096 > h->sort_temp_bytes) {  // the scans over the cell entries need their temporary storage
-      if (h->d_sort_temp) HIPCHK(h, hipFree(h->d_sort_temp));
-      h->d_sort_temp = nullptr;
-      h->sort_temp_bytes = std::max(h->sort_temp_bytes, sort_temp_bytes(int(std::min<size_t>(want * 512, 0x7FFFFFFF))));
-      HIPCHK(h, hipMalloc(&h->d_sort_temp, h->sort_temp_bytes));
-    }
+    // the six tables go before the first of the new ones comes: the peak of a growth is the new size, not the sum of both
+    h->d_cells.reset(); h->d_cell_cap.reset(); h->d_tp.reset(); h->d_cs_a.reset(); h->d_cs_b.reset(); h->d_block_key.reset();
+    h->cells_cap_blocks = 0;
+    HIPCHK(h, h->d_cells.alloc(want * 512));
+    HIPCHK(h, h->d_cell_cap.alloc(want * 512));
+    HIPCHK(h, h->d_tp.alloc(want * 512));
+    HIPCHK(h, h->d_cs_a.alloc(want * 512));
+    HIPCHK(h, h->d_cs_b.alloc(want * 512));
+    HIPCHK(h, h->d_block_key.alloc(want));
+    h->cells_cap_blocks = h->d_block_key.size();
+    if (want * 512 * sizeof(unsigned int) + 4096 > h->d_sort_temp.size())  // the scans over the cell entries need their temporary storage
+      HIPCHK(h, h->d_sort_temp.grow(std::max(h->d_sort_temp.size(), sort_temp_bytes(int(std::min<size_t>(want * 512, 0x7FFFFFFF))))));
   }
   unsigned int bcap = next_pow2(std::max(1024u, 8u * (unsigned int)want_blocks));  // load factor <= 1/8 now, <= 1/2 before the next rebuild
-  if (bcap > h->blocks_cap) {
-    if (h->d_blocks) HIPCHK(h, hipFree(h->d_blocks));
-    h->d_blocks = nullptr;
-    HIPCHK(h, dmalloc(&h->d_blocks, size_t(bcap)));
-    h->blocks_cap = bcap;
-  }
-  bcap = h->blocks_cap;
+  if (bcap > h->d_blocks.size()) HIPCHK(h, h->d_blocks.grow(size_t(bcap)));
+  bcap = (unsigned int)h->d_blocks.size();
   h->block_mask = bcap - 1;
   h->n_blocks = int(n_blocks);
   // every table entry of the pool starts out zero: blocks created later by k_ins_cells find an empty cell table
@@ -78,7 +68,7 @@ int build_index(lii_handle h, int n, int extra_blocks) {
     unsigned int* caps = h->d_cs_a;
     unsigned int* capsum = h->d_cs_b;
     launch_cell_caps(h->d_cells, ne, caps, s);
-    inclusive_scan_u32(h->d_sort_temp, h->sort_temp_bytes, caps, capsum, ne, s);
+    inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), caps, capsum, ne, s);
     launch_spread(h->d_map, h->d_cells, h->d_cell_cap, caps, capsum, ne, h->d_pts, h->d_mapctr, n, int(n_blocks), s);
   }
   HIPCHK(h, hipGetLastError());
@@ -86,7 +76,7 @@ int build_index(lii_handle h, int n, int extra_blocks) {
   if (n > 0) {
     // the dense cell window: the box of the occupied blocks, one block of margin on every side (queries at the map's edge look one
     // cell out), if it fits 64 MiB of entries
-    unsigned int* box = reinterpret_cast<unsigned int*>(h->d_cs_a);  // (free again)
+    unsigned int* box = h->d_cs_a;  // (free again)
     const unsigned int init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     std::memcpy(h->h_small + 2100, init, sizeof(init));
     HIPCHK(h, hipMemcpyAsync(box, h->h_small + 2100, sizeof(init), hipMemcpyHostToDevice, s));
@@ -103,12 +93,7 @@ int build_index(lii_handle h, int n, int extra_blocks) {
       entries_w *= size_t(h->win_dim[a]);
     }
     if (bxx[0] <= bxx[3] && entries_w * sizeof(uint2) <= (64u << 20)) {
-      if (entries_w > h->win_cap) {
-        if (h->d_win) HIPCHK(h, hipFree(h->d_win));
-        h->d_win = nullptr;
-        HIPCHK(h, dmalloc(&h->d_win, entries_w));
-        h->win_cap = entries_w;
-      }
+      if (entries_w > h->d_win.size()) HIPCHK(h, h->d_win.grow(entries_w));
       HIPCHK(h, hipMemsetAsync(h->d_win, 0, sizeof(uint2) * entries_w, s));
       launch_win_fill(h->d_blocks, bcap, h->d_cells, h->d_win, h->win_org, h->win_dim, s);
       HIPCHK(h, hipGetLastError());
@@ -268,7 +253,7 @@ int map_gather(lii_handle h, int* n_out) {
   *n_out = 0;
   if (ne <= 0) return LII_OK;
   launch_cell_counts(h->d_cells, ne, h->d_cs_a, s);
-  inclusive_scan_u32(h->d_sort_temp, h->sort_temp_bytes, h->d_cs_a, h->d_cs_b, ne, s);
+  inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), h->d_cs_a, h->d_cs_b, ne, s);
   launch_gather_live(h->d_pts, h->d_cells, h->d_cs_b, ne, h->d_map_unsorted, h->cfg.max_map_points, s);
   HIPCHK(h, hipMemcpyAsync(h->h_small + 3000, h->d_cs_b + (ne - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
@@ -320,7 +305,7 @@ int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, con
   const unsigned int work_need = 9u * (unsigned int)n_list + (unsigned int)n_ins + 64u;
   if (work_need > h->work_cap) return fail(h, LII_ERR_CAPACITY, "Add_Points batch larger than the work list of the in-place update");
   if (h->test_force_rebuild || (long long)h->pts_cap_eff - h->n_used < tail_need || size_t(h->n_blocks) + spare_blocks + 1 > h->cells_cap_blocks ||
-      2ull * (size_t(h->n_blocks) + spare_blocks) > size_t(h->blocks_cap)) {
+      2ull * (size_t(h->n_blocks) + spare_blocks) > h->d_blocks.size()) {
     rc = map_rebuild(h, h->map_tight ? 0 : std::max(4096, h->n_blocks / 2));
     if (rc != LII_OK) return rc;
     if ((long long)h->pts_cap_eff - h->n_used < tail_need) return fail(h, LII_ERR_CAPACITY, "local map: no room left behind the cells for an in-place update");
@@ -328,7 +313,7 @@ int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, con
   }
   // `beside`: the update runs on the map stream from here (see map_join), behind what the handle's stream holds now
   if (beside) {
-    if (!h->map_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->map_stream, hipStreamNonBlocking));  // (a handle that left a job)
+    if (!h->map_stream) HIPCHK(h, h->map_stream.create(hipStreamNonBlocking));  // (a handle that left a job)
     HIPCHK(h, hipEventRecord(h->ev_lists, h->stream));
     s = h->map_stream;
     HIPCHK(h, hipStreamWaitEvent(s, h->ev_lists, 0));
@@ -367,7 +352,7 @@ int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, con
     flags_a = h->d_u32_a;
   } else if (downsample && n_list > 0) {
     launch_add_keys(list, n_list, n_list_dev, h->ds, h->d_keys_a, h->d_idx_a, h->d_mapctr + kMapCtrEvents, s);
-    sort_pairs_u64(h->d_sort_temp, h->sort_temp_bytes, h->d_keys_a, h->d_keys_b, h->d_idx_a, h->d_idx_b, n_list, s);
+    sort_pairs_u64(h->d_sort_temp, h->d_sort_temp.size(), h->d_keys_a, h->d_keys_b, h->d_idx_a, h->d_idx_b, n_list, s);
     launch_add_fold(list, h->d_keys_b, h->d_idx_b, n_list, h->ds, g, h->d_tomb, h->d_ins, h->d_u32_a,
                     reinterpret_cast<unsigned int*>(h->d_mapctr + kMapCtrEvents), h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
     list_a = h->d_ins;
@@ -412,7 +397,7 @@ int map_update_early(lii_handle h) {
   if (++h->decide_epoch == 0u) h->decide_epoch = 1u;
   // round 6: the hash insert of the fold rides in the decision launch when the fold that follows will take the hash-grouped form
   const bool fill = h->map_fuse && ba > 0 && !h->fold_sorted && ba <= h->cfg.max_scan_points && !h->ah_filled;
-  launch_map_decide_compact(rb, unused, double(h->cfg.map_downsample_size), 1, reinterpret_cast<unsigned long long*>(h->d_u32_b), h->decide_epoch, h->d_world,
+  launch_map_decide_compact(rb, unused, double(h->cfg.map_downsample_size), 1, reinterpret_cast<unsigned long long*>(h->d_u32_b.get()), h->decide_epoch, h->d_world,
                             h->d_list_add, h->d_list_nodown, h->d_counts, ba, bn, h->stream, h->d_ctrl, h->update_seq, h->test_emit_late ? 1 : 0,
                             fill ? h->d_ah_key : nullptr, h->d_ah_best, h->d_ah_slot, h->ds, h->d_u32_a, h->d_mapctr + kMapCtrEvents);
   if (fill) h->ah_filled = true;
@@ -501,7 +486,7 @@ int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int3
   const int n_old = h->n_map;
   if (n_boxes == 0 || n_old == 0) return LII_OK;
   hipStream_t s = h->stream;
-  float* d_boxes = reinterpret_cast<float*>(h->d_keys_b);  // scratch of the index build (max_map_points * 8 bytes), free between calls
+  float* d_boxes = reinterpret_cast<float*>(h->d_keys_b.get());  // scratch of the index build (max_map_points * 8 bytes), free between calls
   if (size_t(n_boxes) * 24 > size_t(h->cfg.max_map_points) * 8)
     return fail(h, LII_ERR_INVALID, "lii_map_delete_boxes: more boxes than the handle's scratch holds (max_map_points / 3)");
   std::memcpy(h->h_small + 4096, boxes, sizeof(float) * 6 * size_t(n_boxes));
@@ -509,10 +494,9 @@ int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int3
   // in place: every cell walks its live points, the cells that lose points squeeze them out (k_cell_apply)
   const int ne = h->n_blocks * 512;
   if ((unsigned int)ne > h->work_cap) {  // more cells than the work list holds: rebuild-free fallback is not worth it - grow the list
-    if (h->d_work) HIPCHK(h, hipFree(h->d_work));
-    h->d_work = nullptr;
-    h->work_cap = (unsigned int)ne + 4096u;
-    HIPCHK(h, dmalloc(&h->d_work, size_t(h->work_cap)));
+    h->work_cap = 0;
+    HIPCHK(h, h->d_work.grow(size_t(ne) + 4096));
+    h->work_cap = (unsigned int)h->d_work.size();
   }
   h->map_dirty = true;
   launch_box_tomb_cells(h->d_pts, h->d_cells, ne, d_boxes, n_boxes, h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
@@ -615,11 +599,11 @@ int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, in
     h->bound_add = ba; h->bound_nodown = bn;  // (LII_TEST=pred_small: every update outgrows its bounds)
     if (++h->decide_epoch == 0u) h->decide_epoch = 1u;
     launch_map_decide_compact(rb, pose_of(*state), double(h->cfg.map_downsample_size), h->have_search ? 1 : 0,
-                              reinterpret_cast<unsigned long long*>(h->d_u32_b), h->decide_epoch, h->d_world, h->d_list_add, h->d_list_nodown, h->d_counts, ba, bn, s, nullptr, 0, h->test_emit_late ? 1 : 0);
+                              reinterpret_cast<unsigned long long*>(h->d_u32_b.get()), h->decide_epoch, h->d_world, h->d_list_add, h->d_list_nodown, h->d_counts, ba, bn, s, nullptr, 0, h->test_emit_late ? 1 : 0);
     return map_apply(h, h->d_list_add, ba, true, h->d_list_nodown, bn, true, h->d_counts + 3, h->d_counts + 4, false);
   }
   if (++h->decide_epoch == 0u) h->decide_epoch = 1u;
-  launch_map_decide_compact(rb, pose_of(*state), double(h->cfg.map_downsample_size), h->have_search ? 1 : 0, reinterpret_cast<unsigned long long*>(h->d_u32_b),
+  launch_map_decide_compact(rb, pose_of(*state), double(h->cfg.map_downsample_size), h->have_search ? 1 : 0, reinterpret_cast<unsigned long long*>(h->d_u32_b.get()),
                             h->decide_epoch, h->d_world, h->d_list_add, h->d_list_nodown, h->d_counts, nb, nb, s, nullptr, 0, h->test_emit_late ? 1 : 0);
   if (exchange) {
     // This rank has decided for ITS points (its block of the cloud, or its voxels): the lists of all ranks, in rank order, are the

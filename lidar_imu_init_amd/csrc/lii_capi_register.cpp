@@ -111,7 +111,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   // stream has been destroyed again: the runtime keeps the hardware queue - makes several processes on one device oversubscribe
   // the hardware queues, and a kernel that waits for a peer's kernel (the mailbox) then waits for a time slice: the one-device
   // rehearsal of a 2-rank job fell from 4 000 to 1 350 scans/s.
-  if (!h->map_stream && h->net.n_ranks <= 1) HIPCHK(h, hipStreamCreateWithFlags(&h->map_stream, hipStreamNonBlocking));
+  if (!h->map_stream && h->net.n_ranks <= 1) HIPCHK(h, h->map_stream.create(hipStreamNonBlocking));
   if (!h->ctrl_preloaded) {
     if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(s));  // a lii_scan_register that failed half way left the buffer in use
     fill_ctrl(h, state, state_prop, opts);
@@ -701,13 +701,13 @@ int lii_neighbors_download(lii_handle h, float* pts, int32_t* counts, uint8_t* s
   if (counts) {
     HIPCHK(h, hipMemcpyAsync(h->h_stage, h->d_nbr_count, sizeof(int) * size_t(n), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const int* src = reinterpret_cast<const int*>(h->h_stage);
+    const int* src = reinterpret_cast<const int*>(h->h_stage.get());
     for (int i = 0; i < n; i++) counts[i] = src[perm ? perm[i] : i] & kCountMask;  // (without the completion flags)
   }
   if (selected) {
     HIPCHK(h, hipMemcpyAsync(h->h_stage, h->d_selected, size_t(n), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(h->h_stage);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(h->h_stage.get());
     for (int i = 0; i < n; i++) selected[i] = src[perm ? perm[i] : i];
   }
   return LII_OK;

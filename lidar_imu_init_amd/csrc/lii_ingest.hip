@@ -26,6 +26,7 @@
 #include "../../include/liinit_hip.h"
 #include "lii_device.h"
 #include "lii_launch.h"
+#include "lii_owned.h"
 
 namespace lii {
 
@@ -47,18 +48,15 @@ struct IngestTable {  // written by k_cut_plan into mapped host memory
 };
 
 struct IngestCtx {
-  int cap = 0;  // raw points the buffers hold
-  size_t raw_bytes = 0;
-  uint8_t* d_raw = nullptr;
-  float4* d_pts = nullptr;       // decoded (x, y, z, curvature) per raw point
-  double* d_yaw = nullptr;       // azimuth [deg] per raw point (time synthesis)
-  uint8_t* d_ring = nullptr;
-  unsigned int *d_flag = nullptr, *d_rank = nullptr, *d_aux = nullptr, *d_aux_rank = nullptr;
-  unsigned int *d_key_a = nullptr, *d_key_b = nullptr, *d_idx_a = nullptr, *d_idx_b = nullptr;
-  float4* d_frames = nullptr;    // the emitted frames, contiguous
-  void* d_temp = nullptr;
-  size_t temp_bytes = 0;
-  IngestTable* h_table = nullptr;  // pinned + mapped
+  DevBuf<uint8_t> d_raw;         // the message as it arrived (size(): its bytes + 64)
+  DevBuf<float4> d_pts;          // decoded (x, y, z, curvature) per raw point; size(): raw points the per-point buffers hold
+  DevBuf<double> d_yaw;          // azimuth [deg] per raw point (time synthesis)
+  DevBuf<uint8_t> d_ring;
+  DevBuf<unsigned int> d_flag, d_rank, d_aux, d_aux_rank;
+  DevBuf<unsigned int> d_key_a, d_key_b, d_idx_a, d_idx_b;
+  DevBuf<float4> d_frames;       // the emitted frames, contiguous
+  DevBuf<unsigned char> d_temp;  // temporary storage of the scan and the sort (size(): bytes)
+  PinnedBuf<IngestTable> h_table;  // pinned + mapped
   IngestTable table;               // host copy of the last message
   bool have = false;
   bool cut_msg = false;            // the message in this context went through the time sort + cut (cut_frame_num != 0)
@@ -310,31 +308,20 @@ __global__ void k_whole_apply(const float4* __restrict__ pts, const unsigned int
   }
 }
 
-template <class T>
-hipError_t dm(T** p, size_t n) { return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (n ? n : 1)); }
-
-void ingest_release(IngestCtx* c) {
-  void* ptrs[] = {c->d_raw, c->d_pts, c->d_yaw, c->d_ring, c->d_flag, c->d_rank, c->d_aux, c->d_aux_rank, c->d_key_a, c->d_key_b,
-                  c->d_idx_a, c->d_idx_b, c->d_frames, c->d_temp};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c->h_table) (void)hipHostFree(c->h_table);
-}
-
 // The handle's ingest state: a ring of three message contexts.  `front` holds the message whose frames lii_frame_select serves (the
 // one-call forms lii_ingest_pcl2 / _livox work in it, on the handle's stream).  The overlapped forms (lii_ingest_*_begin / lii_ingest_end,
 // ABI 9) put up to two more messages under way in the other contexts: raw bytes on a copy stream, decode ... cut on a
 // kernel stream behind them, while the handle's stream registers the sub-frames of `front`.
 struct IngestRing {
   static constexpr int kSlots = 3;
-  IngestCtx slot[kSlots];
+  IngestCtx slot[kSlots];  // (the members go in reverse order: the streams are waited for and destroyed, then the events, then the contexts' buffers)
   int front = 0;
   int pending[kSlots] = {0, 0, 0};  // FIFO of contexts under way, oldest first
   int n_pending = 0;
-  hipStream_t s_copy = nullptr, s_kern = nullptr;
-  hipEvent_t ev_copied[kSlots] = {nullptr, nullptr, nullptr}, ev_done[kSlots] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_read = nullptr;  // recorded on the handle's stream when a message leaves `front`: whatever that stream still has to do with its frames lies in front of it
+  Event ev_copied[kSlots], ev_done[kSlots];
+  Event ev_read;  // recorded on the handle's stream when a message leaves `front`: whatever that stream still has to do with its frames lies in front of it
   bool guard[kSlots] = {false, false, false};  // ... and the contexts whose next message waits for it
+  Stream s_kern, s_copy;
   // The launch plan of the time sort (its eleven launches are two thirds of a message's kernel time): the last cut message's kept points
   // arrived in ascending time order -> the next one is enqueued WITHOUT the sort, the device checks the order, a message that fails the
   // check is done again with the sort before its frames are handed out.  LII_INGEST_SORT=always: never predicted.
@@ -349,55 +336,31 @@ void ingest_free(IngestRing* r) {
   if (r->diag && (r->n_unsorted_skipped || r->n_redone))
     fprintf(stderr, "[libliinit_hip] ingest: messages cut without their time sort (they arrived in time order): %lld, done again with it: %lld\n",
             r->n_unsorted_skipped, r->n_redone);
-  if (r->s_copy) { (void)hipStreamSynchronize(r->s_copy); (void)hipStreamDestroy(r->s_copy); }
-  if (r->s_kern) { (void)hipStreamSynchronize(r->s_kern); (void)hipStreamDestroy(r->s_kern); }
-  for (int k = 0; k < IngestRing::kSlots; k++) {
-    if (r->ev_copied[k]) (void)hipEventDestroy(r->ev_copied[k]);
-    if (r->ev_done[k]) (void)hipEventDestroy(r->ev_done[k]);
-    ingest_release(&r->slot[k]);
-  }
-  if (r->ev_read) (void)hipEventDestroy(r->ev_read);
   delete r;
 }
 
-#define ICHK(h, expr)                                                                                         \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 int ingest_reserve(lii_handle h, IngestCtx* c, int n, size_t raw_bytes) {
-  if (!c->h_table) ICHK(h, hipHostMalloc(reinterpret_cast<void**>(&c->h_table), sizeof(IngestTable), hipHostMallocMapped));
-  if (raw_bytes > c->raw_bytes) {
-    if (c->d_raw) (void)hipFree(c->d_raw);
-    c->d_raw = nullptr;
-    ICHK(h, dm(&c->d_raw, raw_bytes + 64));
-    c->raw_bytes = raw_bytes;
-  }
-  if (n > c->cap) {
-    void** ptrs[] = {(void**)&c->d_pts, (void**)&c->d_yaw, (void**)&c->d_ring, (void**)&c->d_flag, (void**)&c->d_rank, (void**)&c->d_aux,
-                     (void**)&c->d_aux_rank, (void**)&c->d_key_a, (void**)&c->d_key_b, (void**)&c->d_idx_a, (void**)&c->d_idx_b,
-                     (void**)&c->d_frames, (void**)&c->d_temp};
-    for (void** p : ptrs) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
+  if (!c->h_table) HIPCHK(h, c->h_table.alloc(1, hipHostMallocMapped));
+  if (raw_bytes > 0 && raw_bytes + 64 > c->d_raw.size()) HIPCHK(h, c->d_raw.grow(raw_bytes + 64));
+  if (n > int(c->d_pts.size())) {
+    // the thirteen arrays go before the first of the new ones comes (the peak of a growth is the new size); d_pts, the one whose
+    // size() stands for all of them, goes first and comes last
+    c->d_pts.reset(); c->d_yaw.reset(); c->d_ring.reset(); c->d_flag.reset(); c->d_rank.reset(); c->d_aux.reset(); c->d_aux_rank.reset();
+    c->d_key_a.reset(); c->d_key_b.reset(); c->d_idx_a.reset(); c->d_idx_b.reset(); c->d_frames.reset(); c->d_temp.reset();
     const int cap = n + n / 4 + 1024;
-    ICHK(h, dm(&c->d_pts, cap));
-    ICHK(h, dm(&c->d_yaw, cap));
-    ICHK(h, dm(&c->d_ring, cap));
-    ICHK(h, dm(&c->d_flag, cap));
-    ICHK(h, dm(&c->d_rank, cap));
-    ICHK(h, dm(&c->d_aux, cap));
-    ICHK(h, dm(&c->d_aux_rank, cap));
-    ICHK(h, dm(&c->d_key_a, cap));
-    ICHK(h, dm(&c->d_key_b, cap));
-    ICHK(h, dm(&c->d_idx_a, cap));
-    ICHK(h, dm(&c->d_idx_b, cap));
-    ICHK(h, dm(&c->d_frames, cap));
-    c->temp_bytes = sort_temp_bytes(cap);
-    ICHK(h, hipMalloc(&c->d_temp, c->temp_bytes));
-    c->cap = cap;
+    HIPCHK(h, c->d_yaw.alloc(cap));
+    HIPCHK(h, c->d_ring.alloc(cap));
+    HIPCHK(h, c->d_flag.alloc(cap));
+    HIPCHK(h, c->d_rank.alloc(cap));
+    HIPCHK(h, c->d_aux.alloc(cap));
+    HIPCHK(h, c->d_aux_rank.alloc(cap));
+    HIPCHK(h, c->d_key_a.alloc(cap));
+    HIPCHK(h, c->d_key_b.alloc(cap));
+    HIPCHK(h, c->d_idx_a.alloc(cap));
+    HIPCHK(h, c->d_idx_b.alloc(cap));
+    HIPCHK(h, c->d_frames.alloc(cap));
+    HIPCHK(h, c->d_temp.alloc(sort_temp_bytes(cap)));
+    HIPCHK(h, c->d_pts.alloc(cap));
   }
   return LII_OK;
 }
@@ -417,22 +380,22 @@ IngestRing* ring_of(lii_handle h) {
 // at the default priority, 2 541 serial (profiles/r06_ingest_overlap.md): queues of unequal priority are time-sliced on this device.
 int ring_streams(lii_handle h, IngestRing* r) {
   if (r->s_kern) return LII_OK;
-  ICHK(h, hipStreamCreateWithFlags(&r->s_kern, hipStreamNonBlocking));
-  ICHK(h, hipStreamCreateWithFlags(&r->s_copy, hipStreamNonBlocking));
+  HIPCHK(h, r->s_kern.create(hipStreamNonBlocking));
+  HIPCHK(h, r->s_copy.create(hipStreamNonBlocking));
   for (int k = 0; k < IngestRing::kSlots; k++) {
-    ICHK(h, hipEventCreateWithFlags(&r->ev_copied[k], hipEventDisableTiming));
-    ICHK(h, hipEventCreateWithFlags(&r->ev_done[k], hipEventDisableTiming));
+    HIPCHK(h, r->ev_copied[k].create(hipEventDisableTiming));
+    HIPCHK(h, r->ev_done[k].create(hipEventDisableTiming));
   }
-  ICHK(h, hipEventCreateWithFlags(&r->ev_read, hipEventDisableTiming));
+  HIPCHK(h, r->ev_read.create(hipEventDisableTiming));
   return LII_OK;
 }
 
 // shared tail, enqueued on `s`: scan of the keep flags, compaction, stable sort by time, plan, apply (the frame table lands in mapped host memory)
 int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int uncut_below, hipStream_t s) {
   const int nb = (n + 255) / 256;
-  inclusive_scan_u32(c->d_temp, c->temp_bytes, c->d_flag, c->d_rank, n, s);
+  inclusive_scan_u32(c->d_temp, c->d_temp.size(), c->d_flag, c->d_rank, n, s);
   hipLaunchKernelGGL(k_ingest_compact, dim3(nb), dim3(256), 0, s, c->d_pts, c->d_flag, c->d_rank, n, c->d_key_a, c->d_idx_a);
-  IngestTable* d_table = reinterpret_cast<IngestTable*>(c->d_aux);  // d_aux is free again after the Livox scan
+  IngestTable* d_table = reinterpret_cast<IngestTable*>(c->d_aux.get());  // d_aux is free again after the Livox scan
   c->sort_skipped = false;
   c->cut_msg = o->cut_frame_num != 0;
   if (o->cut_frame_num == 0) {  // Preprocess::process: no sort, no cut
@@ -440,7 +403,7 @@ int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int
   } else {
     IngestRing* r = ring_of(h);
     c->sort_skipped = r->predict_sorted && !r->never_predict;
-    if (!c->sort_skipped) sort_pairs_u32(c->d_temp, c->temp_bytes, c->d_key_a, c->d_key_b, c->d_idx_a, c->d_idx_b, n, s);
+    if (!c->sort_skipped) sort_pairs_u32(c->d_temp, c->d_temp.size(), c->d_key_a, c->d_key_b, c->d_idx_a, c->d_idx_b, n, s);
     const unsigned int* order = c->sort_skipped ? c->d_idx_a : c->d_idx_b;  // (a stable sort of keys in ascending order is the identity)
     int required = o->cut_frame_num;
     if (o->scan_count < uncut_below) required = 1;
@@ -448,18 +411,18 @@ int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int
     hipLaunchKernelGGL(k_cut_plan, dim3(1), dim3(64), 0, s, c->d_pts, order, c->d_rank, n, c->stamp_ms_tail, required, d_table, c->h_table);
     hipLaunchKernelGGL(k_cut_apply, dim3(nb), dim3(256), 0, s, c->d_pts, order, d_table, n, c->d_frames, c->d_key_a, c->h_table);
   }
-  ICHK(h, hipGetLastError());
+  HIPCHK(h, hipGetLastError());
   return LII_OK;
 }
 // A message that was enqueued without its time sort and turned out not to be in time order: sort, plan and apply again (on `s`, waited for).
 int ingest_redo_sorted(lii_handle h, IngestCtx* c, hipStream_t s) {
   const int n = c->n_tail, nb = (n + 255) / 256;
-  IngestTable* d_table = reinterpret_cast<IngestTable*>(c->d_aux);
-  sort_pairs_u32(c->d_temp, c->temp_bytes, c->d_key_a, c->d_key_b, c->d_idx_a, c->d_idx_b, n, s);
+  IngestTable* d_table = reinterpret_cast<IngestTable*>(c->d_aux.get());
+  sort_pairs_u32(c->d_temp, c->d_temp.size(), c->d_key_a, c->d_key_b, c->d_idx_a, c->d_idx_b, n, s);
   hipLaunchKernelGGL(k_cut_plan, dim3(1), dim3(64), 0, s, c->d_pts, c->d_idx_b, c->d_rank, n, c->stamp_ms_tail, c->required_tail, d_table, c->h_table);
   hipLaunchKernelGGL(k_cut_apply, dim3(nb), dim3(256), 0, s, c->d_pts, c->d_idx_b, d_table, n, c->d_frames, c->d_key_a, c->h_table);
-  ICHK(h, hipGetLastError());
-  ICHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(s));
   c->sort_skipped = false;
   return LII_OK;
 }
@@ -525,10 +488,10 @@ int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points,
   const size_t bytes = (size_t)n_points * f->point_step;
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
-  ICHK(h, hipMemcpyAsync(c->d_raw, data, bytes, hipMemcpyHostToDevice, s_copy));
+  HIPCHK(h, hipMemcpyAsync(c->d_raw, data, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
-    ICHK(h, hipEventRecord(ev_copied, s_copy));
-    ICHK(h, hipStreamWaitEvent(s, ev_copied, 0));
+    HIPCHK(h, hipEventRecord(ev_copied, s_copy));
+    HIPCHK(h, hipStreamWaitEvent(s, ev_copied, 0));
   }
   Pc2Arg a;
   a.f = *f;
@@ -552,10 +515,10 @@ int livox_enqueue(lii_handle h, IngestCtx* c, const void* points, int32_t n_poin
   const size_t bytes = (size_t)n_points * f->point_step;
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
-  ICHK(h, hipMemcpyAsync(c->d_raw, points, bytes, hipMemcpyHostToDevice, s_copy));
+  HIPCHK(h, hipMemcpyAsync(c->d_raw, points, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
-    ICHK(h, hipEventRecord(ev_copied, s_copy));
-    ICHK(h, hipStreamWaitEvent(s, ev_copied, 0));
+    HIPCHK(h, hipEventRecord(ev_copied, s_copy));
+    HIPCHK(h, hipStreamWaitEvent(s, ev_copied, 0));
   }
   LivoxArg a;
   a.f = *f;
@@ -564,7 +527,7 @@ int livox_enqueue(lii_handle h, IngestCtx* c, const void* points, int32_t n_poin
   a.blind2 = o->blind * o->blind;
   const int nb = (n_points + 255) / 256;
   hipLaunchKernelGGL(k_livox_valid, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux);
-  inclusive_scan_u32(c->d_temp, c->temp_bytes, c->d_aux, c->d_aux_rank, n_points, s);
+  inclusive_scan_u32(c->d_temp, c->d_temp.size(), c->d_aux, c->d_aux_rank, n_points, s);
   hipLaunchKernelGGL(k_livox_decode, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_aux_rank, c->d_pts, c->d_flag);
   return ingest_tail(h, c, n_points, o, 5, s);
 }
@@ -583,7 +546,7 @@ int ring_take(lii_handle h, IngestRing* r, int* out) {
     if (!used) k = q;
   }
   if (r->guard[k]) {  // (the event's latest record lies behind every earlier one on the same stream)
-    ICHK(h, hipStreamWaitEvent(r->s_copy, r->ev_read, 0));
+    HIPCHK(h, hipStreamWaitEvent(r->s_copy, r->ev_read, 0));
     r->guard[k] = false;
   }
   *out = k;
@@ -618,7 +581,7 @@ int lii_ingest_pcl2(lii_handle h, const void* data, int32_t n_points, const lii_
   hipStream_t s = lii_internal_stream(h);
   rc = pcl2_enqueue(h, c, data, n_points, f, o, s, s, nullptr);
   if (rc != LII_OK) return rc;
-  ICHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipStreamSynchronize(s));
   return ingest_collect(h, c, frames, max_frames, n_frames, s);
 }
 
@@ -638,7 +601,7 @@ int lii_ingest_livox(lii_handle h, const void* points, int32_t n_points, const l
   hipStream_t s = lii_internal_stream(h);
   rc = livox_enqueue(h, c, points, n_points, f, o, s, s, nullptr);
   if (rc != LII_OK) return rc;
-  ICHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipStreamSynchronize(s));
   return ingest_collect(h, c, frames, max_frames, n_frames, s);
 }
 
@@ -657,7 +620,7 @@ int lii_ingest_pcl2_begin(lii_handle h, const void* data, int32_t n_points, cons
   if (n_points > 0) {
     rc = pcl2_enqueue(h, c, data, n_points, f, o, r->s_copy, r->s_kern, r->ev_copied[k]);
     if (rc != LII_OK) return rc;
-    ICHK(h, hipEventRecord(r->ev_done[k], r->s_kern));
+    HIPCHK(h, hipEventRecord(r->ev_done[k], r->s_kern));
   }
   ring_push(r, k);
   return LII_OK;
@@ -675,7 +638,7 @@ int lii_ingest_livox_begin(lii_handle h, const void* points, int32_t n_points, c
   if (n_points > 0) {
     rc = livox_enqueue(h, c, points, n_points, f, o, r->s_copy, r->s_kern, r->ev_copied[k]);
     if (rc != LII_OK) return rc;
-    ICHK(h, hipEventRecord(r->ev_done[k], r->s_kern));
+    HIPCHK(h, hipEventRecord(r->ev_done[k], r->s_kern));
   }
   ring_push(r, k);
   return LII_OK;
@@ -695,7 +658,7 @@ int lii_ingest_end(lii_handle h, lii_frame_info* frames, int32_t max_frames, int
   }
   // ... and whatever else that stream has been given to do with the outgoing frames (an asynchronous reader that copied a selected frame
   // on demand) is in front of this event, which the next message to take the context waits for - long complete in the per-scan loop
-  ICHK(h, hipEventRecord(r->ev_read, lii_internal_stream(h)));  // (a message is under way: the ring's streams and events exist)
+  HIPCHK(h, hipEventRecord(r->ev_read, lii_internal_stream(h)));  // (a message is under way: the ring's streams and events exist)
   r->guard[r->front] = true;
   const int k = r->pending[0];
   IngestCtx* c = &r->slot[k];
@@ -705,7 +668,7 @@ int lii_ingest_end(lii_handle h, lii_frame_info* frames, int32_t max_frames, int
     hipError_t e = hipEventQuery(r->ev_done[k]);
     for (int spin = 0; e == hipErrorNotReady && spin < 2000; spin++) e = hipEventQuery(r->ev_done[k]);
     if (e == hipErrorNotReady) { (void)hipGetLastError(); e = hipEventSynchronize(r->ev_done[k]); }
-    ICHK(h, e);
+    HIPCHK(h, e);
   }
   for (int p = 1; p < r->n_pending; p++) r->pending[p - 1] = r->pending[p];
   r->n_pending--;

@@ -10,11 +10,17 @@
 struct lii_context;
 // internal hooks of the handle for the translation units that live beside lii_capi.cpp (not exported in the C-ABI header)
 int lii_internal_fail(lii_context* h, int code, const std::string& msg);
+// The library's one check of a runtime call: a failure is recorded as "<call>: <the runtime's message>" and ends the caller with LII_ERR_HIP.
+#define HIPCHK(h, call)                                                                                            \
+  do {                                                                                                             \
+    hipError_t e_ = (call);                                                                                        \
+    if (e_ != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+  } while (0)
 int lii_internal_scan_defer(lii_context* h, const void* dev_float4, int32_t n);  // (lii_capi.cpp) lii_frame_select's hand-over
-int lii_internal_scan_materialize(lii_context* h);
+int lii_internal_scan_materialize(lii_context* h);  // (lii_capi.cpp) a selected frame nobody has read yet -> the handle's own scan buffer
 int lii_internal_in_wait_hook(lii_context* h);       // (lii_capi.cpp) 1: inside lii_scan_job::while_waiting of a registration under way
 int lii_internal_scan_is_deferred(lii_context* h);  // (lii_capi.cpp) 1: a selected frame that nobody has read yet
-void lii_internal_prearm_cancel(lii_context* h);  // (lii_capi.cpp) see lii_impl::prearm_cancel  // (lii_capi.cpp) a selected frame nobody has read yet -> the handle's own scan buffer
+void lii_internal_prearm_cancel(lii_context* h);  // (lii_capi.cpp) see lii_impl::prearm_cancel
 hipStream_t lii_internal_stream(lii_context* h);
 void** lii_internal_ingest_slot(lii_context* h);
 void lii_internal_ingest_switches(lii_context* h, bool* diag, bool* sort_always);  // (lii_capi.cpp) LII_DIAG, LII_INGEST_SORT=always

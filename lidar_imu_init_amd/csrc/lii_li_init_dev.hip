@@ -19,6 +19,7 @@
 #include "../../include/liinit_hip.h"
 #include "lii_device.h"
 #include "lii_launch.h"
+#include "lii_owned.h"
 
 namespace lii {
 namespace {
@@ -135,15 +136,14 @@ int lii_zero_phase_filter(lii_handle h, const lii_calib_state* in, int32_t n_seq
   hipStream_t s = lii_internal_stream(h);
   const size_t rec = size_t(n_seq) * size_t(n) * 22;
   const size_t scr = size_t(n_seq) * 12 * (2 * size_t(n + 2 * 60) + size_t(n));
-  double *d = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * (rec + scr)) != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, "lii_zero_phase_filter: hipMalloc");
+  DevBuf<double> d;
+  if (d.alloc(rec + scr) != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, "lii_zero_phase_filter: hipMalloc");
   hipError_t e = hipMemcpyAsync(d, in, sizeof(double) * rec, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_zero_phase, dim3((n_seq * 12 + 63) / 64), dim3(64), 0, s, d, n_seq, n, d + rec);
     e = hipMemcpyAsync(out, d, sizeof(double) * rec, hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d);
   if (e != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, std::string("lii_zero_phase_filter: ") + hipGetErrorString(e));
   return LII_OK;
 }
@@ -153,9 +153,9 @@ int lii_xcorr_lag(lii_handle h, const lii_calib_state* imu, const lii_calib_stat
   if (!h || !imu || !lidar || !lag_imu_wrt_lidar || n < 1) return lii_internal_fail(h, LII_ERR_INVALID, "lii_xcorr_lag: bad arguments");
   hipStream_t s = lii_internal_stream(h);
   const size_t rec = size_t(n) * 22;
-  double* d = nullptr;
+  DevBuf<double> d;
   const size_t total = 2 * rec + 2 * size_t(n) + 2 + (2 * size_t(n) - 1) + 2;
-  if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * total) != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, "lii_xcorr_lag: hipMalloc");
+  if (d.alloc(total) != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, "lii_xcorr_lag: hipMalloc");
   double *d_imu = d, *d_lid = d + rec, *d_a = d + 2 * rec, *d_b = d_a + n, *d_means = d_b + n, *d_corr = d_means + 2;
   int* d_lag = reinterpret_cast<int*>(d_corr + (2 * size_t(n) - 1));
   hipError_t e = hipMemcpyAsync(d_imu, imu, sizeof(double) * rec, hipMemcpyHostToDevice, s);
@@ -168,7 +168,6 @@ int lii_xcorr_lag(lii_handle h, const lii_calib_state* imu, const lii_calib_stat
     e = hipMemcpyAsync(&lag, d_lag, sizeof(int), hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d);
   if (e != hipSuccess) return lii_internal_fail(h, LII_ERR_HIP, std::string("lii_xcorr_lag: ") + hipGetErrorString(e));
   *lag_imu_wrt_lidar = lag;
   return LII_OK;
