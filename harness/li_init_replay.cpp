@@ -176,6 +176,7 @@ struct lii_replay {
   double imu_mean_acc_norm = kG;
   std::vector<lii_pose6d> imu_pose;
   std::vector<double> log;  // LII_REPLAY_ROW doubles per processed scan
+  bool device_imu = false;  // lii_replay_set_device_imu: ImuProcess::Process' propagation through lii_scan_register_imu / lii_cv_propagate
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -222,6 +223,14 @@ void lii_replay_destroy(lii_replay* r) {
 }
 const char* lii_replay_last_error(lii_replay* r) { return r ? r->err.c_str() : "null handle"; }
 lii_handle lii_replay_handle(lii_replay* r) { return r ? r->h : nullptr; }
+// 1: the forward propagation of ImuProcess::Process runs on the device - the LIO branch goes through lii_scan_register_imu (the IMU
+// samples instead of a pose table; the carry lives in the handle), the LO branch's through lii_cv_propagate.  0 (default): the host
+// routines below.
+int lii_replay_set_device_imu(lii_replay* r, int32_t on) {
+  if (!r) return LII_ERR_INVALID;
+  r->device_imu = on != 0;
+  return LII_OK;
+}
 
 // imu_cbk, src/laserMapping.cpp:395-433
 int lii_replay_imu(lii_replay* r, double stamp, const double gyr[3], const double acc[3]) {
@@ -519,7 +528,7 @@ static int process(lii_replay* r) {
   job.opts = r->opts;
   job.opts.imu_en = r->imu_en ? 1 : 0;
   job.scan_sorted = r->prm.cut_frame ? 1 : 0;  // lii_ingest_* hands cut frames over in ascending time order, as process_cut_frame_* does; a whole message keeps the driver's order
-  bool select = true;
+  bool select = true, device_lio = false;
   // ---- p_imu->Process(Measures, state, feats_undistort), src/IMU_Processing.hpp:419-462
   if (r->imu_en) {
     if (r->meas_imu.empty()) return LII_OK;
@@ -530,8 +539,27 @@ static int process(lii_replay* r) {
       r->last_imu = r->meas_imu.back();
       r->imu_need_init = false;
       for (int a = 0; a < 3; a++) { r->cov_acc[a] = 0.1; r->cov_gyr[a] = 0.1; }  // cov_acc_scale / cov_gyr_scale as set at :1205-1206
+      if (r->device_imu) {  // the processor's members go to the handle: the noise block as it stands now, the carry with last_imu_ = meas.imu.back()
+        lii_imu_noise nz;
+        lii_imu_noise_defaults(&nz);
+        std::memcpy(nz.cov_gyr, r->cov_gyr, 24); std::memcpy(nz.cov_acc, r->cov_acc, 24);
+        std::memcpy(nz.cov_bias_gyr, r->cov_bias_gyr, 24); std::memcpy(nz.cov_bias_acc, r->cov_bias_acc, 24);
+        std::memcpy(nz.cov_R_LI, r->cov_R_LI, 24); std::memcpy(nz.cov_T_LI, r->cov_T_LI, 24);
+        nz.mean_acc_norm = r->imu_mean_acc_norm;
+        lii_imu_carry c{};
+        c.last_imu.t = r->last_imu.t;
+        std::memcpy(c.last_imu.gyr, r->last_imu.gyr, 24); std::memcpy(c.last_imu.acc, r->last_imu.acc, 24);
+        std::memcpy(c.acc_s_last, r->acc_s_last, 24); std::memcpy(c.angvel_last, r->angvel_last, 24);
+        c.last_lidar_end_time = r->last_lidar_end_time_;
+        int rc = lii_imu_set_noise(r->h, &nz);
+        if (rc == LII_OK) rc = lii_imu_set_carry(r->h, &c);
+        if (rc != LII_OK) return fail(r, rc, std::string("lii_imu_set_noise / lii_imu_set_carry: ") + lii_last_error(r->h));
+      }
       select = false;
       job.undistort = 0;
+    } else if (r->device_imu && r->map_built) {
+      device_lio = true;  // (propagation, de-skew and update in one call further down: lii_scan_register_imu)
+      job.undistort = 1;
     } else {
       r->imu_pose.assign(r->meas_imu.size() + 2, lii_pose6d{});
       std::vector<double> imu7(r->meas_imu.size() * 7);
@@ -553,6 +581,17 @@ static int process(lii_replay* r) {
                                r->lidar_end_time, r->imu_pose.data(), &K);
       std::memcpy(r->acc_s_last, carry, 24); std::memcpy(r->angvel_last, carry + 3, 24); r->last_lidar_end_time_ = carry[6];
       r->last_imu = r->meas_imu.back();
+      if (r->device_imu) {
+        // (a LIO scan in front of the first map - not reachable on a stream whose LO phase built it - was propagated here: the handle's
+        // carry follows the host's members, so that the first device scan goes on from them)
+        lii_imu_carry c{};
+        c.last_imu.t = r->last_imu.t;
+        std::memcpy(c.last_imu.gyr, r->last_imu.gyr, 24); std::memcpy(c.last_imu.acc, r->last_imu.acc, 24);
+        std::memcpy(c.acc_s_last, r->acc_s_last, 24); std::memcpy(c.angvel_last, r->angvel_last, 24);
+        c.last_lidar_end_time = r->last_lidar_end_time_;
+        const int rcc = lii_imu_set_carry(r->h, &c);
+        if (rcc != LII_OK) return fail(r, rcc, std::string("lii_imu_set_carry: ") + lii_last_error(r->h));
+      }
       job.undistort = 1;
       job.imu_poses = r->imu_pose.data();
       job.n_imu_poses = K;
@@ -564,7 +603,12 @@ static int process(lii_replay* r) {
     if (r->b_first_frame) { dt = 0.1; r->b_first_frame = false; }
     else dt = r->lidar_beg_time - r->time_last_scan;
     r->time_last_scan = r->lidar_beg_time;
-    lii_replay_cv_propagate(&st, dt, r->cov_gyr, r->cov_acc);
+    if (r->device_imu) {
+      const int rc = lii_cv_propagate(r->h, dt, r->cov_gyr, r->cov_acc, &st);
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_cv_propagate: ") + lii_last_error(r->h));
+    } else {
+      lii_replay_cv_propagate(&st, dt, r->cov_gyr, r->cov_acc);
+    }
     job.undistort = 2;
   }
   r->state_propagat = st;
@@ -604,8 +648,20 @@ static int process(lii_replay* r) {
   // (map_incremental rides in the job - lii_scan_job::map_update: its launches are enqueued behind the update's passes)
   lii_iekf_report rep{};
   job.map_update = 1;
-  int rc = lii_scan_register(r->h, &job, &st, &r->state_propagat, &rep);
-  if (rc != LII_OK) return fail(r, rc, std::string("lii_scan_register (+ map_incremental): ") + lii_last_error(r->h));
+  int rc;
+  if (device_lio) {
+    std::vector<lii_imu_sample> imu(r->meas_imu.size());
+    for (size_t i = 0; i < imu.size(); i++) {
+      imu[i].t = r->meas_imu[i].t;
+      std::memcpy(imu[i].gyr, r->meas_imu[i].gyr, 24);
+      std::memcpy(imu[i].acc, r->meas_imu[i].acc, 24);
+    }
+    rc = lii_scan_register_imu(r->h, &job, imu.data(), int32_t(imu.size()), r->lidar_beg_time, &st, &r->state_propagat, &rep);
+    r->last_imu = r->meas_imu.back();
+  } else {
+    rc = lii_scan_register(r->h, &job, &st, &r->state_propagat, &rep);
+  }
+  if (rc != LII_OK) return fail(r, rc, std::string(device_lio ? "lii_scan_register_imu (+ map_incremental): " : "lii_scan_register (+ map_incremental): ") + lii_last_error(r->h));
   // ---- "Device starts to move, data accumulation begins" (:1151-1155)
   const double pn = std::sqrt(st.pos_end[0] * st.pos_end[0] + st.pos_end[1] * st.pos_end[1] + st.pos_end[2] * st.pos_end[2]);
   if (!r->imu_en && !r->data_accum_start && pn > 0.05) {

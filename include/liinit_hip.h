@@ -334,6 +334,68 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
  * map is unchanged by the failed update and the handle stays usable. */
 int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, int32_t* n_no_downsample);
 
+/* ---------------------------------------------------------------- IMU processing (ImuProcess::Process on the device)
+ * The FORWARD half of ImuProcess::Process (src/IMU_Processing.hpp:419-461) - what lii_undistort_imu / lii_scan_register leave to the
+ * caller: the state, the 24 x 24 covariance and the IMUpose table propagated over the scan's IMU samples (propagation_and_undist,
+ * :292-382) or by the constant-velocity model (Forward_propagation_without_imu, :212-244).  One launch per scan (k_imu_propagate /
+ * k_cv_propagate, lii_imu.hip).  What stays on the host: IMU_init (:161-200, a running mean over the first scans), the setters
+ * (:127-159 - they become lii_imu_set_noise), sync_packages, and the hand-over scans of Process() that only re-arm the processor
+ * (:426-453 - they become lii_imu_set_carry).  The L515 branch (:278-282) is not served: these entry points take no lidar type.
+ *   lii_imu_sample          one sensor_msgs/Imu as the loop reads it (:304-319): header.stamp.toSec(), angular_velocity, linear_acceleration
+ *   lii_imu_noise           cov_gyr ... cov_T_LI and IMU_mean_acc_norm, the members the setters write (:127-159).  lii_imu_noise_defaults:
+ *                           the values of ImuProcess::ImuProcess() (:97-102); mean_acc_norm - which the constructor leaves unset and main()
+ *                           installs from the parameter file - that of lii_params_defaults.  Host only, no handle.
+ *   lii_imu_carry           what ImuProcess keeps between two scans: last_imu_, acc_s_last, angvel_last, last_lidar_end_time_
+ *   lii_imu_set_noise       the setters; lii_imu_set_carry: what Process() sets on the init / switch-to-LIO scan (:432, :448: last_imu_ =
+ *                           meas.imu.back()) - or any other carry a host wants to go on from; lii_imu_get_carry: the members after Process
+ *                           (reads the device: waits for the handle's stream).
+ *   lii_imu_propagate       the forward part of propagation_and_undist alone (:292-382): `state` in = after the previous update, out =
+ *                           propagated; poses_out = IMUpose (capacity >= n_imu + 1 records, else LII_ERR_CAPACITY; *n_poses of them are
+ *                           written); the handle's carry is advanced.  A synchronous call (tests, hosts that keep their own de-skew).
+ *   lii_cv_propagate        Forward_propagation_without_imu without its de-skew (:212-244): dt as the caller's b_first_frame_ /
+ *                           time_last_scan logic gives it (:215-221), cov_gyr_scale / cov_acc_scale of :234-235; `state` in / out.
+ *   lii_scan_register_imu   Process() + the per-scan sequence in ONE call: propagate -> de-skew -> voxel filter -> iterated update
+ *                           (-> map update).  The job is lii_scan_register's with undistort == 1, imu_poses == NULL, n_imu_poses == 0
+ *                           (anything else: LII_ERR_INVALID).  `state` in is the state after the PREVIOUS update, NOT propagated; the
+ *                           propagated state, the pose table and the update's state_propagated go from k_imu_propagate to the de-skew
+ *                           and the solve in device memory.  pcl_end_time is formed on the device from the scan (pcl_beg_time + largest
+ *                           t_ms / 1000, :288: the last point of a scan_sorted job, the time-extent reduction otherwise).  The carry lives
+ *                           in the handle and is advanced by the call.  The samples are copied before the call returns (they ride in the
+ *                           pinned block that carries the update's control block; k_imu_propagate pulls both).  leaf, scan_dev,
+ *                           scan_sorted, map_update, while_waiting mean what they mean to lii_scan_register.  state_propagated_out (may
+ *                           be NULL): the propagated state, covariance included.
+ * Rules: n_imu < 1 -> LII_ERR_INVALID (the reference returns untouched when meas.imu.empty(), :423); n_imu > 63 (more than 64 poses, the
+ * limit of the fused de-skew) -> LII_ERR_CAPACITY; no noise block or no carry set -> LII_ERR_STATE.  A pre-armed launch of the handle is
+ * ended first, as by every other entry point, and job->next_scan_dev is IGNORED by lii_scan_register_imu (nothing is armed).  With a
+ * communicator attached: LII_ERR_STATE (single rank only for now).  LII_TEST=host_solve: lii_scan_register_imu returns LII_ERR_STATE
+ * (the host-driven loop has no device-resident control block to propagate into); lii_imu_propagate / lii_cv_propagate work.
+ * The carry is advanced as soon as the propagation launch is on the stream: a call that fails BEHIND it (e.g. LII_ERR_STATE "no map",
+ * a singular solve) has still consumed its samples, as Process() has when the update behind it fails; a call refused by the rules above,
+ * or whose propagation launch itself fails, leaves the carry as it was.
+ * lii_set_profiling(h, 3) attributes the new launch (and, for a scan that is not scan_sorted, the time-extent launch in front of it)
+ * to LII_KP_PROPAGATE. */
+typedef struct lii_imu_sample { double t; double gyr[3]; double acc[3]; } lii_imu_sample; /* 56 bytes */
+typedef struct lii_imu_noise {
+  uint32_t struct_size; /* sizeof(lii_imu_noise) */
+  int32_t reserved0;
+  double cov_gyr[3], cov_acc[3], cov_bias_gyr[3], cov_bias_acc[3], cov_R_LI[3], cov_T_LI[3];
+  double mean_acc_norm;
+} lii_imu_noise;
+typedef struct lii_imu_carry {
+  lii_imu_sample last_imu;
+  double acc_s_last[3], angvel_last[3];
+  double last_lidar_end_time;
+} lii_imu_carry;
+int lii_imu_noise_defaults(lii_imu_noise* out);
+int lii_imu_set_noise(lii_handle h, const lii_imu_noise* noise);
+int lii_imu_set_carry(lii_handle h, const lii_imu_carry* carry);
+int lii_imu_get_carry(lii_handle h, lii_imu_carry* out);
+int lii_imu_propagate(lii_handle h, const lii_imu_sample* imu, int32_t n_imu, double pcl_beg_time, double pcl_end_time, lii_state* state,
+                      lii_pose6d* poses_out, int32_t capacity, int32_t* n_poses);
+int lii_cv_propagate(lii_handle h, double dt, const double cov_gyr_scale[3], const double cov_acc_scale[3], lii_state* state);
+int lii_scan_register_imu(lii_handle h, const lii_scan_job* job, const lii_imu_sample* imu, int32_t n_imu, double pcl_beg_time,
+                          lii_state* state, lii_state* state_propagated_out, lii_iekf_report* report);
+
 /* ---------------------------------------------------------------- LI-Init batch calibration evaluators
  * CalibState record (include/LI_init/LI_init.h:31-89). */
 typedef struct lii_calib_state {
@@ -513,6 +575,7 @@ enum lii_kernel_kind {
   LII_KP_FIT_SEARCH = 3, /* plane fit + residual + reduction behind a k-NN pass */
   LII_KP_FIT = 4,        /* residual + reduction on cached planes */
   LII_KP_SOLVE = 5,      /* final sum + 24-state solve */
+  LII_KP_PROPAGATE = 6,  /* lii_scan_register_imu: IMU forward propagation (+ the time-extent launch of an unsorted scan in front of it) */
   LII_KP_KINDS = 8
 };
 typedef struct lii_kernel_profile {

@@ -59,7 +59,22 @@ class lii_kernel_profile(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("scans", C.c_int32), ("ms", C.c_double * 8), ("launches", C.c_int32 * 8)]
 
 
-KERNEL_KINDS = ("deskew", "voxel", "knn", "fit_search", "fit", "solve")  # enum lii_kernel_kind
+KERNEL_KINDS = ("deskew", "voxel", "knn", "fit_search", "fit", "solve", "propagate")  # enum lii_kernel_kind
+
+
+class lii_imu_sample(C.Structure):
+    _fields_ = [("t", C.c_double), ("gyr", C.c_double * 3), ("acc", C.c_double * 3)]
+
+
+class lii_imu_noise(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("cov_gyr", C.c_double * 3), ("cov_acc", C.c_double * 3),
+                ("cov_bias_gyr", C.c_double * 3), ("cov_bias_acc", C.c_double * 3), ("cov_R_LI", C.c_double * 3),
+                ("cov_T_LI", C.c_double * 3), ("mean_acc_norm", C.c_double)]
+
+
+class lii_imu_carry(C.Structure):
+    _fields_ = [("last_imu", lii_imu_sample), ("acc_s_last", C.c_double * 3), ("angvel_last", C.c_double * 3),
+                ("last_lidar_end_time", C.c_double)]
 
 
 class lii_pc2_fields(C.Structure):
@@ -126,6 +141,15 @@ _DECLS = {
     "lii_neighbors_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_last_solve_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_last_unfinished_queries": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "lii_imu_noise_defaults": (C.c_int, [C.POINTER(lii_imu_noise)]),
+    "lii_imu_set_noise": (C.c_int, [C.c_void_p, C.POINTER(lii_imu_noise)]),
+    "lii_imu_set_carry": (C.c_int, [C.c_void_p, C.POINTER(lii_imu_carry)]),
+    "lii_imu_get_carry": (C.c_int, [C.c_void_p, C.POINTER(lii_imu_carry)]),
+    "lii_imu_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.POINTER(C.c_int32)]),
+    "lii_cv_propagate": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_scan_register_imu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.POINTER(lii_iekf_report)]),
     "lii_map_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_calib_set_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_calib_eval": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -489,6 +513,92 @@ class Registrar:
         self._check(self.L.lii_scan_register(self.h, C.byref(job), _ptr(state.pod), _ptr(state_prop.pod), C.byref(rep)))
         return dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
                     converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+
+    # ------------------------------------------------------------------ IMU processing (ImuProcess::Process on the device)
+    def set_imu_noise(self, cov_gyr=None, cov_acc=None, cov_bias_gyr=None, cov_bias_acc=None, cov_R_LI=None, cov_T_LI=None,
+                      mean_acc_norm=None):
+        """The setters of ImuProcess (src/IMU_Processing.hpp:127-159); what is left None keeps the constructor's value
+        (lii_imu_noise_defaults).  Scalars are spread over the three axes."""
+        nz = lii_imu_noise()
+        self._check(self.L.lii_imu_noise_defaults(C.byref(nz)), None)
+        for name, v in (("cov_gyr", cov_gyr), ("cov_acc", cov_acc), ("cov_bias_gyr", cov_bias_gyr), ("cov_bias_acc", cov_bias_acc),
+                        ("cov_R_LI", cov_R_LI), ("cov_T_LI", cov_T_LI)):
+            if v is not None:
+                getattr(nz, name)[:] = list(np.broadcast_to(np.asarray(v, np.float64), (3,)))
+        if mean_acc_norm is not None:
+            nz.mean_acc_norm = float(mean_acc_norm)
+        self._check(self.L.lii_imu_set_noise(self.h, C.byref(nz)))
+
+    @property
+    def imu_carry(self):
+        """dict(last_imu (7,) = t, gyr, acc; acc_s_last, angvel_last, last_lidar_end_time) - the members ImuProcess keeps between scans."""
+        c = lii_imu_carry()
+        self._check(self.L.lii_imu_get_carry(self.h, C.byref(c)))
+        return dict(last_imu=np.r_[c.last_imu.t, c.last_imu.gyr[:], c.last_imu.acc[:]], acc_s_last=np.array(c.acc_s_last[:]),
+                    angvel_last=np.array(c.angvel_last[:]), last_lidar_end_time=float(c.last_lidar_end_time))
+
+    @imu_carry.setter
+    def imu_carry(self, d):
+        c = lii_imu_carry()
+        li = np.asarray(d["last_imu"], np.float64).reshape(7)
+        c.last_imu.t = float(li[0])
+        c.last_imu.gyr[:] = list(li[1:4])
+        c.last_imu.acc[:] = list(li[4:7])
+        c.acc_s_last[:] = list(np.asarray(d.get("acc_s_last", np.zeros(3)), np.float64))
+        c.angvel_last[:] = list(np.asarray(d.get("angvel_last", np.zeros(3)), np.float64))
+        c.last_lidar_end_time = float(d.get("last_lidar_end_time", 0.0))
+        self._check(self.L.lii_imu_set_carry(self.h, C.byref(c)))
+
+    def propagate_imu(self, imu, pcl_beg_time, pcl_end_time, state: State):
+        """The forward part of propagation_and_undist (:292-382).  imu: (n, 7) rows (t, gyr, acc).  Returns (propagated state,
+        IMUpose table (K, 22)); `state` is left as it was, the handle's carry is advanced."""
+        imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+        out = state.copy()
+        poses = pose6d_array(len(imu) + 1)
+        k = C.c_int32(0)
+        self._check(self.L.lii_imu_propagate(self.h, _ptr(imu) if len(imu) else None, len(imu), float(pcl_beg_time), float(pcl_end_time),
+                                             _ptr(out.pod), _ptr(poses), len(poses), C.byref(k)))
+        return out, poses[:k.value]
+
+    def propagate_cv(self, dt, cov_gyr_scale, cov_acc_scale, state: State):
+        """Forward_propagation_without_imu without its de-skew (:212-244); returns the propagated state."""
+        out = state.copy()
+        cg = np.ascontiguousarray(np.broadcast_to(np.asarray(cov_gyr_scale, np.float64), (3,)))
+        ca = np.ascontiguousarray(np.broadcast_to(np.asarray(cov_acc_scale, np.float64), (3,)))
+        self._check(self.L.lii_cv_propagate(self.h, float(dt), _ptr(cg), _ptr(ca), _ptr(out.pod)))
+        return out
+
+    def register_imu(self, imu, pcl_beg_time, state: State, *, leaf=0.0, max_iterations=4, imu_en=True, scan_dev=None, scan_sorted=False,
+                     map_update=False, next_scan=None, while_waiting=None, imu_poses=None, want_propagated=True):
+        """ImuProcess::Process + de-skew + voxel grid + iterated update in one library call (lii_scan_register_imu): `state` in is the
+        state after the previous update and is updated in place.  Returns (state, propagated state or None, report dict).  The
+        keywords are scan_register's; imu_poses must stay None (the table is formed on the device)."""
+        imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+        job = lii_scan_job()
+        job.struct_size = C.sizeof(lii_scan_job)
+        job.undistort = 1
+        job.scan_sorted = 1 if scan_sorted else 0
+        job.map_update = 1 if map_update else 0
+        if scan_dev is not None:
+            job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
+        if next_scan is not None:
+            job.next_scan_dev, job.next_n_scan = next_scan[0], next_scan[1]
+        hook = None
+        if while_waiting is not None:
+            hook = WAIT_HOOK(lambda _arg: while_waiting())
+            job.while_waiting = C.cast(hook, C.c_void_p)
+        poses = None
+        if imu_poses is not None:
+            poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
+            job.imu_poses, job.n_imu_poses = _ptr(poses), len(poses)
+        job.leaf = float(leaf)
+        job.opts = lii_iekf_opts(int(max_iterations), int(imu_en))
+        rep = lii_iekf_report()
+        prop = State() if want_propagated else None
+        self._check(self.L.lii_scan_register_imu(self.h, C.byref(job), _ptr(imu) if len(imu) else None, len(imu), float(pcl_beg_time),
+                                                 _ptr(state.pod), _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
+        return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
+                                 converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
 
     def neighbors(self, n):
         pts = np.zeros((n, 5, 3), np.float32)

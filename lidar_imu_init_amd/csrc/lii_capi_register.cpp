@@ -2,6 +2,8 @@
 // download.  Kernels: lii_kernels.hip (k-NN, fit + reduce), lii_iekf.hip (final sum + 24-state solve), lii_scan.hip (prologue of
 // lii_scan_register).  Reference: src/laserMapping.cpp:909-1134.
 #include "lii_context.h"
+#include <cstddef>
+
 #include "lii_hostmath.h"
 
 using namespace lii_impl;
@@ -363,124 +365,89 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
 }
 
 
+
+// The prologue of lii_scan_register_imu: IMU forward propagation and de-skew, back to back on the stream.  The host's part is what it
+// knows BEFORE the previous update has ended - the samples - and the state that update left; everything that depends on them (the
+// propagated state, the IMUpose table, the update's control block with state and state_propagat filled in) is formed on the device.
+int imu_prologue(lii_handle h, const lii_scan_job* job, const ImuFeed* feed, const lii_state* state, bool adopt, const float4* src_dev, int n_next,
+                 bool sorted) {
+  if (n_next <= 0) return fail(h, LII_ERR_STATE, "lii_scan_register_imu: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
+  int rc = imu_buffers(h);
+  if (rc != LII_OK) return rc;
+  if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
+  HIPCHK(h, hipEventSynchronize(h->ev_poses));  // a pose table uploaded by a stand-alone lii_undistort_imu (long done): the samples take its staging area
+  h->staging_busy = true;
+  fill_ctrl(h, state, state, &job->opts);  // (st / prop of the block on the device are written by k_imu_propagate, not pulled)
+  std::memcpy(h->h_poses, feed->imu, sizeof(lii_imu_sample) * size_t(feed->n_imu));
+  extent_discard(h);
+  h->n_scan = n_next;
+  h->n_body = 0;
+  h->n_body_pending = false;
+  h->have_search = false;
+  const float fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
+  h->vh_inserted = fuse_filter(h, fuse_leaf);
+  if (h->vh_inserted) h->vh_inserted_leaf = fuse_leaf;
+  const float4* in = adopt ? src_dev : h->d_scan.get();
+  const unsigned long long* ext = nullptr;
+  if (!sorted) {  // the sweep's end and the time-earliest point of a scan in any order: the time-extent reduction (adopting the scan on the way)
+    unsigned long long* e = h->d_extent + 2 * h->extent_sel;
+    launch_time_extent(in, n_next, e, h->d_extent + 2 * (h->extent_sel ^ 1), adopt ? h->d_scan.get() : nullptr, nullptr, nullptr, 0, h->stream);
+    h->extent_sel ^= 1;
+    ext = e;
+    in = h->d_scan;
+  }
+  ImuPropArgs a = {};
+  a.st_in = h->h_ctrl->st;
+  a.samples = reinterpret_cast<const double*>(h->h_poses);
+  a.n_imu = feed->n_imu;
+  static_assert(sizeof(lii_imu_noise) == 8 + 19 * sizeof(double), "lii_imu_noise layout");
+  std::memcpy(a.noise, h->imu.noise.cov_gyr, sizeof(a.noise));
+  a.pcl_beg_time = feed->pcl_beg_time;
+  a.scan = in; a.n_scan = n_next; a.sorted = sorted ? 1 : 0; a.extent = ext;
+  a.carry_in = h->imu.d_carry(h->imu.carry_sel);
+  a.carry_out = h->imu.d_carry(h->imu.carry_sel ^ 1);
+  a.poses = h->d_poses;
+  a.n_poses = h->imu.d_n_poses();
+  a.st_out = h->d_ctrl->st;
+  a.prop_out = h->d_ctrl->prop;
+  a.host_out = feed->prop_out ? h->imu.h_out.get() : nullptr;
+  a.ctrl_src = reinterpret_cast<const uint4*>(h->h_ctrl);
+  a.ctrl_dst = reinterpret_cast<uint4*>(h->d_ctrl);
+  static_assert(offsetof(IekfCtrl, solution) % 16 == 0 && offsetof(IekfCtrl, prop) + sizeof(IekfCtrl::prop) == offsetof(IekfCtrl, solution), "IekfCtrl: the two states come first");
+  a.ctrl_from = int(offsetof(IekfCtrl, solution) / 16);
+  a.ctrl_vec = int((sizeof(IekfCtrl) + 15) / 16);
+  launch_imu_propagate(a, h->stream);
+  {
+    const hipError_t e_prop = hipGetLastError();
+    if (e_prop != hipSuccess) { h->vh_inserted = false; return fail(h, LII_ERR_HIP, std::string("IMU propagation launch: ") + hipGetErrorString(e_prop)); }
+  }
+  h->imu.carry_sel ^= 1;  // the launch is on the stream: the carry it writes is the current one from here on, whatever becomes of the rest of the call
+  if (h->prof.kp_active) { rc = kp_mark(h, LII_KP_DESKEW); if (rc != LII_OK) return rc; }
+  DeskewPlan dp = {};
+  dp.in = in; dp.out = h->d_scan; dp.n = n_next; dp.sorted = sorted ? 1 : 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
+  dp.leaf = fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
+#ifdef LII_GAP_TRACE
+  dp.gap = h->d_gran;
+#endif
+  launch_deskew_imu_dev(dp, h->d_ctrl->st, h->imu.d_n_poses(), h->d_poses, h->stream);
+  h->bbox_rows = (n_next + 255) / 256;
+  h->ctrl_preloaded = true;
+  const hipError_t e_launch = hipGetLastError();
+  if (e_launch != hipSuccess) { h->vh_inserted = false; h->ctrl_preloaded = false; return fail(h, LII_ERR_HIP, std::string("de-skew launch behind the IMU propagation: ") + hipGetErrorString(e_launch)); }
+  return LII_OK;
+}
+
 }  // namespace
 
-extern "C" {
-
-// ------------------------------------------------------------------------------------------------ registration
-int lii_last_solve_info(lii_handle h, int32_t* pivoted_passes) {
-  if (!h || !pivoted_passes) return LII_ERR_INVALID;
-  *pivoted_passes = h->last_pivoted_passes;
-  return LII_OK;
-}
-
-int lii_last_unfinished_queries(lii_handle h, int32_t* n_last) {
-  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
-  if (!h || !n_last) return LII_ERR_INVALID;
-  if (h->unfinished_known) { *n_last = h->h_res->unfinished; return LII_OK; }  // (came with the last update's result: the largest count among its search passes)
-  int c[2] = {0, 0};
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(c, h->d_flags, sizeof(c), hipMemcpyDeviceToHost));  // RegistrationBuffers::flag_count, one word per slot
-  *n_last = c[h->knn_epoch & 1];  // (consecutive launch numbers alternate between the two slots; a launch clears the other one)
-  return LII_OK;
-}
-
-int lii_iekf_iterate(lii_handle h, const lii_state* state, int32_t search, int32_t imu_en, double out91[91]) {
-  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
-  if (!h || !state || !out91) return fail(h, LII_ERR_INVALID, "lii_iekf_iterate: bad arguments");
-  return iterate(h, state, search != 0, imu_en != 0, out91);
-}
-
-int lii_iekf_update(lii_handle h, lii_state* state, const lii_state* state_prop, const lii_iekf_opts* opts,
-                    lii_iekf_report* report) {
-  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
-  if (!h || !state || !state_prop || !opts || opts->max_iterations < 1) return fail(h, LII_ERR_INVALID, "lii_iekf_update: bad arguments");
-  const int max_it = opts->max_iterations;
-  auto t_begin = std::chrono::steady_clock::now();
-  if (!h->host_solve) {
-    int rc = update_on_device(h, state, state_prop, opts, report);
-    h->prof.timings[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return rc;
-  }
-  double host_ms = 0;
-  // cov is constant inside the loop (it is only rewritten on exit, :1112-1114), so invert it once
-  std::vector<double> Pinv(kDim * kDim), A(kDim * kDim), K1(kDim * kDim), KH(kDim * 12), G(kDim * kDim);
-  if (!mat_inverse(state->cov, kDim, Pinv.data())) return fail(h, LII_ERR_INVALID, "state covariance is singular");
-  int rematch_num = 0;
-  bool search = true, stop = false, converged = false;
-  int it = 0, searches = 0;
-  double ne[kNormalEq];
-  for (it = 0; it < max_it; it++) {
-    int rc = iterate(h, state, search, opts->imu_en != 0, ne);
-    if (rc != LII_OK) return rc;
-    if (search) searches++;
-    auto t0 = std::chrono::steady_clock::now();
-    // H_T_H (+) P^-1  (:1080-1081)
-    A = Pinv;
-    double HTH[12][12];
-    int t = 0;
-    for (int i = 0; i < 12; i++)
-      for (int j = i; j < 12; j++) { HTH[i][j] = ne[t]; HTH[j][i] = ne[t]; t++; }
-    for (int i = 0; i < 12; i++)
-      for (int j = 0; j < 12; j++) A[size_t(i) * kDim + j] += HTH[i][j];
-    if (!mat_inverse(A.data(), kDim, K1.data())) return fail(h, LII_ERR_INVALID, "normal matrix is singular");
-    double vec[kDim], sol[kDim];
-    state_minus(*state_prop, *state, vec);
-    for (int r = 0; r < kDim; r++) {
-      double kz = 0;
-      for (int c = 0; c < 12; c++) kz += K1[size_t(r) * kDim + c] * ne[78 + c];
-      double khv = 0;
-      for (int c = 0; c < 12; c++) {
-        double s = 0;
-        for (int k = 0; k < 12; k++) s += K1[size_t(r) * kDim + k] * HTH[k][c];
-        KH[size_t(r) * 12 + c] = s;
-        khv += s * vec[c];
-      }
-      sol[r] = kz + vec[r] - khv;
-    }
-    state_plus(*state, sol);
-    double rn = std::sqrt(sol[0] * sol[0] + sol[1] * sol[1] + sol[2] * sol[2]);
-    double tn = std::sqrt(sol[3] * sol[3] + sol[4] * sol[4] + sol[5] * sol[5]);
-    converged = (rn * 57.3 < 0.01) && (tn * 100 < 0.015);
-    search = false;
-    if (converged || ((rematch_num == 0) && (it == (max_it - 2)))) {
-      search = true;
-      rematch_num++;
-    }
-    if (!stop && (rematch_num >= 2 || (it == max_it - 1))) {
-      // state.cov = (I - G) cov, G[:, :12] = K H   (:1111-1114)
-      std::vector<double> newcov(kDim * kDim);
-      for (int r = 0; r < kDim; r++)
-        for (int c = 0; c < kDim; c++) {
-          double s = state->cov[size_t(r) * kDim + c];
-          for (int k = 0; k < 12; k++) s -= KH[size_t(r) * 12 + k] * state->cov[size_t(k) * kDim + c];
-          newcov[size_t(r) * kDim + c] = s;
-        }
-      std::memcpy(state->cov, newcov.data(), sizeof(double) * kDim * kDim);
-      stop = true;
-    }
-    host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (stop) { it++; break; }
-  }
-  if (report) {
-    report->iterations = it;
-    report->searches = searches;
-    report->effect_num = int(ne[90]);
-    report->converged = converged ? 1 : 0;
-    std::memcpy(report->normal_eq, ne, sizeof(ne));
-  }
-  h->prof.timings[3] = host_ms;
-  h->prof.timings[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  return LII_OK;
-}
-
-int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop,
-                      lii_iekf_report* report) {
+// lii_scan_register, and - feed != nullptr - lii_scan_register_imu (lii_capi_imu.cpp: its checks are made there; state_prop is not used)
+int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report,
+                                const ImuFeed* feed) {
+  const char* const who = feed ? "lii_scan_register_imu" : "lii_scan_register";
   // (struct_size 48: a job of ABI 5, without scan_sorted)
   // (struct_size 88: ABI 9; 72: ABI 8, without while_waiting; 56: ABI 6 - 7, without next_scan_dev; 48: ABI 5, without scan_sorted)
   static_assert(sizeof(lii_scan_job) == 88, "lii_scan_job: the sizes of the earlier ABIs are accepted by number");
-  if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || !state_prop || job->opts.max_iterations < 1)
-    return fail(h, LII_ERR_INVALID, "lii_scan_register: bad arguments");
+  if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || (!state_prop && !feed) || job->opts.max_iterations < 1)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
   const bool sorted = job->struct_size >= 56u && job->scan_sorted == 1;
   h->scan_buf_idle = false;
   int rc = LII_OK;
@@ -491,7 +458,7 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
   const void* const src_dev = from_job ? job->scan_dev : static_cast<const void*>(h->scan_pending);
   const int src_n = from_job ? job->n_scan_dev : h->scan_pending_n;
   const bool adopt = src_dev != nullptr && src_n > 0;
-  if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_scan_register: n_scan_dev > max_scan_points");
+  if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": n_scan_dev > max_scan_points");
   const int n_next = adopt ? src_n : h->n_scan;
   // A gated de-skew launch waits on the stream (the previous call enqueued it for the scan its job announced): it is used when THIS
   // call asks for exactly that, and told to end otherwise - before anything here could wait for the stream.
@@ -503,13 +470,14 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
   bool use_pre = h->pre.armed && sorted && job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= lii::kGateMaxPoses &&
                  cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && leaf_now == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
                  h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, leaf_now) == h->pre.fuse;
+  if (feed) use_pre = false;  // (lii_scan_register_imu: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
   if (!use_pre) prearm_cancel(h);
   // ... and what this job announces for the next call (update_on_device arms it behind the passes)
   h->pre.want_dev = nullptr;
-  if (job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
+  if (!feed && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
       sorted && job->undistort == 1) {
     h->pre.want_dev = job->next_scan_dev; h->pre.want_n = job->next_n_scan; h->pre.want_leaf = leaf_now; h->pre.want_late = false;
-  } else if (h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
+  } else if (!feed && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
     // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
     h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = leaf_now; h->pre.want_late = true;
   }
@@ -519,13 +487,16 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
   // time extent + pull: 8.9 us per scan).
   h->prof.kp_active = h->prof.prof_mode == 3 && !h->host_solve;
   h->prof.kp_n = 0;
-  if (h->prof.kp_active) { rc = kp_mark(h, LII_KP_DESKEW); if (rc != LII_OK) { h->prof.kp_active = false; return rc; } }
+  if (h->prof.kp_active) { rc = kp_mark(h, feed ? LII_KP_PROPAGATE : LII_KP_DESKEW); if (rc != LII_OK) { h->prof.kp_active = false; return rc; } }
   const bool fast = sorted && !h->host_solve && n_next > 0 && !h->no_fast_prologue &&
                     ((job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= 64) || job->undistort == 2);
   if (use_pre && !fast) { prearm_cancel(h); use_pre = false; }  // (cannot happen with the conditions above; a waiting launch must never be left behind a call that will not feed it)
-  if (job->undistort != 0 && job->undistort != 1 && job->undistort != 2) return fail(h, LII_ERR_INVALID, "lii_scan_register: undistort must be 0, 1 or 2");
+  if (job->undistort != 0 && job->undistort != 1 && job->undistort != 2) return fail(h, LII_ERR_INVALID, std::string(who) + ": undistort must be 0, 1 or 2");
   const auto t_first = std::chrono::steady_clock::now();
-  if (fast) {
+  if (feed) {
+    rc = imu_prologue(h, job, feed, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
+    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
+  } else if (fast) {
     if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
     h->staging_busy = true;
     fill_ctrl(h, state, state_prop, &job->opts);
@@ -652,7 +623,7 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
   // arrangement without that wait (LII_TEST=host_solve) calls it behind the update - once per call that got this far, never otherwise
   h->wait_hook = (rc == LII_OK && job->struct_size >= 88u) ? job->while_waiting : nullptr;
   h->wait_hook_arg = job->struct_size >= 88u ? job->while_waiting_arg : nullptr;
-  if (rc == LII_OK) rc = lii_iekf_update(h, state, state_prop, &job->opts, report);
+  if (rc == LII_OK) rc = lii_iekf_update(h, state, state_prop ? state_prop : state, &job->opts, report);
   if (h->wait_hook) {
     void (*hook)(void*) = h->wait_hook;
     h->wait_hook = nullptr;
@@ -673,9 +644,124 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
     h->prof.host_us[4] += 1;
     h->prof.host_last_return = t_end;
   }
+  // lii_scan_register_imu: the propagated state, as k_imu_propagate left it in mapped host memory (it ran in front of the passes whose result has arrived)
+  if (rc == LII_OK && feed && feed->prop_out) std::memcpy(feed->prop_out, h->imu.h_out.get(), sizeof(lii_state));
   return rc;
 }
 
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ registration
+int lii_last_solve_info(lii_handle h, int32_t* pivoted_passes) {
+  if (!h || !pivoted_passes) return LII_ERR_INVALID;
+  *pivoted_passes = h->last_pivoted_passes;
+  return LII_OK;
+}
+
+int lii_last_unfinished_queries(lii_handle h, int32_t* n_last) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !n_last) return LII_ERR_INVALID;
+  if (h->unfinished_known) { *n_last = h->h_res->unfinished; return LII_OK; }  // (came with the last update's result: the largest count among its search passes)
+  int c[2] = {0, 0};
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(c, h->d_flags, sizeof(c), hipMemcpyDeviceToHost));  // RegistrationBuffers::flag_count, one word per slot
+  *n_last = c[h->knn_epoch & 1];  // (consecutive launch numbers alternate between the two slots; a launch clears the other one)
+  return LII_OK;
+}
+
+int lii_iekf_iterate(lii_handle h, const lii_state* state, int32_t search, int32_t imu_en, double out91[91]) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !state || !out91) return fail(h, LII_ERR_INVALID, "lii_iekf_iterate: bad arguments");
+  return iterate(h, state, search != 0, imu_en != 0, out91);
+}
+
+int lii_iekf_update(lii_handle h, lii_state* state, const lii_state* state_prop, const lii_iekf_opts* opts,
+                    lii_iekf_report* report) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !state || !state_prop || !opts || opts->max_iterations < 1) return fail(h, LII_ERR_INVALID, "lii_iekf_update: bad arguments");
+  const int max_it = opts->max_iterations;
+  auto t_begin = std::chrono::steady_clock::now();
+  if (!h->host_solve) {
+    int rc = update_on_device(h, state, state_prop, opts, report);
+    h->prof.timings[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return rc;
+  }
+  double host_ms = 0;
+  // cov is constant inside the loop (it is only rewritten on exit, :1112-1114), so invert it once
+  std::vector<double> Pinv(kDim * kDim), A(kDim * kDim), K1(kDim * kDim), KH(kDim * 12), G(kDim * kDim);
+  if (!mat_inverse(state->cov, kDim, Pinv.data())) return fail(h, LII_ERR_INVALID, "state covariance is singular");
+  int rematch_num = 0;
+  bool search = true, stop = false, converged = false;
+  int it = 0, searches = 0;
+  double ne[kNormalEq];
+  for (it = 0; it < max_it; it++) {
+    int rc = iterate(h, state, search, opts->imu_en != 0, ne);
+    if (rc != LII_OK) return rc;
+    if (search) searches++;
+    auto t0 = std::chrono::steady_clock::now();
+    // H_T_H (+) P^-1  (:1080-1081)
+    A = Pinv;
+    double HTH[12][12];
+    int t = 0;
+    for (int i = 0; i < 12; i++)
+      for (int j = i; j < 12; j++) { HTH[i][j] = ne[t]; HTH[j][i] = ne[t]; t++; }
+    for (int i = 0; i < 12; i++)
+      for (int j = 0; j < 12; j++) A[size_t(i) * kDim + j] += HTH[i][j];
+    if (!mat_inverse(A.data(), kDim, K1.data())) return fail(h, LII_ERR_INVALID, "normal matrix is singular");
+    double vec[kDim], sol[kDim];
+    state_minus(*state_prop, *state, vec);
+    for (int r = 0; r < kDim; r++) {
+      double kz = 0;
+      for (int c = 0; c < 12; c++) kz += K1[size_t(r) * kDim + c] * ne[78 + c];
+      double khv = 0;
+      for (int c = 0; c < 12; c++) {
+        double s = 0;
+        for (int k = 0; k < 12; k++) s += K1[size_t(r) * kDim + k] * HTH[k][c];
+        KH[size_t(r) * 12 + c] = s;
+        khv += s * vec[c];
+      }
+      sol[r] = kz + vec[r] - khv;
+    }
+    state_plus(*state, sol);
+    double rn = std::sqrt(sol[0] * sol[0] + sol[1] * sol[1] + sol[2] * sol[2]);
+    double tn = std::sqrt(sol[3] * sol[3] + sol[4] * sol[4] + sol[5] * sol[5]);
+    converged = (rn * 57.3 < 0.01) && (tn * 100 < 0.015);
+    search = false;
+    if (converged || ((rematch_num == 0) && (it == (max_it - 2)))) {
+      search = true;
+      rematch_num++;
+    }
+    if (!stop && (rematch_num >= 2 || (it == max_it - 1))) {
+      // state.cov = (I - G) cov, G[:, :12] = K H   (:1111-1114)
+      std::vector<double> newcov(kDim * kDim);
+      for (int r = 0; r < kDim; r++)
+        for (int c = 0; c < kDim; c++) {
+          double s = state->cov[size_t(r) * kDim + c];
+          for (int k = 0; k < 12; k++) s -= KH[size_t(r) * 12 + k] * state->cov[size_t(k) * kDim + c];
+          newcov[size_t(r) * kDim + c] = s;
+        }
+      std::memcpy(state->cov, newcov.data(), sizeof(double) * kDim * kDim);
+      stop = true;
+    }
+    host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stop) { it++; break; }
+  }
+  if (report) {
+    report->iterations = it;
+    report->searches = searches;
+    report->effect_num = int(ne[90]);
+    report->converged = converged ? 1 : 0;
+    std::memcpy(report->normal_eq, ne, sizeof(ne));
+  }
+  h->prof.timings[3] = host_ms;
+  h->prof.timings[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  return LII_OK;
+}
+
+int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop,
+                      lii_iekf_report* report) {
+  return scan_register_job(h, job, state, state_prop, report, nullptr);
+}
 int lii_neighbors_download(lii_handle h, float* pts, int32_t* counts, uint8_t* selected, int32_t capacity) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   if (!h) return LII_ERR_INVALID;

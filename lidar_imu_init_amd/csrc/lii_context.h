@@ -4,6 +4,7 @@
 //   lii_capi_register.cpp  the registration loop: lii_iekf_*, lii_scan_register, neighbour download
 //   lii_capi_comm.cpp      the communicator of a sharded job (node-local mailbox / RCCL)
 //   lii_capi_calib.cpp     the LI_init evaluators' entry points
+//   lii_capi_imu.cpp       IMU forward propagation: lii_imu_*, lii_cv_propagate, lii_scan_register_imu
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -241,7 +242,7 @@ struct lii_context {
 
   // ---- pinned staging
   PinnedBuf<float4> h_stage;     // max(max_scan, max_map) float4
-  PinnedBuf<double> h_small;     // 4096 doubles
+  PinnedBuf<double> h_small;     // 32 768 doubles
 
   // ---- calibration
   struct CalibState {  // lii_capi_calib.cpp: the LI_init evaluators' buffers
@@ -250,6 +251,18 @@ struct lii_context {
 
     bool li_init_device = false;  // lii_li_init_set_device: zero-phase filter + cross-correlation of lii_li_init_run on the device
   } cal;
+  // ---- IMU processing (lii_capi_imu.cpp, lii_imu.hip)
+  struct ImuState {
+    lii_imu_noise noise{};
+    bool have_noise = false, have_carry = false;
+    DevBuf<double> d_buf;       // carry (ping) | carry (pong) | number of poses (an int) | a propagated state (stand-alone calls); created on first use
+    int carry_sel = 0;          // which of the two carries is current
+    PinnedBuf<double> h_in;     // pinned: state | samples of a stand-alone lii_imu_propagate / lii_cv_propagate
+    PinnedBuf<double> h_out;    // pinned, device-mapped: propagated state | carry | number of poses, written by the kernels
+    double* d_carry(int sel) const { return d_buf.get() + lii::kImuCarryDoubles * sel; }
+    int* d_n_poses() const { return reinterpret_cast<int*>(d_buf.get() + 2 * lii::kImuCarryDoubles); }
+    double* d_state() const { return d_buf.get() + 2 * lii::kImuCarryDoubles + 8; }
+  } imu;
   void* ingest = nullptr;  // lii_ingest.hip state (frames of the last driver message)
   bool ingest_sort_always = false;  // LII_INGEST_SORT=always: the ingest never leaves the time sort out (IngestRing::never_predict)
 
@@ -331,6 +344,16 @@ int map_gather(lii_handle h, int* n_out);
 int map_rebuild(lii_handle h, int extra_blocks);
 int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, const float4* extra, int n_extra, bool beside = false,
               const int* n_list_dev = nullptr, const int* n_extra_dev = nullptr, bool count_events = true, bool prefilled = false);
+// lii_capi_register.cpp / lii_capi_imu.cpp
+// lii_scan_register_imu hands lii_scan_register's job to the same routine with the scan's IMU samples instead of a pose table
+struct ImuFeed {
+  const lii_imu_sample* imu;
+  int n_imu;
+  double pcl_beg_time;
+  lii_state* prop_out;  // may be nullptr
+};
+int scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report, const ImuFeed* feed);
+int imu_buffers(lii_handle h);  // creates lii_context::imu's buffers on first use
 // lii_capi_comm.cpp
 void comm_drop(lii_handle h);
 void partition_refresh(lii_handle h);  // the voxel filter's view of the job after the communicator or its partition changed

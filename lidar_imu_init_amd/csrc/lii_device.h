@@ -43,6 +43,36 @@ __device__ __forceinline__ void mat3t_vec(const double A[9], const double v[3], 
   for (int r = 0; r < 3; r++) o[r] = A[r] * v[0] + A[3 + r] * v[1] + A[6 + r] * v[2];
 }
 
+// order-preserving uint -> float (the inverse of the map the min / max reductions of a scan use)
+__device__ __forceinline__ float ord2f(unsigned int o) {
+  unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+  return __uint_as_float(u);
+}
+
+// Exp(ang_vel, dt) — include/so3_math.h:37-59 — applied to a vector: R v with Rodrigues, R built explicitly
+__device__ __forceinline__ void exp_so3(const double w[3], double dt, double R[9]) {
+  double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  if (n > 0.0000001) {
+    double ax = w[0] / n, ay = w[1] / n, az = w[2] / n;
+    double ang = n * dt;
+    double s = sin(ang), c1 = 1.0 - cos(ang);
+    // K = skew(axis).  The reference writes `(1.0 - cos) * K * K`, which C++ evaluates as ((1 - cos) K) K: the scalar is
+    // rounded into K before the product (so3_math.h:48-53; pinned by tests/test_oracle_math_pinned.py)
+    double K[9] = {0, -az, ay, az, 0, -ax, -ay, ax, 0};
+    double cK[9], KK[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) cK[e] = c1 * K[e];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) KK[3 * r + c] = cK[3 * r] * K[c] + cK[3 * r + 1] * K[3 + c] + cK[3 * r + 2] * K[6 + c];
+#pragma unroll
+    for (int e = 0; e < 9; e++) R[e] = ((e % 4 == 0) ? 1.0 : 0.0) + s * K[e] + KK[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 9; e++) R[e] = (e % 4 == 0) ? 1.0 : 0.0;
+  }
+}
 // Pose the per-point kernels need: state.rot_end, pos_end, offset_R_L_I, offset_T_L_I (row-major).
 struct PoseArg {
   double R[9];

@@ -168,6 +168,41 @@ struct DeskewGate {
 };
 void launch_deskew_imu_gated(const DeskewPlan& p, const DeskewGate& gate, hipStream_t s);
 void launch_deskew_cv(const DeskewPlan& p, const CvArgH& a, hipStream_t s);
+// The de-skew behind k_imu_propagate (lii_imu.hip): end pose + extrinsic (the first 24 doubles of the propagated state: IekfCtrl::st),
+// the number of poses and the table itself are read from DEVICE memory - none of them has visited the host.
+void launch_deskew_imu_dev(const DeskewPlan& p, const double* pose24_dev, const int* n_poses_dev, const double* poses_dev, hipStream_t s);
+// IMU forward propagation (lii_imu.hip).  The carry of ImuProcess between two scans: last_imu_ (t, gyr, acc), acc_s_last, angvel_last,
+// last_lidar_end_time_, one spare word - 15 + 1 doubles, in one buffer and out another (both workgroups of the launch read the old one).
+constexpr int kImuCarryDoubles = 16;
+struct ImuPropArgs {
+  const double* st_in;      // lii_state as the previous update left it (pinned host memory, or device memory)
+  const double* samples;    // n_imu x (t, gyr[3], acc[3]) (pinned host memory, or device memory)
+  int n_imu;                // 1 .. 63
+  double noise[19];         // cov_gyr, cov_acc, cov_bias_gyr, cov_bias_acc, cov_R_LI, cov_T_LI, mean_acc_norm (lii_imu_noise)
+  double pcl_beg_time, pcl_end_time;
+  const float4* scan;       // != nullptr: pcl_end_time = pcl_beg_time + (the scan's last time stamp) / 1000 instead of the argument
+  int n_scan, sorted;       // sorted: the last point carries it; else extent[1] (k_time_extent)
+  const unsigned long long* extent;
+  const double* carry_in;
+  double* carry_out;
+  double* poses;            // IMUpose table, lii_pose6d records
+  int* n_poses;
+  double* st_out;           // the propagated lii_state (612 doubles)
+  double* prop_out;         // optional: its first 36 doubles once more (IekfCtrl::prop)
+  double* host_out;         // optional, mapped host memory: state (612) | carry (15) | number of poses
+  const uint4* ctrl_src;    // ctrl_vec > 0: 16-byte words [ctrl_from, ctrl_vec) of the update's control block are pulled along
+  uint4* ctrl_dst;
+  int ctrl_from, ctrl_vec;
+};
+struct CvPropArgs {
+  const double* st_in;
+  double dt;
+  double cov_gyr_scale[3], cov_acc_scale[3];
+  double* st_out;
+  double* host_out;         // optional, mapped host memory
+};
+void launch_imu_propagate(const ImuPropArgs& a, hipStream_t s);
+void launch_cv_propagate(const CvPropArgs& a, hipStream_t s);
 // calibration
 void launch_calib_eval(int stage, const double* imu, const double* lidar, int n, const double* params, double* out,
                        hipStream_t s);

@@ -79,35 +79,7 @@ __global__ __launch_bounds__(256) void k_time_extent(const float4* __restrict__ 
     atomicMax(&extent[1], mx);
   }
 }
-__device__ __forceinline__ float ord2f(unsigned int o) {
-  unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-  return __uint_as_float(u);
-}
-
-// Exp(ang_vel, dt) — include/so3_math.h:37-59 — applied to a vector: R v with Rodrigues, R built explicitly
-__device__ __forceinline__ void exp_so3(const double w[3], double dt, double R[9]) {
-  double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  if (n > 0.0000001) {
-    double ax = w[0] / n, ay = w[1] / n, az = w[2] / n;
-    double ang = n * dt;
-    double s = sin(ang), c1 = 1.0 - cos(ang);
-    // K = skew(axis).  The reference writes `(1.0 - cos) * K * K`, which C++ evaluates as ((1 - cos) K) K: the scalar is
-    // rounded into K before the product (so3_math.h:48-53; pinned by tests/test_oracle_math_pinned.py)
-    double K[9] = {0, -az, ay, az, 0, -ax, -ay, ax, 0};
-    double cK[9], KK[9];
-#pragma unroll
-    for (int e = 0; e < 9; e++) cK[e] = c1 * K[e];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) KK[3 * r + c] = cK[3 * r] * K[c] + cK[3 * r + 1] * K[3 + c] + cK[3 * r + 2] * K[6 + c];
-#pragma unroll
-    for (int e = 0; e < 9; e++) R[e] = ((e % 4 == 0) ? 1.0 : 0.0) + s * K[e] + KK[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 9; e++) R[e] = (e % 4 == 0) ? 1.0 : 0.0;
-  }
-}
+// (ord2f and exp_so3 - Exp(ang_vel, dt), include/so3_math.h:37-59 - live in lii_device.h: lii_imu.hip shares them)
 struct UndistArg {
   double endR[9], endp[3], RLI[9], TLI[3];
 };
@@ -363,6 +335,18 @@ __global__ __launch_bounds__(256) void k_deskew_imu(DeskewIo io, UndistArg u, in
   const bool in_range = i < io.n;
   float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
   deskew_imu_point<FUSE>(io, u, K, poses, (int)blockIdx.x, i, in_range, P);
+}
+// The form behind k_imu_propagate (lii_imu.hip; lii_scan_register_imu): end pose, extrinsic, number of poses and the table come from
+// device memory, where that launch left them (u_g: the first 24 doubles of the propagated state).
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_deskew_imu_dev(DeskewIo io, const UndistArg* __restrict__ u_g, const int* __restrict__ k_g, const double* __restrict__ poses_g) {
+  gap_trace(io);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in_range = i < io.n;
+  float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
+  const UndistArg u = *u_g;
+  const int K = *k_g;
+  deskew_imu_point<FUSE>(io, u, K, poses_g, (int)blockIdx.x, i, in_range, P);
 }
 template <bool FUSE>
 __device__ __forceinline__ void deskew_imu_point(const DeskewIo& io, const UndistArg& u, int K, const double* __restrict__ poses, int row, int i, bool in_range,
@@ -947,6 +931,15 @@ void launch_deskew_imu(const DeskewPlan& p, const double* poses_host, const doub
     else if (kp == 64) launch_deskew_imu_t<false, 64>(io, u, K, poses_host, poses_dev, nb, s);
     else launch_deskew_imu_t<false, 0>(io, u, K, poses_host, poses_dev, nb, s);
   }
+}
+void launch_deskew_imu_dev(const DeskewPlan& p, const double* pose24_dev, const int* n_poses_dev, const double* poses_dev, hipStream_t s) {
+  if (p.n <= 0) return;
+  DeskewIo io = deskew_io(p);
+  io.ctrl_vec = 0;  // (k_imu_propagate has pulled the control block)
+  const int nb = nblk(p.n, 256);
+  const UndistArg* u = reinterpret_cast<const UndistArg*>(pose24_dev);
+  if (p.vh) hipLaunchKernelGGL(k_deskew_imu_dev<true>, dim3(nb), dim3(256), 0, s, io, u, n_poses_dev, poses_dev);
+  else hipLaunchKernelGGL(k_deskew_imu_dev<false>, dim3(nb), dim3(256), 0, s, io, u, n_poses_dev, poses_dev);
 }
 void launch_deskew_imu_gated(const DeskewPlan& p, const DeskewGate& gate, hipStream_t s) {
   if (p.n <= 0) return;
