@@ -176,7 +176,8 @@ struct lii_replay {
   double imu_mean_acc_norm = kG;
   std::vector<lii_pose6d> imu_pose;
   std::vector<double> log;  // LII_REPLAY_ROW doubles per processed scan
-  bool device_imu = false;  // lii_replay_set_device_imu: ImuProcess::Process' propagation through lii_scan_register_imu / lii_cv_propagate
+  bool device_imu = false;  // lii_replay_set_device_imu: ImuProcess::Process' propagation through lii_scan_register_imu / lii_scan_register_cv
+  int32_t device_calls[4] = {0, 0, 0, 0};  // lii_replay_device_calls: lii_scan_register_imu, lii_scan_register_cv, lii_cv_propagate, lii_map_build_from_scan
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -224,7 +225,9 @@ void lii_replay_destroy(lii_replay* r) {
 const char* lii_replay_last_error(lii_replay* r) { return r ? r->err.c_str() : "null handle"; }
 lii_handle lii_replay_handle(lii_replay* r) { return r ? r->h : nullptr; }
 // 1: the forward propagation of ImuProcess::Process runs on the device - the LIO branch goes through lii_scan_register_imu (the IMU
-// samples instead of a pose table; the carry lives in the handle), the LO branch's through lii_cv_propagate.  0 (default): the host
+// samples instead of a pose table; the carry lives in the handle), the LO branch through lii_scan_register_cv (the constant-velocity
+// propagation rides in the de-skew launch); the scan that seeds the map goes through lii_cv_propagate + lii_undistort_cv +
+// lii_downsample + lii_map_build_from_scan and stays on the device.  0 (default): the host
 // routines below.
 int lii_replay_set_device_imu(lii_replay* r, int32_t on) {
   if (!r) return LII_ERR_INVALID;
@@ -232,6 +235,12 @@ int lii_replay_set_device_imu(lii_replay* r, int32_t on) {
   return LII_OK;
 }
 
+// out[0 .. 3]: calls made so far to lii_scan_register_imu, lii_scan_register_cv, lii_cv_propagate, lii_map_build_from_scan (all 0 with the switch off)
+int lii_replay_device_calls(lii_replay* r, int32_t out[4]) {
+  if (!r || !out) return LII_ERR_INVALID;
+  std::memcpy(out, r->device_calls, sizeof(r->device_calls));
+  return LII_OK;
+}
 // imu_cbk, src/laserMapping.cpp:395-433
 int lii_replay_imu(lii_replay* r, double stamp, const double gyr[3], const double acc[3]) {
   if (!r || !gyr || !acc) return LII_ERR_INVALID;
@@ -528,7 +537,8 @@ static int process(lii_replay* r) {
   job.opts = r->opts;
   job.opts.imu_en = r->imu_en ? 1 : 0;
   job.scan_sorted = r->prm.cut_frame ? 1 : 0;  // lii_ingest_* hands cut frames over in ascending time order, as process_cut_frame_* does; a whole message keeps the driver's order
-  bool select = true, device_lio = false;
+  bool select = true, device_lio = false, device_lo = false;
+  double dt_cv = 0.0;
   // ---- p_imu->Process(Measures, state, feats_undistort), src/IMU_Processing.hpp:419-462
   if (r->imu_en) {
     if (r->meas_imu.empty()) return LII_OK;
@@ -603,8 +613,12 @@ static int process(lii_replay* r) {
     if (r->b_first_frame) { dt = 0.1; r->b_first_frame = false; }
     else dt = r->lidar_beg_time - r->time_last_scan;
     r->time_last_scan = r->lidar_beg_time;
-    if (r->device_imu) {
+    if (r->device_imu && r->map_built) {
+      device_lo = true;  // (propagation, de-skew and update in one call further down: lii_scan_register_cv)
+      dt_cv = dt;
+    } else if (r->device_imu) {
       const int rc = lii_cv_propagate(r->h, dt, r->cov_gyr, r->cov_acc, &st);
+      r->device_calls[2]++;
       if (rc != LII_OK) return fail(r, rc, std::string("lii_cv_propagate: ") + lii_last_error(r->h));
     } else {
       lii_replay_cv_propagate(&st, dt, r->cov_gyr, r->cov_acc);
@@ -625,7 +639,13 @@ static int process(lii_replay* r) {
     int32_t n_down = 0;
     if (rc == LII_OK) rc = lii_downsample(r->h, r->leaf, &n_down, nullptr);
     if (rc != LII_OK) return fail(r, rc, std::string("first scan: ") + lii_last_error(r->h));
-    if (n_down > 5) {
+    if (r->device_imu && job.undistort == 2) {  // the down-sampled cloud becomes the map where it is
+      int32_t n_map = 0;
+      rc = lii_map_build_from_scan(r->h, &st, &n_map);
+      r->device_calls[3]++;
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_map_build_from_scan: ") + lii_last_error(r->h));
+      if (n_map > 0) r->map_built = true;
+    } else if (n_down > 5) {
       std::vector<float> body(size_t(n_down) * 4), world(size_t(n_down) * 3);
       int32_t n = 0;
       rc = lii_scan_download(r->h, 1, body.data(), n_down, &n);
@@ -657,11 +677,15 @@ static int process(lii_replay* r) {
       std::memcpy(imu[i].acc, r->meas_imu[i].acc, 24);
     }
     rc = lii_scan_register_imu(r->h, &job, imu.data(), int32_t(imu.size()), r->lidar_beg_time, &st, &r->state_propagat, &rep);
+    r->device_calls[0]++;
     r->last_imu = r->meas_imu.back();
+  } else if (device_lo) {
+    rc = lii_scan_register_cv(r->h, &job, dt_cv, r->cov_gyr, r->cov_acc, &st, &r->state_propagat, &rep);
+    r->device_calls[1]++;
   } else {
     rc = lii_scan_register(r->h, &job, &st, &r->state_propagat, &rep);
   }
-  if (rc != LII_OK) return fail(r, rc, std::string(device_lio ? "lii_scan_register_imu (+ map_incremental): " : "lii_scan_register (+ map_incremental): ") + lii_last_error(r->h));
+  if (rc != LII_OK) return fail(r, rc, std::string(device_lio ? "lii_scan_register_imu (+ map_incremental): " : (device_lo ? "lii_scan_register_cv (+ map_incremental): " : "lii_scan_register (+ map_incremental): ")) + lii_last_error(r->h));
   // ---- "Device starts to move, data accumulation begins" (:1151-1155)
   const double pn = std::sqrt(st.pos_end[0] * st.pos_end[0] + st.pos_end[1] * st.pos_end[1] + st.pos_end[2] * st.pos_end[2]);
   if (!r->imu_en && !r->data_accum_start && pn > 0.05) {

@@ -373,7 +373,21 @@ int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, in
  * a singular solve) has still consumed its samples, as Process() has when the update behind it fails; a call refused by the rules above,
  * or whose propagation launch itself fails, leaves the carry as it was.
  * lii_set_profiling(h, 3) attributes the new launch (and, for a scan that is not scan_sorted, the time-extent launch in front of it)
- * to LII_KP_PROPAGATE. */
+ * to LII_KP_PROPAGATE.
+ *   lii_scan_register_cv    Process() with imu_en == false (src/IMU_Processing.hpp:212-266) + the per-scan sequence in ONE call, the LO
+ *                           phase's counterpart of lii_scan_register_imu: propagate -> de-skew -> voxel filter -> iterated update
+ *                           (-> map update), WITHOUT a launch for the propagation - it rides in the CV de-skew launch (k_deskew_cv_prop,
+ *                           lii_scan.hip: every scan workgroup forms rot_end * Exp(bias_g, dt) for itself, one extra workgroup propagates
+ *                           the state and its covariance and writes the update's state / state_propagated in device memory).  `state`
+ *                           in is the state after the PREVIOUS update, NOT propagated; out: the updated state.  dt, cov_gyr_scale,
+ *                           cov_acc_scale as for lii_cv_propagate (:215-221, :234-235).  state_propagated_out (may be NULL): the
+ *                           propagated state, covariance included.  leaf, scan_dev, scan_sorted, map_update, while_waiting mean what
+ *                           they mean to lii_scan_register.
+ * Rules of lii_scan_register_cv: job->undistort != 2, imu_poses != NULL, n_imu_poses != 0, a NULL scale or a dt that is not finite ->
+ * LII_ERR_INVALID; a communicator attached -> LII_ERR_STATE; LII_TEST=host_solve -> LII_ERR_STATE; no scan -> LII_ERR_STATE; no map ->
+ * what lii_scan_register returns.  A refused call leaves `state` as it was.  A pre-armed launch is ended first and job->next_scan_dev is
+ * IGNORED.  lii_set_profiling(h, 3) counts the launch as LII_KP_DESKEW: there is no propagate launch.  Under LII_TEST=no_fast the call is
+ * lii_cv_propagate followed by lii_scan_register's general path - the same device code on the same numbers, the same results. */
 typedef struct lii_imu_sample { double t; double gyr[3]; double acc[3]; } lii_imu_sample; /* 56 bytes */
 typedef struct lii_imu_noise {
   uint32_t struct_size; /* sizeof(lii_imu_noise) */
@@ -395,6 +409,15 @@ int lii_imu_propagate(lii_handle h, const lii_imu_sample* imu, int32_t n_imu, do
 int lii_cv_propagate(lii_handle h, double dt, const double cov_gyr_scale[3], const double cov_acc_scale[3], lii_state* state);
 int lii_scan_register_imu(lii_handle h, const lii_scan_job* job, const lii_imu_sample* imu, int32_t n_imu, double pcl_beg_time,
                           lii_state* state, lii_state* state_propagated_out, lii_iekf_report* report);
+int lii_scan_register_cv(lii_handle h, const lii_scan_job* job, double dt, const double cov_gyr_scale[3], const double cov_acc_scale[3],
+                         lii_state* state, lii_state* state_propagated_out, lii_iekf_report* report);
+
+/* The first scan seeds the map (src/laserMapping.cpp:921-929) on the device: pointBodyToWorld (:209-220) at `state` over the current
+ * down-sampled cloud - feats_down_body, which lii_downsample / lii_downsample_skip must have left (else LII_ERR_STATE) - becomes the map,
+ * and the index is built; nothing visits the host.  *n_map: the points of the new map.  feats_down_size <= 5 (:922): nothing is built,
+ * *n_map = 0, LII_OK - the map the handle had, if any, stays.  More points than max_map_points: LII_ERR_CAPACITY.  Like lii_map_build it
+ * joins a pending map update first and the next pass searches again. */
+int lii_map_build_from_scan(lii_handle h, const lii_state* state, int32_t* n_map);
 
 /* ---------------------------------------------------------------- LI-Init batch calibration evaluators
  * CalibState record (include/LI_init/LI_init.h:31-89). */

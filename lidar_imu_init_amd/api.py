@@ -150,6 +150,9 @@ _DECLS = {
     "lii_cv_propagate": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_scan_register_imu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                         C.POINTER(lii_iekf_report)]),
+    "lii_scan_register_cv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(lii_iekf_report)]),
+    "lii_map_build_from_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_map_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_calib_set_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_calib_eval": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -322,6 +325,14 @@ class Registrar:
     def map_build(self, xyz):
         xyz = np.ascontiguousarray(xyz, np.float32)
         self._check(self.L.lii_map_build(self.h, _ptr(xyz), len(xyz), xyz.strides[0]))
+
+    def map_build_from_scan(self, state: "State") -> int:
+        """The first scan seeds the map (src/laserMapping.cpp:921-929): the current down-sampled cloud, moved to the world frame at
+        `state` on the device, becomes the map (lii_map_build_from_scan).  Returns the number of map points (0: five points or
+        fewer, nothing built)."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_build_from_scan(self.h, _ptr(state.pod), C.byref(n)))
+        return n.value
 
     def map_add_points(self, xyz, downsample_on: bool) -> int:
         xyz = np.ascontiguousarray(xyz, np.float32)
@@ -597,6 +608,38 @@ class Registrar:
         prop = State() if want_propagated else None
         self._check(self.L.lii_scan_register_imu(self.h, C.byref(job), _ptr(imu) if len(imu) else None, len(imu), float(pcl_beg_time),
                                                  _ptr(state.pod), _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
+        return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
+                                 converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+
+    def register_cv(self, dt, cov_gyr_scale, cov_acc_scale, state: State, *, leaf=0.0, max_iterations=4, scan_dev=None, scan_sorted=False,
+                    map_update=False, while_waiting=None, imu_poses=None, want_propagated=True, undistort=2):
+        """Process() with imu_en == false + voxel grid + iterated update in one library call (lii_scan_register_cv): the constant-velocity
+        propagation rides in the de-skew launch.  `state` in is the state after the previous update and is updated in place.  Returns
+        (state, propagated state or None, report dict).  imu_poses must stay None and undistort 2 (the rules' tests pass others)."""
+        cg = None if cov_gyr_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cov_gyr_scale, np.float64), (3,)))
+        ca = None if cov_acc_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cov_acc_scale, np.float64), (3,)))
+        job = lii_scan_job()
+        job.struct_size = C.sizeof(lii_scan_job)
+        job.undistort = int(undistort)
+        job.scan_sorted = 1 if scan_sorted else 0
+        job.map_update = 1 if map_update else 0
+        if scan_dev is not None:
+            job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
+        hook = None
+        if while_waiting is not None:
+            hook = WAIT_HOOK(lambda _arg: while_waiting())
+            job.while_waiting = C.cast(hook, C.c_void_p)
+        poses = None
+        if imu_poses is not None:
+            poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
+            job.imu_poses, job.n_imu_poses = _ptr(poses), len(poses)
+        job.leaf = float(leaf)
+        job.opts = lii_iekf_opts(int(max_iterations), 0)
+        rep = lii_iekf_report()
+        prop = State() if want_propagated else None
+        self._check(self.L.lii_scan_register_cv(self.h, C.byref(job), float(dt), _ptr(cg) if cg is not None else None,
+                                                _ptr(ca) if ca is not None else None, _ptr(state.pod),
+                                                _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
         return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
                                  converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
 

@@ -1,5 +1,5 @@
 // libliinit_hip — IMU processing (host side): lii_imu_noise_defaults / lii_imu_set_noise / lii_imu_set_carry / lii_imu_get_carry,
-// lii_imu_propagate, lii_cv_propagate, lii_scan_register_imu.  Kernels: lii_imu.hip.  Reference: ImuProcess::Process,
+// lii_imu_propagate, lii_cv_propagate, lii_scan_register_imu, lii_scan_register_cv.  Kernels: lii_imu.hip, and k_deskew_cv_prop of lii_scan.hip.  Reference: ImuProcess::Process,
 // src/IMU_Processing.hpp:419-461 (its forward half; the de-skew is lii_undistort_* / k_deskew_*).  The prologue of
 // lii_scan_register_imu lives with the routine it shares with lii_scan_register (lii_capi_register.cpp: imu_prologue).
 #include "lii_context.h"
@@ -159,6 +159,40 @@ int lii_scan_register_imu(lii_handle h, const lii_scan_job* job, const lii_imu_s
   if (h->host_solve) return fail(h, LII_ERR_STATE, "lii_scan_register_imu: not available under LII_TEST=host_solve (the host-driven loop has no device-resident control block)");
   ImuFeed feed = {imu, n_imu, pcl_beg_time, state_propagated_out};
   return scan_register_job(h, job, state, nullptr, report, &feed);
+}
+
+// Process() with imu_en == false (src/IMU_Processing.hpp:212-266) + the per-scan sequence: the propagation rides in the de-skew launch
+int lii_scan_register_cv(lii_handle h, const lii_scan_job* job, double dt, const double cov_gyr_scale[3], const double cov_acc_scale[3], lii_state* state,
+                         lii_state* state_propagated_out, lii_iekf_report* report) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !job || !state || !cov_gyr_scale || !cov_acc_scale) return fail(h, LII_ERR_INVALID, "lii_scan_register_cv: bad arguments");
+  if (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u)
+    return fail(h, LII_ERR_INVALID, "lii_scan_register_cv: bad job size");
+  if (job->undistort != 2 || job->imu_poses != nullptr || job->n_imu_poses != 0)
+    return fail(h, LII_ERR_INVALID, "lii_scan_register_cv: the job must say undistort = 2, imu_poses = NULL, n_imu_poses = 0");
+  if (!std::isfinite(dt)) return fail(h, LII_ERR_INVALID, "lii_scan_register_cv: dt is not finite");
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_scan_register_cv: single rank only for now (a communicator is attached)");
+  if (h->host_solve) return fail(h, LII_ERR_STATE, "lii_scan_register_cv: not available under LII_TEST=host_solve (the host-driven loop has no device-resident control block)");
+  if (h->no_fast_prologue) {
+    // LII_TEST=no_fast: no launch carries anything along - k_cv_propagate, then lii_scan_register's general path (the same device code on the
+    // same numbers: the same results).  A copy is propagated: `state` changes only with a successful update.
+    const bool have_scan = (job->scan_dev != nullptr && job->n_scan_dev > 0) || h->n_scan > 0 || lii_internal_scan_is_deferred(h);
+    if (!have_scan) return fail(h, LII_ERR_STATE, "lii_scan_register_cv: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
+    std::vector<lii_state> st(2, *state);
+    int rc = lii_cv_propagate(h, dt, cov_gyr_scale, cov_acc_scale, &st[0]);
+    if (rc != LII_OK) return rc;
+    st[1] = st[0];
+    lii_scan_job plain = {};
+    std::memcpy(&plain, job, job->struct_size);
+    if (plain.struct_size >= 72u) { plain.next_scan_dev = nullptr; plain.next_n_scan = 0; }
+    rc = scan_register_job(h, &plain, &st[1], &st[0], report, nullptr);
+    if (rc != LII_OK) return rc;
+    *state = st[1];
+    if (state_propagated_out) *state_propagated_out = st[0];
+    return LII_OK;
+  }
+  CvFeed cv = {dt, cov_gyr_scale, cov_acc_scale, state_propagated_out};
+  return scan_register_job(h, job, state, nullptr, report, nullptr, &cv);
 }
 
 }  // extern "C"

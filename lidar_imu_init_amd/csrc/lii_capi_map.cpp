@@ -455,6 +455,28 @@ int lii_map_build(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return LII_OK;
 }
+// src/laserMapping.cpp:921-929: the first scan's down-sampled cloud becomes the map, without leaving the device
+int lii_map_build_from_scan(lii_handle h, const lii_state* state, int32_t* n_map) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !state || !n_map) return fail(h, LII_ERR_INVALID, "lii_map_build_from_scan: bad arguments");
+  int rc = resolve_n_body(h);
+  if (rc != LII_OK) return rc;
+  const int n = h->n_body;
+  if (n <= 0) return fail(h, LII_ERR_STATE, "lii_map_build_from_scan: no down-sampled scan (call lii_downsample / lii_downsample_skip)");
+  *n_map = 0;
+  if (n <= 5) return LII_OK;  // `if (feats_down_size > 5)`, :922 - the next scan tries again
+  if (n > h->cfg.max_map_points) return fail(h, LII_ERR_CAPACITY, "lii_map_build_from_scan: the down-sampled scan holds more than max_map_points");
+  rc = map_join(h);
+  if (rc != LII_OK) return rc;
+  h->have_search = false;
+  launch_body_to_map(h->d_body, n, pose_of(*state), h->d_map_unsorted, h->stream);
+  HIPCHK(h, hipGetLastError());
+  rc = build_index(h, n);
+  if (rc != LII_OK) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *n_map = n;
+  return LII_OK;
+}
 int lii_map_add_points(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t downsample_on, int32_t* n_added) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   if (!h || (!xyz && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4) return fail(h, LII_ERR_INVALID, "lii_map_add_points: bad arguments");

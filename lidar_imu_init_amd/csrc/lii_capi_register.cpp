@@ -437,16 +437,72 @@ int imu_prologue(lii_handle h, const lii_scan_job* job, const ImuFeed* feed, con
   return LII_OK;
 }
 
+// The prologue of lii_scan_register_cv: ONE launch, the CV de-skew whose extra workgroup propagates (k_deskew_cv_prop).  The host hands
+// over the state the previous update left - inside the control block in pinned memory for the extra workgroup, rot_end / bias_g /
+// vel_end by value for the scan workgroups - and never sees the propagated one unless it asks for it.
+int cv_prologue(lii_handle h, const lii_scan_job* job, const CvFeed* cv, const lii_state* state, bool adopt, const float4* src_dev, int n_next, bool sorted) {
+  if (n_next <= 0) return fail(h, LII_ERR_STATE, "lii_scan_register_cv: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
+  int rc = LII_OK;
+  if (cv->prop_out) { rc = imu_buffers(h); if (rc != LII_OK) return rc; }
+  if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
+  h->staging_busy = true;
+  fill_ctrl(h, state, state, &job->opts);  // (st / prop of the block on the device are written by the extra workgroup, not pulled; st is what it reads)
+  extent_discard(h);
+  h->n_scan = n_next;
+  h->n_body = 0;
+  h->n_body_pending = false;
+  h->have_search = false;
+  const float fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
+  h->vh_inserted = fuse_filter(h, fuse_leaf);
+  if (h->vh_inserted) h->vh_inserted_leaf = fuse_leaf;
+  const float4* in = adopt ? src_dev : h->d_scan.get();
+  const unsigned long long* ext = nullptr;
+  if (!sorted) {  // a scan in any order: the time-extent reduction in front (adopting the scan on the way), as on lii_scan_register's general path
+    unsigned long long* e = h->d_extent + 2 * h->extent_sel;
+    launch_time_extent(in, n_next, e, h->d_extent + 2 * (h->extent_sel ^ 1), adopt ? h->d_scan.get() : nullptr, nullptr, nullptr, 0, h->stream);
+    h->extent_sel ^= 1;
+    ext = e;
+    in = h->d_scan;
+  }
+  DeskewPlan dp = {};
+  dp.in = in; dp.out = h->d_scan; dp.n = n_next; dp.sorted = sorted ? 1 : 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
+  dp.leaf = fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
+  dp.ctrl_src = h->h_ctrl; dp.ctrl_dst = h->d_ctrl; dp.ctrl_bytes = (sizeof(IekfCtrl) + 15) / 16 * 16;
+#ifdef LII_GAP_TRACE
+  dp.gap = h->d_gran;
+#endif
+  CvFuseH f = {};
+  std::memcpy(f.rot, state->rot_end, 72);
+  std::memcpy(f.bias_g, state->bias_g, 24);
+  std::memcpy(f.vel, state->vel_end, 24);
+  f.dt = cv->dt;
+  std::memcpy(f.cov_gyr_scale, cv->cov_gyr_scale, 24);
+  std::memcpy(f.cov_acc_scale, cv->cov_acc_scale, 24);
+  f.st_in = h->h_ctrl->st;
+  f.st_out = h->d_ctrl->st;
+  f.prop_out = h->d_ctrl->prop;
+  f.host_out = cv->prop_out ? h->imu.h_out.get() : nullptr;
+  static_assert(offsetof(IekfCtrl, solution) % 16 == 0 && offsetof(IekfCtrl, prop) + sizeof(IekfCtrl::prop) == offsetof(IekfCtrl, solution), "IekfCtrl: the two states come first");
+  f.ctrl_from = int(offsetof(IekfCtrl, solution) / 16);
+  launch_deskew_cv_prop(dp, f, h->stream);
+  h->bbox_rows = (n_next + 255) / 256;
+  h->ctrl_preloaded = true;
+  const hipError_t e_launch = hipGetLastError();
+  if (e_launch != hipSuccess) { h->vh_inserted = false; h->ctrl_preloaded = false; return fail(h, LII_ERR_HIP, std::string("de-skew launch with the CV propagation: ") + hipGetErrorString(e_launch)); }
+  return LII_OK;
+}
+
 }  // namespace
 
-// lii_scan_register, and - feed != nullptr - lii_scan_register_imu (lii_capi_imu.cpp: its checks are made there; state_prop is not used)
+// lii_scan_register, and - feed != nullptr - lii_scan_register_imu, - cv != nullptr - lii_scan_register_cv (lii_capi_imu.cpp: their checks
+// are made there; state_prop is not used)
 int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report,
-                                const ImuFeed* feed) {
-  const char* const who = feed ? "lii_scan_register_imu" : "lii_scan_register";
+                                const ImuFeed* feed, const CvFeed* cv) {
+  const char* const who = feed ? "lii_scan_register_imu" : (cv ? "lii_scan_register_cv" : "lii_scan_register");
   // (struct_size 48: a job of ABI 5, without scan_sorted)
   // (struct_size 88: ABI 9; 72: ABI 8, without while_waiting; 56: ABI 6 - 7, without next_scan_dev; 48: ABI 5, without scan_sorted)
   static_assert(sizeof(lii_scan_job) == 88, "lii_scan_job: the sizes of the earlier ABIs are accepted by number");
-  if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || (!state_prop && !feed) || job->opts.max_iterations < 1)
+  if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || (!state_prop && !feed && !cv) || job->opts.max_iterations < 1)
     return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
   const bool sorted = job->struct_size >= 56u && job->scan_sorted == 1;
   h->scan_buf_idle = false;
@@ -470,14 +526,14 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   bool use_pre = h->pre.armed && sorted && job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= lii::kGateMaxPoses &&
                  cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && leaf_now == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
                  h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, leaf_now) == h->pre.fuse;
-  if (feed) use_pre = false;  // (lii_scan_register_imu: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
+  if (feed || cv) use_pre = false;  // (lii_scan_register_imu / _cv: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
   if (!use_pre) prearm_cancel(h);
   // ... and what this job announces for the next call (update_on_device arms it behind the passes)
   h->pre.want_dev = nullptr;
-  if (!feed && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
+  if (!feed && !cv && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
       sorted && job->undistort == 1) {
     h->pre.want_dev = job->next_scan_dev; h->pre.want_n = job->next_n_scan; h->pre.want_leaf = leaf_now; h->pre.want_late = false;
-  } else if (!feed && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
+  } else if (!feed && !cv && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
     // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
     h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = leaf_now; h->pre.want_late = true;
   }
@@ -495,6 +551,9 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   const auto t_first = std::chrono::steady_clock::now();
   if (feed) {
     rc = imu_prologue(h, job, feed, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
+    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
+  } else if (cv) {
+    rc = cv_prologue(h, job, cv, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
     if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
   } else if (fast) {
     if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
@@ -646,6 +705,8 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   }
   // lii_scan_register_imu: the propagated state, as k_imu_propagate left it in mapped host memory (it ran in front of the passes whose result has arrived)
   if (rc == LII_OK && feed && feed->prop_out) std::memcpy(feed->prop_out, h->imu.h_out.get(), sizeof(lii_state));
+  // lii_scan_register_cv: likewise, as the extra workgroup of k_deskew_cv_prop left it
+  if (rc == LII_OK && cv && cv->prop_out) std::memcpy(cv->prop_out, h->imu.h_out.get(), sizeof(lii_state));
   return rc;
 }
 

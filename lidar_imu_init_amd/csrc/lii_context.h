@@ -4,7 +4,7 @@
 //   lii_capi_register.cpp  the registration loop: lii_iekf_*, lii_scan_register, neighbour download
 //   lii_capi_comm.cpp      the communicator of a sharded job (node-local mailbox / RCCL)
 //   lii_capi_calib.cpp     the LI_init evaluators' entry points
-//   lii_capi_imu.cpp       IMU forward propagation: lii_imu_*, lii_cv_propagate, lii_scan_register_imu
+//   lii_capi_imu.cpp       IMU forward propagation: lii_imu_*, lii_cv_propagate, lii_scan_register_imu, lii_scan_register_cv
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -352,7 +352,15 @@ struct ImuFeed {
   double pcl_beg_time;
   lii_state* prop_out;  // may be nullptr
 };
-int scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report, const ImuFeed* feed);
+// ... and lii_scan_register_cv with what the constant-velocity propagation of the LO phase needs
+struct CvFeed {
+  double dt;
+  const double* cov_gyr_scale;  // [3]
+  const double* cov_acc_scale;  // [3]
+  lii_state* prop_out;          // may be nullptr
+};
+int scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report, const ImuFeed* feed,
+                      const CvFeed* cv = nullptr);
 int imu_buffers(lii_handle h);  // creates lii_context::imu's buffers on first use
 // lii_capi_comm.cpp
 void comm_drop(lii_handle h);

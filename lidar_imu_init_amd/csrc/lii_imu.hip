@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "lii_device.h"
+#include "lii_imu_dev.h"
 #include "lii_launch.h"
 
 namespace lii {
@@ -74,55 +75,6 @@ __device__ __forceinline__ void fill_steps(StepTab& tb, const double* __restrict
   }
 }
 
-// sum_k F[r][k] M[k] over the non-zero entries of row r of F_x, in ascending k (M[k] = Mb[k * sk]):
-//   rows 0-2    E (cols 0-2), a15 I (cols 15-17)                          :338-339 / :229-230
-//   rows 3-5    I, dt I (cols 12-14)                                      :340 / :231
-//   rows 12-14  B (cols 0-2), I, Cm (cols 18-20), dt I (cols 21-23)       :341-343   (B == nullptr: the CV model has no such rows)
-__device__ __forceinline__ double f_row(int r, const double* __restrict__ Mb, int sk, const double* __restrict__ E, double a15, double dt,
-                                        const double* __restrict__ B, const double* __restrict__ Cm) {
-  if (r < 3) return E[3 * r] * Mb[0] + E[3 * r + 1] * Mb[sk] + E[3 * r + 2] * Mb[2 * sk] + a15 * Mb[(15 + r) * sk];
-  if (r < 6) return Mb[r * sk] + dt * Mb[(r + 9) * sk];
-  if (B && r >= 12 && r < 15) {
-    const int i = r - 12;
-    double s = B[3 * i] * Mb[0] + B[3 * i + 1] * Mb[sk] + B[3 * i + 2] * Mb[2 * sk];
-    s += Mb[r * sk];
-    s += Cm[3 * i] * Mb[18 * sk];
-    s += Cm[3 * i + 1] * Mb[19 * sk];
-    s += Cm[3 * i + 2] * Mb[20 * sk];
-    s += dt * Mb[(21 + i) * sk];
-    return s;
-  }
-  return Mb[r * sk];
-}
-// P <- F P F^T + Q (:352 / :238), P and T in LDS, every lane of a 256-lane workgroup calls it.  qd: the diagonal of cov_w; Qa: its
-// (12,12) block when that block is full (:348), else nullptr.
-__device__ __forceinline__ void cov_step(double* __restrict__ P, double* __restrict__ T, const double* __restrict__ E, double a15, double dt,
-                                         const double* __restrict__ B, const double* __restrict__ Cm, const double* __restrict__ qd,
-                                         const double* __restrict__ Qa) {
-  for (int e = threadIdx.x; e < 576; e += 256) {  // T = F P
-    const int r = e / 24, c = e - 24 * r;
-    T[e] = f_row(r, P + c, 24, E, a15, dt, B, Cm);
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 576; e += 256) {  // P = T F^T + Q:  (T F^T)[r][c] = sum_k F[c][k] T[r][k]
-    const int r = e / 24, c = e - 24 * r;
-    double q = r == c ? qd[r] : 0.0;
-    if (Qa && r >= 12 && r < 15 && c >= 12 && c < 15) q = Qa[3 * (r - 12) + (c - 12)];
-    P[e] = f_row(c, T + 24 * r, 1, E, a15, dt, B, Cm) + q;
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ void pull_words(const uint4* __restrict__ src, uint4* __restrict__ dst, int from, int to, int lane, int lanes) {
-  for (int i0 = from + lane; i0 < to; i0 += lanes * 4) {  // four PCIe reads in flight per lane
-    uint4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) v[u] = i0 + lanes * u < to ? src[i0 + lanes * u] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-      if (i0 + lanes * u < to) dst[i0 + lanes * u] = v[u];
-  }
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_imu_propagate(ImuPropArgs io) {
@@ -300,40 +252,17 @@ __global__ __launch_bounds__(256) void k_imu_propagate(ImuPropArgs io) {
   }
 }
 
-// Forward_propagation_without_imu, src/IMU_Processing.hpp:212-244, without its de-skew (k_deskew_cv): one workgroup.
+// Forward_propagation_without_imu, src/IMU_Processing.hpp:212-244, without its de-skew (k_deskew_cv): one workgroup.  The arithmetic
+// is cv_propagate_lds (lii_imu_dev.h), which the extra workgroup of k_deskew_cv_prop (lii_scan.hip) runs as well.
 __global__ __launch_bounds__(256) void k_cv_propagate(CvPropArgs io) {
-  __shared__ double s_x[36], s_P[576], s_T[576], s_E[18], s_qd[24];
+  __shared__ CvPropLds L;
   const int tid = threadIdx.x;
-  if (tid < 36) s_x[tid] = io.st_in[tid];
-  for (int e = tid; e < 576; e += 256) s_P[e] = io.st_in[36 + e];
+  if (tid < 36) L.x[tid] = io.st_in[tid];
+  for (int e = tid; e < 576; e += 256) L.P[e] = io.st_in[36 + e];
   __syncthreads();
-  const double dt = io.dt;
-  if (tid < 2) {  // Exp(bias_g, dt) and Exp(bias_g, -dt): in the CV model bias_g is the angular velocity (:226-229)
-    double E[9];
-    exp_so3(s_x + 27, tid == 0 ? dt : -dt, E);
-#pragma unroll
-    for (int e = 0; e < 9; e++) s_E[9 * tid + e] = E[e];
-  }
-  if (tid >= 64 && tid < 64 + 24) {  // :234-235
-    const int r = tid - 64;
-    double q = 0.0;
-    if (r >= 15 && r < 18) q = io.cov_gyr_scale[r - 15] * dt * dt;
-    else if (r >= 12 && r < 15) q = io.cov_acc_scale[r - 12] * dt * dt;
-    s_qd[r] = q;
-  }
-  __syncthreads();
-  cov_step(s_P, s_T, s_E + 9, dt, dt, nullptr, nullptr, s_qd, nullptr);
-  if (tid == 0) {
-    double Rn[9];
-    mat3_mul(s_x, s_E, Rn);  // :241
-#pragma unroll
-    for (int e = 0; e < 9; e++) s_x[e] = Rn[e];
-#pragma unroll
-    for (int c = 0; c < 3; c++) s_x[9 + c] += s_x[24 + c] * dt;  // :244
-  }
-  __syncthreads();
-  if (tid < 36) { io.st_out[tid] = s_x[tid]; if (io.host_out) io.host_out[tid] = s_x[tid]; }
-  for (int e = tid; e < 576; e += 256) { io.st_out[36 + e] = s_P[e]; if (io.host_out) io.host_out[36 + e] = s_P[e]; }
+  cv_propagate_lds(L, io.dt, io.cov_gyr_scale, io.cov_acc_scale);
+  if (tid < 36) { io.st_out[tid] = L.x[tid]; if (io.host_out) io.host_out[tid] = L.x[tid]; }
+  for (int e = tid; e < 576; e += 256) { io.st_out[36 + e] = L.P[e]; if (io.host_out) io.host_out[36 + e] = L.P[e]; }
 }
 
 void launch_imu_propagate(const ImuPropArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_imu_propagate, dim3(2), dim3(256), 0, s, a); }

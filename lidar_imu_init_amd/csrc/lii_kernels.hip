@@ -539,6 +539,14 @@ __device__ __forceinline__ void body_to_world(const PoseArg& ps, const float4 pb
   wy = (float)(ps.R[3] * ix + ps.R[4] * iy + ps.R[5] * iz + ps.p[1]);
   wz = (float)(ps.R[6] * ix + ps.R[7] * iy + ps.R[8] * iz + ps.p[2]);
 }
+// The first scan seeds the map (src/laserMapping.cpp:921-929): the down-sampled cloud in the world frame, as map points (w = 0)
+__global__ __launch_bounds__(256) void k_body_to_map(const float4* __restrict__ body, int n, PoseArg ps, float4* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float wx, wy, wz;
+  body_to_world(ps, body[i], wx, wy, wz);
+  dst[i] = make_float4(wx, wy, wz, 0.f);
+}
 
 // Where a query sits in the grid: its cell, the nearer-side neighbour on every axis, the radius round 1 covers (g0) and the
 // radius the whole 3x3x3 block covers (guard).
@@ -2007,6 +2015,10 @@ static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 
 void launch_map_keys(const float4* pts, int n, float inv_cs, unsigned long long* keys, unsigned int* idx, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_map_keys, dim3(nblk(n, 256)), dim3(256), 0, s, pts, n, inv_cs, keys, idx);
+}
+void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_body_to_map, dim3(nblk(n, 256)), dim3(256), 0, s, body, n, ps, dst);
 }
 void launch_map_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_map_gather, dim3(nblk(n, 256)), dim3(256), 0, s, src, idx, n, dst);

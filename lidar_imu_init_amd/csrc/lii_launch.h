@@ -34,6 +34,7 @@ struct CvArgH { double omega[3], vel[3], endR[9]; };
 // map index
 void launch_map_keys(const float4* pts, int n, float inv_cs, unsigned long long* keys, unsigned int* idx, hipStream_t s);
 void launch_map_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
+void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s);  // pointBodyToWorld over a cloud: dst[i] = (world xyz, 0)
 void launch_block_flags(const unsigned long long* keys, int n, unsigned int* flags, hipStream_t s);
 void launch_table_clear(BlockEntry* blocks, unsigned int cap, hipStream_t s);
 void launch_win_bbox(const BlockEntry* blocks, unsigned int cap, unsigned int* box, hipStream_t s);
@@ -168,6 +169,21 @@ struct DeskewGate {
 };
 void launch_deskew_imu_gated(const DeskewPlan& p, const DeskewGate& gate, hipStream_t s);
 void launch_deskew_cv(const DeskewPlan& p, const CvArgH& a, hipStream_t s);
+// The CV de-skew that propagates as well (k_deskew_cv_prop; lii_scan_register_cv): the scan's workgroups plus one, which runs
+// k_cv_propagate's arithmetic on the state in pinned host memory (st_in), writes the propagated state to st_out (612 doubles) /
+// prop_out (36) / host_out (612, optional, mapped host memory) and pulls the 16-byte words [ctrl_from, p.ctrl_bytes / 16) of the
+// control block.  rot / bias_g / vel: rot_end, bias_g, vel_end of the UNPROPAGATED state, for the scan workgroups.
+struct CvFuseH {
+  double rot[9], bias_g[3], vel[3];
+  double dt;
+  double cov_gyr_scale[3], cov_acc_scale[3];
+  const double* st_in;
+  double* st_out;
+  double* prop_out;
+  double* host_out;
+  int ctrl_from;
+};
+void launch_deskew_cv_prop(const DeskewPlan& p, const CvFuseH& f, hipStream_t s);
 // The de-skew behind k_imu_propagate (lii_imu.hip): end pose + extrinsic (the first 24 doubles of the propagated state: IekfCtrl::st),
 // the number of poses and the table itself are read from DEVICE memory - none of them has visited the host.
 void launch_deskew_imu_dev(const DeskewPlan& p, const double* pose24_dev, const int* n_poses_dev, const double* poses_dev, hipStream_t s);

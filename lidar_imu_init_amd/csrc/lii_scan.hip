@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "lii_device.h"
+#include "lii_imu_dev.h"
 #include "lii_launch.h"
 
 namespace lii {
@@ -479,11 +480,10 @@ __global__ __launch_bounds__(256) void k_deskew_imu_gated(DeskewIo io, DeskewGat
 struct CvArg {
   double omega[3], vel[3], endR[9];
 };
-// CV-mode de-skew (src/IMU_Processing.hpp:246-266).  The time-earliest point is skipped (quirk A3).
+// CV-mode de-skew (src/IMU_Processing.hpp:246-266).  The time-earliest point is skipped (quirk A3).  What a scan workgroup does,
+// shared by the two kernels below.
 template <bool FUSE>
-__global__ __launch_bounds__(256) void k_deskew_cv(DeskewIo io, CvArg a) {
-  const int n_scan_blocks = gridDim.x - (io.ctrl_vec > 0 ? 1 : 0);
-  if ((int)blockIdx.x == n_scan_blocks) { pull_ctrl(io); return; }
+__device__ __forceinline__ void deskew_cv_point(const DeskewIo& io, const double (&omega)[3], const double (&rv)[3] /* endR^T vel */) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = i < io.n;
   float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
@@ -495,9 +495,7 @@ __global__ __launch_bounds__(256) void k_deskew_cv(DeskewIo io, CvArg a) {
       double end_off = t_end / double(1000);
       double dt_j = end_off - P.w / double(1000);
       double R[9];
-      exp_so3(a.omega, -dt_j, R);
-      double rv[3];
-      mat3t_vec(a.endR, a.vel, rv);
+      exp_so3(omega, -dt_j, R);
       double p[3] = {P.x, P.y, P.z}, o[3];
       mat3_vec(R, p, o);
 #pragma unroll
@@ -510,6 +508,71 @@ __global__ __launch_bounds__(256) void k_deskew_cv(DeskewIo io, CvArg a) {
   }
   deskew_bbox(P, in_range, io.bbox_rows);
   if (FUSE && in_range) vhash_insert_abs(P, i, io.leaf, io.tb);
+}
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_deskew_cv(DeskewIo io, CvArg a) {
+  const int n_scan_blocks = gridDim.x - (io.ctrl_vec > 0 ? 1 : 0);
+  if ((int)blockIdx.x == n_scan_blocks) { pull_ctrl(io); return; }
+  double rv[3];
+  mat3t_vec(a.endR, a.vel, rv);
+  deskew_cv_point<FUSE>(io, a.omega, rv);
+}
+
+// The CV de-skew that carries the propagation of the LO phase (lii_scan_register_cv): Process() with imu_en == false,
+// src/IMU_Processing.hpp:212-266, in ONE launch.  The arguments hold the state as the previous update left it - not propagated.
+//   scan workgroups  form the propagated end rotation themselves, rot_end * Exp(bias_g, dt) (:228, :241) - everything they need
+//                    arrives by value, so they wait for nothing - and go on as k_deskew_cv does;
+//   extra workgroup  the whole propagation (cv_propagate_lds, the arithmetic of k_cv_propagate: the one cov_step over P in LDS, then
+//                    rotation and position).  The state comes out of the control block in pinned host memory (fill_ctrl); the
+//                    propagated state goes to IekfCtrl::st and ::prop on the device - and to mapped host memory if asked - and the
+//                    words of the block behind the two states are pulled over beside it.
+// Its st[0..8] and the scan workgroups' end rotation are the same instructions on the same numbers: the same bits.
+struct CvFuseArg {
+  double rot[9], bias_g[3], vel[3];  // rot_end, bias_g, vel_end of the unpropagated state
+  double dt;
+  double cov_gyr_scale[3], cov_acc_scale[3];
+  const double* st_in;   // the whole lii_state (pinned host memory)
+  double* st_out;        // IekfCtrl::st (612 doubles)
+  double* prop_out;      // IekfCtrl::prop (36 doubles)
+  double* host_out;      // optional, mapped host memory (612 doubles)
+  int ctrl_from;         // first 16-byte word of the control block behind the two states
+};
+__device__ __forceinline__ void cv_extra_workgroup(const DeskewIo& io, const CvFuseArg& f) {
+  __shared__ CvPropLds L;
+  const int tid = threadIdx.x;
+  // (both PCIe reads under way together: the state's 612 doubles and the rest of the block)
+  const double x = tid < 36 ? f.st_in[tid] : 0.0;
+  const double p0 = f.st_in[36 + tid], p1 = f.st_in[36 + 256 + tid], p2 = tid < 64 ? f.st_in[36 + 512 + tid] : 0.0;
+  if (io.ctrl_vec > f.ctrl_from) pull_words(io.ctrl_src, io.ctrl_dst, f.ctrl_from, io.ctrl_vec, tid, 256);
+  if (tid < 36) L.x[tid] = x;
+  L.P[tid] = p0;
+  L.P[256 + tid] = p1;
+  if (tid < 64) L.P[512 + tid] = p2;
+  __syncthreads();
+  cv_propagate_lds(L, f.dt, f.cov_gyr_scale, f.cov_acc_scale);
+  if (tid < 36) {
+    f.st_out[tid] = L.x[tid];
+    f.prop_out[tid] = L.x[tid];
+    if (f.host_out) f.host_out[tid] = L.x[tid];
+  }
+  for (int e = tid; e < 576; e += 256) {
+    f.st_out[36 + e] = L.P[e];
+    if (f.host_out) f.host_out[36 + e] = L.P[e];
+  }
+}
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_deskew_cv_prop(DeskewIo io, CvFuseArg f) {
+  if ((int)blockIdx.x == (int)gridDim.x - 1) { cv_extra_workgroup(io, f); return; }  // (always there: the grid is the scan's workgroups + 1)
+  double endR[9], rv[3];
+  cv_end_rotation(f.rot, f.bias_g, f.dt, endR);
+  mat3t_vec(endR, f.vel, rv);  // (the nine doubles of the rotation end here: three stay live over the per-point code)
+#pragma unroll
+  for (int c = 0; c < 3; c++) {  // (the same in every lane: held in scalar registers, the kernel stays at k_deskew_cv's 50 VGPRs - 68 with them in vector registers)
+    const long long b = __double_as_longlong(rv[c]);
+    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
+    rv[c] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+  }
+  deskew_cv_point<FUSE>(io, f.bias_g, rv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -957,6 +1020,16 @@ void launch_deskew_cv(const DeskewPlan& p, const CvArgH& ah, hipStream_t s) {
   const int nb = nblk(p.n, 256) + (io.ctrl_vec > 0 ? 1 : 0);
   if (p.vh) hipLaunchKernelGGL(k_deskew_cv<true>, dim3(nb), dim3(256), 0, s, io, a);
   else hipLaunchKernelGGL(k_deskew_cv<false>, dim3(nb), dim3(256), 0, s, io, a);
+}
+void launch_deskew_cv_prop(const DeskewPlan& p, const CvFuseH& fh, hipStream_t s) {
+  if (p.n <= 0) return;
+  CvFuseArg f;
+  static_assert(sizeof(CvFuseArg) == sizeof(CvFuseH), "layout");
+  memcpy(&f, &fh, sizeof(f));
+  const DeskewIo io = deskew_io(p);
+  const int nb = nblk(p.n, 256) + 1;  // (+ the workgroup that propagates)
+  if (p.vh) hipLaunchKernelGGL(k_deskew_cv_prop<true>, dim3(nb), dim3(256), 0, s, io, f);
+  else hipLaunchKernelGGL(k_deskew_cv_prop<false>, dim3(nb), dim3(256), 0, s, io, f);
 }
 void launch_voxel_hash_clear(const VoxelHashBuffers& vh, size_t slots, hipStream_t s) {
   hipLaunchKernelGGL(k_vh_clear, dim3((unsigned int)((slots + 255) / 256)), dim3(256), 0, s, static_cast<VhSlot*>(vh.slots), (unsigned int)slots);
