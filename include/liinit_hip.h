@@ -142,12 +142,25 @@ int lii_map_commit(lii_handle h);
  *                  the handle has returned).
  * ORDER OF THE POINTS.  The reference sorts every scan by time before it de-skews it (std::sort by curvature,
  *                  src/IMU_Processing.hpp:209, :287; its preprocess hands the scan over sorted as well,
- *                  src/preprocess.cpp:296-302) and everything downstream sees that order.  The library does NOT sort: the
+ *                  src/preprocess.cpp:296-302) and everything downstream sees that order.  The library sorts ONLY WHEN ASKED: the
  *                  de-skew itself does not need it (the time-earliest point is found by a reduction), but the voxel-grid
  *                  centroids are float sums in input order, so results are bit-identical to the reference's only for a
- *                  scan handed over in ascending time order (equal stamps in the reference's order) - which is what
- *                  lii_ingest_* / lii_frame_select deliver.  An unsorted scan is registered correctly up to the rounding of
- *                  those sums (~1e-6 m per centroid).  The voxel filter emits the down-sampled cloud in the order of the
+ *                  scan in ascending time order (equal stamps in the reference's order) - which is what the cutting
+ *                  lii_ingest_* / lii_frame_select deliver.  An unsorted scan registered as it is comes out correct up to the
+ *                  rounding of those sums (~1e-6 m per centroid).  To get the reference's bits for it, have the library sort it
+ *                  on the device: lii_scan_job::scan_sorted = 2 inside a registration, or lii_scan_sort as a call of its own.
+ * lii_scan_sort:   puts the handle's current scan (lii_scan_upload / lii_scan_set_device / lii_scan_advance / lii_frame_select)
+ *                  into ascending time order, on the device: one key launch, a stable radix sort of (key, index), one gather
+ *                  launch into another buffer of the handle (a selected ingest frame is only read).  The order is ascending t,
+ *                  compared as floats, STABLE: equal stamps keep their input order (the reference's std::sort leaves it
+ *                  unspecified; the ingest fixes it the same way), and -0.0f and +0.0f are equal stamps - they are not
+ *                  reordered.  All four floats of a point travel unchanged.  A NaN stamp is outside the contract: any order,
+ *                  but every point still appears exactly once.  Afterwards lii_scan_download(h, 0, ...) returns the sorted
+ *                  scan and a registration may state scan_sorted = 1.  For callers of lii_undistort_* + lii_downsample +
+ *                  lii_iekf_update.  No scan: LII_ERR_STATE; one point: LII_OK, nothing to do; a communicator attached:
+ *                  LII_ERR_STATE (a sharded job cannot sort for now).  The buffers of the sort (36 bytes per point of
+ *                  max_scan_points + the radix sort's temporary storage) are allocated by the handle's first sort, not by
+ *                  lii_create.  The voxel filter emits the down-sampled cloud in the order of the
  *                  voxels' first points; lii_scan_download(1 / 2) and lii_neighbors_download return the reference's order
  *                  (ascending PCL voxel index).
  * lii_undistort_imu <- back-propagation loop of ImuProcess::propagation_and_undist, src/IMU_Processing.hpp:390-414
@@ -168,6 +181,7 @@ int lii_scan_upload(lii_handle h, const void* points, int32_t n, int32_t stride_
 int lii_scan_upload_next(lii_handle h, const void* points, int32_t n, int32_t stride_bytes, int32_t time_offset_bytes);
 int lii_scan_advance(lii_handle h);
 int lii_scan_set_device(lii_handle h, const void* dev_float4, int32_t n);
+int lii_scan_sort(lii_handle h);
 int lii_undistort_imu(lii_handle h, const lii_pose6d* poses, int32_t n_poses, const double end_R[9],
                       const double end_p[3], const double R_LI[9], const double T_LI[3]);
 int lii_undistort_cv(lii_handle h, const double omega[3], const double vel[3], const double end_R[9]);
@@ -184,7 +198,9 @@ int lii_scan_download(lii_handle h, int32_t which, float* out_float4, int32_t ca
  *                     (CustomMsg) with feature extraction disabled, src/preprocess.cpp:337-713: the handler's filters (they are not
  *                     the cutting functions' in every detail: velodyne_handler has no ring test), no time sort, no cut - ONE frame
  *                     holding pl_surf in input order, its first point included, begin_time_s = header.stamp; hand such a frame to
- *                     lii_scan_register with scan_sorted = 0.  An empty cloud yields no frame (the node skips it, laserMapping.cpp:909-914).
+ *                     lii_scan_register with scan_sorted = 2 (sorted on the device first: the reference's bits - its
+ *                     ImuProcess::Process sorts the frame, src/IMU_Processing.hpp:209, :287) or with scan_sorted = 0 (registered
+ *                     in input order: no sort, the centroids' rounding differs).  An empty cloud yields no frame (the node skips it, laserMapping.cpp:909-914).
  * `data` is sensor_msgs/PointCloud2::data (or the CustomPoint array) as received; the field offsets are what
  * pcl::fromROSMsg derives from msg->fields for the point structs of src/preprocess.h:35-116 (types per lidar_type:
  * VELO time f32 [s] / ring u16; OUSTER t u32 [ns] / ring u8; PANDAR timestamp f64 / ring u16; ROBOSENSE timestamp f64 /
@@ -291,7 +307,17 @@ typedef struct lii_scan_job {
                                       The time-earliest point is then the first and the sweep ends with the last: the library
                                       skips the reduction that finds them (one launch per scan) and de-skews scan_dev in place of
                                       copying it first.  0: nothing is assumed.  A job that claims an order the scan does not have
-                                      gets the A3 quirk / the CV sweep end applied to the wrong point - nothing else depends on it. */
+                                      gets the A3 quirk / the CV sweep end applied to the wrong point - nothing else depends on it.
+                                      2: sort this scan by time on the device first (what lii_scan_sort does: ascending t, stable, -0.0f
+                                      and +0.0f equal) and go on as for 1 - no time-extent launch, the time-earliest point is the first,
+                                      the sweep ends with the last (also pcl_end_time of lii_scan_register_imu).  It buys the reference's
+                                      bits for a scan in any order (a driver cloud, a whole-message ingest frame) without a host sort.
+                                      scan_dev and a selected ingest frame are only read: the sorted scan is written to the handle's own
+                                      scan buffer.  Honoured by lii_scan_register, lii_scan_register_imu and lii_scan_register_cv.  Such a
+                                      job neither uses nor arms the pre-armed prologue (next_scan_dev is ignored); with a communicator
+                                      attached it returns LII_ERR_STATE (single rank only for now).  lii_set_profiling(h, 3) counts the
+                                      sort's launches where it counts the time-extent launch of a scan_sorted = 0 job.  A job of
+                                      struct_size 48 has no such field. */
   int32_t map_update;              /* 1: lii_map_incremental(h, state, NULL, NULL) with the update's final state follows the update inside
                                       this call (src/laserMapping.cpp:1146 behind :1134) - its launches are enqueued behind the update's passes
                                       while the device still works on them, instead of after the result has come back.  The caller does NOT

@@ -121,6 +121,7 @@ _DECLS = {
     "lii_scan_upload_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_advance": (C.c_int, [C.c_void_p]),
     "lii_scan_set_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "lii_scan_sort": (C.c_int, [C.c_void_p]),
     "lii_undistort_imu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
     "lii_undistort_cv": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3),
     "lii_downsample": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -257,6 +258,18 @@ class State:
     bias_a = property(lambda s: s.pod[30:33])
     gravity = property(lambda s: s.pod[33:36])
     cov = property(lambda s: s.pod[36:].reshape(24, 24))
+
+
+def scan_sorted_value(scan_sorted) -> int:
+    """lii_scan_job::scan_sorted from the Python argument: False / 0 - nothing is assumed; True / 1 - ascending time order;
+    2 / "sort" - the library sorts the scan by time on the device first."""
+    if isinstance(scan_sorted, str):
+        if scan_sorted != "sort":
+            raise ValueError(f"scan_sorted: {scan_sorted!r} (False, True, 2 or 'sort')")
+        return 2
+    if not isinstance(scan_sorted, (bool, np.bool_)) and scan_sorted == 2:
+        return 2
+    return 1 if scan_sorted else 0
 
 
 def pose6d_array(n):
@@ -396,6 +409,11 @@ class Registrar:
     def scan_set_device(self, dev):
         self._check(self.L.lii_scan_set_device(self.h, dev[0], dev[1]))
 
+    def scan_sort(self):
+        """The current scan is put into ascending time order on the device (lii_scan_sort): stable, -0.0 and +0.0 equal - the
+        reference's order.  scan_download(0) then returns the sorted scan and a registration may say scan_sorted=True."""
+        self._check(self.L.lii_scan_sort(self.h))
+
     def undistort_imu(self, poses22, end_R, end_p, R_LI, T_LI):
         poses = np.ascontiguousarray(poses22, np.float64).reshape(-1, 22)
         a = [np.ascontiguousarray(x, np.float64).reshape(-1) for x in (end_R, end_p, R_LI, T_LI)]
@@ -497,12 +515,13 @@ class Registrar:
     def scan_register(self, state: State, state_prop: State, *, imu_poses=None, cv=False, leaf=0.0, max_iterations=4,
                       imu_en=False, scan_dev=None, scan_sorted=False, map_update=False, next_scan=None, while_waiting=None):
         """Undistortion + voxel grid + iterated update in one library call (one host synchronisation).  scan_dev: a
-        device_scan() handle to adopt first (what scan_set_device would do, without the separate call).  scan_sorted: the
-        points are in ascending time order (lii_scan_job::scan_sorted).  map_update: map_incremental with the final state
+        device_scan() handle to adopt first (what scan_set_device would do, without the separate call).  scan_sorted: True / 1 - the
+        points are in ascending time order; 2 / "sort" - the library sorts them by time on the device first
+        (lii_scan_job::scan_sorted; register_imu and register_cv take the same values).  map_update: map_incremental with the final state
         follows inside the call (lii_scan_job::map_update) - do not call map_incremental() for this scan."""
         job = lii_scan_job()
         job.struct_size = C.sizeof(lii_scan_job)
-        job.scan_sorted = 1 if scan_sorted else 0
+        job.scan_sorted = scan_sorted_value(scan_sorted)
         job.map_update = 1 if map_update else 0
         if scan_dev is not None:
             job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
@@ -588,7 +607,7 @@ class Registrar:
         job = lii_scan_job()
         job.struct_size = C.sizeof(lii_scan_job)
         job.undistort = 1
-        job.scan_sorted = 1 if scan_sorted else 0
+        job.scan_sorted = scan_sorted_value(scan_sorted)
         job.map_update = 1 if map_update else 0
         if scan_dev is not None:
             job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
@@ -621,7 +640,7 @@ class Registrar:
         job = lii_scan_job()
         job.struct_size = C.sizeof(lii_scan_job)
         job.undistort = int(undistort)
-        job.scan_sorted = 1 if scan_sorted else 0
+        job.scan_sorted = scan_sorted_value(scan_sorted)
         job.map_update = 1 if map_update else 0
         if scan_dev is not None:
             job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]

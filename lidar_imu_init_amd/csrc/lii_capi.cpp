@@ -164,6 +164,32 @@ int scan_materialize(lii_handle h) {
   const int n = h->scan_pending_n;
   return lii_scan_set_device(h, src, n);  // (clears the pending frame through extent_discard, then copies from `src`)
 }
+int scan_sort_into(lii_handle h, const float4* src, int n) {
+  if (n <= 0) return LII_OK;
+  lii_context::ScanSort& b = h->ssort;
+  if (!b.d_temp) {  // the first sort of this handle: a handle that never sorts holds none of this (d_temp comes last: an attempt that failed half way is repeated whole)
+    const size_t cap = size_t(h->cfg.max_scan_points);
+    HIPCHK(h, b.d_key_a.grow(cap));
+    HIPCHK(h, b.d_key_b.grow(cap));
+    HIPCHK(h, b.d_idx_a.grow(cap));
+    HIPCHK(h, b.d_idx_b.grow(cap));
+    HIPCHK(h, b.d_out.grow(cap));
+    HIPCHK(h, b.d_temp.alloc(sort_temp_bytes(h->cfg.max_scan_points)));
+  }
+  hipStream_t s = h->stream;
+  const bool in_place = src == h->d_scan.get();
+  if (n == 1) {  // nothing to sort
+    if (!in_place) HIPCHK(h, hipMemcpyAsync(h->d_scan, src, sizeof(float4), hipMemcpyDeviceToDevice, s));
+    return LII_OK;
+  }
+  launch_sort_keys(src, n, b.d_key_a, b.d_idx_a, s);
+  sort_pairs_u32(b.d_temp, b.d_temp.size(), b.d_key_a, b.d_key_b, b.d_idx_a, b.d_idx_b, n, s);
+  launch_sort_gather(src, b.d_idx_b, n, in_place ? b.d_out.get() : h->d_scan.get(), s);
+  HIPCHK(h, hipGetLastError());
+  // (the stream orders everything that read or writes either buffer; the other scan buffer of lii_scan_upload_next is not involved)
+  if (in_place) std::swap(h->d_scan, b.d_out);
+  return LII_OK;
+}
 unsigned long long* extent_of_scan(lii_handle h) {
   unsigned long long* ext = h->d_extent + 2 * h->extent_sel;
   if (!h->extent_valid) {
@@ -672,6 +698,23 @@ int lii_scan_advance(lii_handle h) {
   h->n_scan = h->n_scan_next;
   h->n_scan_next = -1;
   extent_discard(h);
+  h->bbox_rows = 0;
+  h->n_body = 0;
+  h->n_body_pending = false;
+  h->have_search = false;
+  return LII_OK;
+}
+int lii_scan_sort(lii_handle h) {
+  if (h) h->scan_buf_idle = false;  // (work on the current scan buffer goes out)
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h) return LII_ERR_INVALID;
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_scan_sort: single rank only for now (a communicator is attached)");
+  if (h->n_scan <= 0) return fail(h, LII_ERR_STATE, "lii_scan_sort: no scan (lii_scan_upload / lii_scan_set_device / lii_scan_advance / lii_frame_select)");
+  if (h->n_scan == 1) return scan_materialize(h);
+  // a frame selected by lii_frame_select and not read yet is sorted from where the ingest left it (only read)
+  const int rc = scan_sort_into(h, h->scan_pending ? h->scan_pending : h->d_scan.get(), h->n_scan);
+  if (rc != LII_OK) return rc;
+  extent_discard(h);  // (also: the selected frame has been read)
   h->bbox_rows = 0;
   h->n_body = 0;
   h->n_body_pending = false;

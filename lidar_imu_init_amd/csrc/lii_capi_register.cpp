@@ -504,16 +504,20 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   static_assert(sizeof(lii_scan_job) == 88, "lii_scan_job: the sizes of the earlier ABIs are accepted by number");
   if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || (!state_prop && !feed && !cv) || job->opts.max_iterations < 1)
     return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
-  const bool sorted = job->struct_size >= 56u && job->scan_sorted == 1;
+  // scan_sorted == 2: the scan is put into ascending time order on the device first (scan_sort_into, below), and the call goes on as for
+  // a scan_sorted == 1 job on the handle's own scan buffer
+  const bool sort_first = job->struct_size >= 56u && job->scan_sorted == 2;
+  if (sort_first && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": scan_sorted = 2 is single rank only for now (a communicator is attached)");
+  const bool sorted = job->struct_size >= 56u && (job->scan_sorted == 1 || sort_first);
   h->scan_buf_idle = false;
   int rc = LII_OK;
   const auto t_entry = std::chrono::steady_clock::now();
   if (h->diag && h->prof.host_us[4] > 0) h->prof.host_us[5] += std::chrono::duration<double, std::micro>(t_entry - h->prof.host_last_return).count();
   // the scan to adopt: the caller's device buffer (lii_scan_job::scan_dev), or the frame lii_frame_select left where the ingest put it
   const bool from_job = job->scan_dev != nullptr && job->n_scan_dev > 0;
-  const void* const src_dev = from_job ? job->scan_dev : static_cast<const void*>(h->scan_pending);
+  const void* src_dev = from_job ? job->scan_dev : static_cast<const void*>(h->scan_pending);
   const int src_n = from_job ? job->n_scan_dev : h->scan_pending_n;
-  const bool adopt = src_dev != nullptr && src_n > 0;
+  bool adopt = src_dev != nullptr && src_n > 0;
   if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": n_scan_dev > max_scan_points");
   const int n_next = adopt ? src_n : h->n_scan;
   // A gated de-skew launch waits on the stream (the previous call enqueued it for the scan its job announced): it is used when THIS
@@ -526,14 +530,14 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   bool use_pre = h->pre.armed && sorted && job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= lii::kGateMaxPoses &&
                  cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && leaf_now == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
                  h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, leaf_now) == h->pre.fuse;
-  if (feed || cv) use_pre = false;  // (lii_scan_register_imu / _cv: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
+  if (feed || cv || sort_first) use_pre = false;  // (lii_scan_register_imu / _cv, a job that sorts: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
   if (!use_pre) prearm_cancel(h);
   // ... and what this job announces for the next call (update_on_device arms it behind the passes)
   h->pre.want_dev = nullptr;
-  if (!feed && !cv && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
+  if (!feed && !cv && !sort_first && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
       sorted && job->undistort == 1) {
     h->pre.want_dev = job->next_scan_dev; h->pre.want_n = job->next_n_scan; h->pre.want_leaf = leaf_now; h->pre.want_late = false;
-  } else if (!feed && !cv && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
+  } else if (!feed && !cv && !sort_first && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
     // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
     h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = leaf_now; h->pre.want_late = true;
   }
@@ -549,6 +553,16 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   if (use_pre && !fast) { prearm_cancel(h); use_pre = false; }  // (cannot happen with the conditions above; a waiting launch must never be left behind a call that will not feed it)
   if (job->undistort != 0 && job->undistort != 1 && job->undistort != 2) return fail(h, LII_ERR_INVALID, std::string(who) + ": undistort must be 0, 1 or 2");
   const auto t_first = std::chrono::steady_clock::now();
+  if (sort_first && n_next > 0) {
+    // (behind the first profiling mark: lii_set_profiling(h, 3) counts these launches where it counts the time-extent launch of a scan in any order)
+    rc = scan_sort_into(h, adopt ? static_cast<const float4*>(src_dev) : h->d_scan.get(), n_next);
+    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
+    extent_discard(h);  // (the sorted scan in d_scan is the current one: a selected frame has been read, an extent of the old order is void)
+    h->n_scan = n_next;
+    h->bbox_rows = 0;
+    adopt = false;
+    src_dev = nullptr;
+  }
   if (feed) {
     rc = imu_prologue(h, job, feed, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
     if (rc != LII_OK) { h->prof.kp_active = false; return rc; }

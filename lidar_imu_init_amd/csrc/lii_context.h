@@ -119,6 +119,13 @@ struct lii_context {
   bool scan_buf_idle = false;        // everything ever enqueued on the CURRENT scan buffer is known to have completed (an update's result came back behind it,
                                      // nothing touched the buffer since): lii_scan_upload_next may write the other buffer - the one that was current before the
                                      // last lii_scan_advance - without an event between the two streams
+  // the time sort of a scan (lii_scan_job::scan_sorted == 2, lii_scan_sort): created by the first sort (scan_sort_buffers), sized from
+  // max_scan_points; nothing else uses them (d_sort_temp may be in use by a map update on map_stream)
+  struct ScanSort {
+    DevBuf<unsigned int> d_key_a, d_key_b, d_idx_a, d_idx_b;
+    DevBuf<float4> d_out;            // a scan that sits in d_scan is gathered into this buffer, and the two are swapped
+    DevBuf<unsigned char> d_temp;    // temporary storage of sort_pairs_u32
+  } ssort;
   DevBuf<float4> d_body;   // down-sampled body points
   DevBuf<float4> d_world;
   DevBuf<float4> d_nbr;    // 5 x cap
@@ -325,6 +332,9 @@ int resolve_n_body(lii_handle h);
 bool fuse_filter(lii_handle h, float leaf);  // does the de-skew of this scan fill the hashed voxel filter's table on the way?
 int pcl_order(lii_handle h, const int** perm);
 void extent_discard(lii_handle h);
+// `src` (n points: a caller's device buffer, a frame of the ingest, or d_scan itself) -> d_scan in ascending time order, stable; the
+// launches go on the handle's stream, `src` is only read.  Does not touch the handle's book-keeping of the scan (n_scan, extent, ...).
+int scan_sort_into(lii_handle h, const float4* src, int n);
 int scan_materialize(lii_handle h);  // a frame selected by lii_frame_select and not read yet -> d_scan (lii_scan_set_device)
 bool gate_move(lii::GateState* st, unsigned long long seq, unsigned long long to);  // the state word: armed -> `to`, if still armed
 void prearm_cancel(lii_handle h);  // a gated de-skew launch that waits on the stream is told to end (every entry point that uses the stream calls this first)

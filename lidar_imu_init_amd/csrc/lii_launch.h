@@ -98,6 +98,9 @@ int register_blocks(int n);
 // undistortion
 void launch_time_extent(const float4* pts, int n, unsigned long long* extent, unsigned long long* extent_next, float4* copy_to,
                         const void* ctrl_src, void* ctrl_dst, size_t ctrl_bytes, hipStream_t s);
+// the time sort of a scan: key[i] = order-preserving image of t (-0.0 as +0.0), idx[i] = i; then sort_pairs_u32; then dst[i] = src[idx[i]]
+void launch_sort_keys(const float4* pts, int n, unsigned int* key, unsigned int* idx, hipStream_t s);
+void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
 // voxel grid
 void launch_voxel_minmax(const float4* pts, int n, unsigned int* mm, unsigned int* mm_next, hipStream_t s);
 void launch_voxel_keys(const float4* pts, int n, const unsigned int* mm, const unsigned int* bbox_rows, int n_rows, float leaf,

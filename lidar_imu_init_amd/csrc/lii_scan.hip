@@ -80,6 +80,27 @@ __global__ __launch_bounds__(256) void k_time_extent(const float4* __restrict__ 
     atomicMax(&extent[1], mx);
   }
 }
+// ------------------------------------------------------------------------------------------------
+// the time sort of a scan (lii_scan_job::scan_sorted == 2, lii_scan_sort; src/IMU_Processing.hpp:209, :287): key launch ->
+// sort_pairs_u32 (lii_sort.hip; an LSD radix sort is stable and the value is the input index: equal keys keep their input order)
+// -> gather launch.
+// key[i] = the order-preserving image of t, idx[i] = i.  The reference compares floats: -0.0f == +0.0f, so the two must not be
+// told apart by the key (f2ord alone would put -0.0 first) - the KEY is canonicalised, the point travels as it is.
+__global__ __launch_bounds__(256) void k_sort_keys(const float4* __restrict__ pts, int n, unsigned int* __restrict__ key, unsigned int* __restrict__ idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned int u = __float_as_uint(pts[i].w);
+  if ((u << 1) == 0u) u = 0u;  // (-0.0 -> +0.0)
+  key[i] = f2ord(__uint_as_float(u));
+  idx[i] = (unsigned int)i;
+}
+// dst[i] = src[idx[i]], all four floats as they are.  Never in place: dst is another buffer than src.
+__global__ __launch_bounds__(256) void k_sort_gather(const float4* __restrict__ src, const unsigned int* __restrict__ idx, int n, float4* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned int j = idx[i];
+  if (j < (unsigned int)n) dst[i] = src[j];  // (idx is a permutation of 0 .. n - 1: the sort only moves what k_sort_keys wrote)
+}
 // (ord2f and exp_so3 - Exp(ang_vel, dt), include/so3_math.h:37-59 - live in lii_device.h: lii_imu.hip shares them)
 struct UndistArg {
   double endR[9], endp[3], RLI[9], TLI[3];
@@ -922,6 +943,12 @@ void launch_time_extent(const float4* pts, int n, unsigned long long* extent, un
   if (nb < 1) nb = 1;
   hipLaunchKernelGGL(k_time_extent, dim3(nb + (ctrl_bytes ? 1 : 0)), dim3(256), 0, s, pts, n, extent, extent_next, copy_to,
                      static_cast<const uint4*>(ctrl_src), static_cast<uint4*>(ctrl_dst), (int)(ctrl_bytes / 16));
+}
+void launch_sort_keys(const float4* pts, int n, unsigned int* key, unsigned int* idx, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_sort_keys, dim3(nblk(n, 256)), dim3(256), 0, s, pts, n, key, idx);
+}
+void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_sort_gather, dim3(nblk(n, 256)), dim3(256), 0, s, src, idx, n, dst);
 }
 void launch_voxel_minmax(const float4* pts, int n, unsigned int* mm, unsigned int* mm_next, hipStream_t s) {
   int nb = nblk(n, 256 * 4);
