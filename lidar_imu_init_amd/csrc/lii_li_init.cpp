@@ -14,12 +14,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/liinit_hip.h"
 
 struct lii_context;
 int lii_internal_li_init_on_device(lii_context* h);  // lii_capi.cpp: lii_li_init_set_device
+int lii_internal_fail(lii_context* h, int code, const std::string& msg);  // lii_capi.cpp: records the message of lii_last_error
 
 namespace {
 
@@ -257,6 +259,10 @@ int lii_li_init_run(lii_handle h, const lii_calib_state* imu_in, const lii_calib
   // (lii_li_init_dev.hip - bit-identical to the host functions above); everything else of the chain is O(N) bookkeeping
   const bool dev = lii_internal_li_init_on_device(h) != 0;
   auto zero_phase_pair = [&](const Seq& a, const Seq& b, Seq& fa, Seq& fb) -> int {
+    // butter()'s 60-sample reflection reads in[60] and in[n - 61]: fewer than 61 records (a cross-correlation lag that leaves
+    // almost no overlap) would be read out of bounds, as the reference reads them - refused on both chains
+    if (a.size() < 61 || b.size() < 61)
+      return lii_internal_fail(h, LII_ERR_INVALID, "lii_li_init_run: fewer than 61 aligned states left to filter");
     if (!dev || a.size() != b.size() || a.size() < 62) { fa = zero_phase(a); fb = zero_phase(b); return LII_OK; }
     Seq both(a);
     both.insert(both.end(), b.begin(), b.end());
