@@ -178,6 +178,13 @@ struct lii_replay {
   std::vector<double> log;  // LII_REPLAY_ROW doubles per processed scan
   bool device_imu = false;  // lii_replay_set_device_imu: ImuProcess::Process' propagation through lii_scan_register_imu / lii_scan_register_cv
   int32_t device_calls[4] = {0, 0, 0, 0};  // lii_replay_device_calls: lii_scan_register_imu, lii_scan_register_cv, lii_cv_propagate, lii_map_build_from_scan
+  // lii_replay_set_publish: the registered clouds of every scan (:1152-1156) and the pcl_wait_save flush (:603-612); off by default
+  int32_t pub_clouds = 0, pub_save_interval = 0, max_scan_points = 0;
+  bool pub_placed = false;
+  int scan_wait_num = 0;
+  std::vector<float> pub_cloud[4];   // the last scan's clouds, by bit of lii_publish_opts::clouds
+  std::vector<float> pcl_wait_save;  // what the last flush handed over (the reference writes it to a PCD file)
+  int32_t pcd_index = 0;             // flushes so far
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -205,6 +212,7 @@ int lii_replay_create(const lii_replay_config* cfg, lii_replay** out) {
   if (cfg->result_path) r->result_path = cfg->result_path;
   r->stop_after_init = cfg->stop_after_init != 0;
   r->cut_frame_num = r->prm.cut_frame ? r->prm.cut_frame_num : 1;
+  r->max_scan_points = cfg->max_scan_points;
   r->mean_acc_norm = r->prm.mean_acc_norm;
   state_init(&r->state);
   // main() :851-867: the IMU processor's noise scales come from the parameter file; the extrinsic covariance from Rot_LI_cov / Trans_LI_cov
@@ -232,6 +240,31 @@ lii_handle lii_replay_handle(lii_replay* r) { return r ? r->h : nullptr; }
 int lii_replay_set_device_imu(lii_replay* r, int32_t on) {
   if (!r) return LII_ERR_INVALID;
   r->device_imu = on != 0;
+  return LII_OK;
+}
+
+// The registered clouds where the reference publishes them (src/laserMapping.cpp:1152-1156): `clouds` (LII_PUB_* bits) are ordered from the
+// library once (lii_publish_set, with copies to the host) and fetched behind every registration; save_interval > 0 is pcd_save_en with
+// pcd_save_interval: the dense world cloud of every scan is appended on the device and flushed every save_interval scans (:603-612).
+// 0, 0 (the default): process() makes the calls it made before.
+int lii_replay_set_publish(lii_replay* r, int32_t clouds, int32_t save_interval) {
+  if (!r || (clouds & ~15) || save_interval < 0) return LII_ERR_INVALID;
+  r->pub_clouds = clouds;
+  r->pub_save_interval = save_interval;
+  r->pub_placed = false;
+  return LII_OK;
+}
+// cloud: one LII_PUB_* bit, or 0 for what the last flush of the save buffer handed over; the last processed scan's points -> out
+// (capacity points of 4 floats; out may be NULL: *n only)
+int lii_replay_cloud(lii_replay* r, int32_t cloud, float* out, int32_t capacity, int32_t* n) {
+  if (!r || !n) return LII_ERR_INVALID;
+  const int c = cloud == 0 ? 4 : cloud == LII_PUB_DENSE ? 0 : cloud == LII_PUB_DOWN ? 1 : cloud == LII_PUB_EFFECT ? 2 : cloud == LII_PUB_BODY ? 3 : -1;
+  if (c < 0) return LII_ERR_INVALID;
+  const std::vector<float>& v = c == 4 ? r->pcl_wait_save : r->pub_cloud[c];
+  *n = int32_t(v.size() / 4);
+  if (!out) return LII_OK;
+  if (capacity < *n) return LII_ERR_CAPACITY;
+  if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(float));
   return LII_OK;
 }
 
@@ -669,6 +702,14 @@ static int process(lii_replay* r) {
   lii_iekf_report rep{};
   job.map_update = 1;
   int rc;
+  if ((r->pub_clouds || r->pub_save_interval > 0) && !r->pub_placed) {  // the standing order, once
+    lii_publish_opts po = {sizeof(lii_publish_opts), r->pub_clouds, 1, 0};
+    const long long cap = (long long)r->pub_save_interval * r->max_scan_points;
+    po.save_capacity = cap > 0x7FFFFFFFll ? 0x7FFFFFFF : int32_t(cap);
+    rc = lii_publish_set(r->h, &po);
+    if (rc != LII_OK) return fail(r, rc, std::string("lii_publish_set: ") + lii_last_error(r->h));
+    r->pub_placed = true;
+  }
   if (device_lio) {
     std::vector<lii_imu_sample> imu(r->meas_imu.size());
     for (size_t i = 0; i < imu.size(); i++) {
@@ -694,6 +735,28 @@ static int process(lii_replay* r) {
   }
   r->frame_num++;
   log_row(r, rep.iterations, rep.effect_num);
+  // ---- publish_frame_world / _body / publish_effect_world (:1152-1156) and the pcl_wait_save flush (:603-612)
+  if (r->pub_placed) {
+    for (int c = 0; c < 4; c++) {
+      if (!(r->pub_clouds & (1 << c))) continue;
+      const float* host = nullptr;
+      int32_t n = 0;
+      rc = lii_publish_fetch(r->h, 1 << c, &host, nullptr, &n);
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_publish_fetch: ") + lii_last_error(r->h));
+      r->pub_cloud[c].assign(host, host + size_t(n) * 4);
+    }
+    if (r->pub_save_interval > 0 && ++r->scan_wait_num >= r->pub_save_interval) {
+      int32_t n = 0;
+      rc = lii_publish_saved(r->h, nullptr, 0, &n, 0);
+      if (rc == LII_OK) {
+        r->pcl_wait_save.resize(size_t(n) * 4);
+        rc = lii_publish_saved(r->h, r->pcl_wait_save.data(), n, &n, 1);
+      }
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_publish_saved: ") + lii_last_error(r->h));
+      r->pcd_index++;
+      r->scan_wait_num = 0;
+    }
+  }
   // ---- refinement result after online_refine_time of LIO (:1164-1178)
   if (r->imu_en && !r->refine_done) {
     double done = r->lidar_end_time - r->online_calib_starts_time;

@@ -445,6 +445,54 @@ int lii_scan_register_cv(lii_handle h, const lii_scan_job* job, double dt, const
  * joins a pending map update first and the next pass searches again. */
 int lii_map_build_from_scan(lii_handle h, const lii_state* state, int32_t* n_map);
 
+/* ---------------------------------------------------------------- the registered clouds of a scan (publish_frame_world / pcd_save)
+ * What laserMapping's loop hands out BEHIND the update, every scan (src/laserMapping.cpp:1152-1156), formed on the device at the
+ * UPDATED state - pointBodyToWorld (:209-220; fp64 arithmetic, float result, the same bits) - without a host round trip:
+ *   LII_PUB_DENSE   publish_frame_world with dense_publish_en (:561-614): the whole de-skewed scan (feats_undistort) in the world frame;
+ *   LII_PUB_DOWN    publish_frame_world without it: feats_down_body in the world frame, in the device's order (that of the voxels'
+ *                   first points; lii_scan_download(h, 1) restores PCL's);
+ *   LII_PUB_EFFECT  publish_effect_world (:625-636): the points whose selection stands after the last pass (laserCloudOri), in the
+ *                   world frame, compacted in ascending index of the device's down-sampled order - the same bits on every run; their
+ *                   number is lii_iekf_report::effect_num;
+ *   LII_PUB_BODY    publish_frame_body (:616-623): the de-skewed scan as it is (a copy).
+ * Every cloud is float4 (x, y, z, t_ms), t_ms carried through unchanged (the scan format has no intensity: a caller joins it by index).
+ * lii_publish_set places a STANDING ORDER on the handle (off by default): from then on every call that reaches its update -
+ * lii_scan_register, lii_scan_register_imu, lii_scan_register_cv, lii_iekf_update - enqueues one more launch behind its passes (behind
+ * the map update of lii_scan_job::map_update, in front of a pre-armed prologue of lii_scan_job::next_scan_dev), which reads the final
+ * state from device memory; a loop the host had to continue gets the launch again behind the passes that ended it.  The clouds are
+ * always those of the state the call returns.  With save_capacity > 0 the dense world cloud of every scan is also appended to a save
+ * buffer on the device (pcl_wait_save, :594-613; created by the first order that asks for it; another capacity: a new, empty buffer):
+ * a scan that does not fit is not appended at all and raises a sticky flag - what the buffer holds is never lost.  With to_host the
+ * clouds are copied to pinned host memory on the handle's copy stream, behind an event.  The clouds live in buffers of their own, two
+ * deep.  NULL, or clouds == 0 && save_capacity == 0: the order is off (the buffers stay for a later order).  A communicator attached,
+ * or LII_TEST=host_solve: LII_ERR_STATE (single rank only for now).  Bad struct_size, unknown bits in clouds, to_host other than
+ * 0 / 1, save_capacity < 0: LII_ERR_INVALID.  lii_set_profiling(h, 3) attributes the launch to LII_KP_PUBLISH.
+ *   lii_publish_now    the same outputs at the CALLER's state from the handle's current scan / down-sampled cloud / selection, for
+ *                      hosts that call lii_undistort_* / lii_downsample / lii_iekf_iterate themselves (:1152-1156 behind their own loop).
+ *   lii_publish_fetch  one cloud (ONE of the LII_PUB_* bits) of the LAST FINISHED registration (or lii_publish_now): *host_float4
+ *                      (NULL without to_host) and *dev_float4 point into the library's buffers and stay valid until the registration
+ *                      AFTER THE NEXT ONE BEGINS (that call's launch and copies overwrite them while it runs, its while_waiting
+ *                      included); *n points.  Either pointer argument may be NULL.  The call waits for that cloud's copy
+ *                      event only (without to_host: the launch's event): it neither uses the handle's stream nor ends a pre-armed launch,
+ *                      so it MAY BE CALLED FROM lii_scan_job::while_waiting of the next call - scan m's clouds are consumed while scan
+ *                      m + 1 is registered.  A cloud that was not ordered, or no registration since the order: LII_ERR_STATE; an unknown
+ *                      cloud: LII_ERR_INVALID.
+ *   lii_publish_saved  the save buffer's points so far -> out_float4 (may be NULL: *n only), and, with clear != 0, an empty buffer
+ *                      (:603-612, the flush every pcd_save_interval scans; writing the PCD file is the caller's).  capacity < *n:
+ *                      LII_ERR_CAPACITY, nothing is cleared.  A scan that did not fit since the last clear: the points are returned
+ *                      and the call reports LII_ERR_CAPACITY.  Uses the handle's stream (not from while_waiting). */
+enum { LII_PUB_DENSE = 1, LII_PUB_DOWN = 2, LII_PUB_EFFECT = 4, LII_PUB_BODY = 8 };
+typedef struct lii_publish_opts {
+  uint32_t struct_size;   /* sizeof(lii_publish_opts) */
+  int32_t clouds;         /* LII_PUB_DENSE 1 | LII_PUB_DOWN 2 | LII_PUB_EFFECT 4 | LII_PUB_BODY 8 */
+  int32_t to_host;        /* 1: also copy each cloud to pinned host memory on the copy stream */
+  int32_t save_capacity;  /* > 0: append the dense world cloud of every scan to a save buffer of that many points */
+} lii_publish_opts;
+int lii_publish_set(lii_handle h, const lii_publish_opts* opts);
+int lii_publish_now(lii_handle h, const lii_state* state);
+int lii_publish_fetch(lii_handle h, int32_t cloud, const float** host_float4, const void** dev_float4, int32_t* n);
+int lii_publish_saved(lii_handle h, float* out_float4, int32_t capacity, int32_t* n, int32_t clear);
+
 /* ---------------------------------------------------------------- LI-Init batch calibration evaluators
  * CalibState record (include/LI_init/LI_init.h:31-89). */
 typedef struct lii_calib_state {
@@ -625,6 +673,7 @@ enum lii_kernel_kind {
   LII_KP_FIT = 4,        /* residual + reduction on cached planes */
   LII_KP_SOLVE = 5,      /* final sum + 24-state solve */
   LII_KP_PROPAGATE = 6,  /* lii_scan_register_imu: IMU forward propagation (+ the time-extent launch of an unsorted scan in front of it) */
+  LII_KP_PUBLISH = 7,    /* lii_publish_set: the registered clouds of the scan (k_publish_world) */
   LII_KP_KINDS = 8
 };
 typedef struct lii_kernel_profile {

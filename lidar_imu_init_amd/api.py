@@ -59,7 +59,14 @@ class lii_kernel_profile(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("scans", C.c_int32), ("ms", C.c_double * 8), ("launches", C.c_int32 * 8)]
 
 
-KERNEL_KINDS = ("deskew", "voxel", "knn", "fit_search", "fit", "solve", "propagate")  # enum lii_kernel_kind
+KERNEL_KINDS = ("deskew", "voxel", "knn", "fit_search", "fit", "solve", "propagate", "publish")  # enum lii_kernel_kind
+
+
+class lii_publish_opts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("clouds", C.c_int32), ("to_host", C.c_int32), ("save_capacity", C.c_int32)]
+
+
+PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 
 
 class lii_imu_sample(C.Structure):
@@ -154,6 +161,10 @@ _DECLS = {
     "lii_scan_register_cv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(lii_iekf_report)]),
     "lii_map_build_from_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "lii_publish_set": (C.c_int, [C.c_void_p, C.POINTER(lii_publish_opts)]),
+    "lii_publish_now": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lii_publish_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "lii_publish_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "lii_map_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_calib_set_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_calib_eval": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -214,6 +225,13 @@ def load_library():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+class _DeviceFloat4:
+    """A device buffer the library hands out, as torch reads it (__cuda_array_interface__): n x 4 float32."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = dict(shape=(int(n), 4), typestr="<f4", data=(int(ptr), False), version=2)
 
 
 def _ptr(a):
@@ -661,6 +679,42 @@ class Registrar:
                                                 _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
         return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
                                  converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+
+    # ------------------------------------------------------------------ the registered clouds (publish_frame_world / pcd_save)
+    def publish_set(self, clouds=0, to_host=False, save_capacity=0):
+        """The standing order (lii_publish_set): clouds = PUB_DENSE | PUB_DOWN | PUB_EFFECT | PUB_BODY; nothing ordered: off."""
+        if not clouds and not save_capacity:
+            self._check(self.L.lii_publish_set(self.h, None))
+            return
+        o = lii_publish_opts(C.sizeof(lii_publish_opts), int(clouds), int(bool(to_host)), int(save_capacity))
+        self._check(self.L.lii_publish_set(self.h, C.byref(o)))
+
+    def publish_now(self, state: State):
+        self._check(self.L.lii_publish_now(self.h, _ptr(state.pod)))
+
+    def publish_fetch(self, cloud, copy=True):
+        """One cloud of the last finished registration as an (n, 4) float32 array: a view of the library's pinned buffer (to_host;
+        copy=False - valid until the registration after the next one begins) or a copy; without to_host the device buffer is
+        downloaded.  Callable from while_waiting of the next call."""
+        hp, dp, n = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self._check(self.L.lii_publish_fetch(self.h, int(cloud), C.byref(hp), C.byref(dp), C.byref(n)))
+        if n.value == 0:
+            return np.zeros((0, 4), np.float32)
+        if hp.value:
+            a = np.ctypeslib.as_array(C.cast(hp, C.POINTER(C.c_float)), shape=(n.value, 4))
+            return a.copy() if copy else a
+        import torch  # (device only: the buffer is read through torch, the project's plumbing)
+        return torch.as_tensor(_DeviceFloat4(dp.value, n.value), device="cuda").cpu().numpy().copy()
+
+    def publish_saved(self, clear=False):
+        """The save buffer (pcl_wait_save) as an (n, 4) float32 array; LIIError(-4) if a scan did not fit since the last clear."""
+        n = C.c_int32(0)
+        rc = self.L.lii_publish_saved(self.h, None, 0, C.byref(n), 0)
+        if rc not in (0, -4):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._check(self.L.lii_publish_saved(self.h, _ptr(out), len(out), C.byref(n), int(bool(clear))))
+        return out[:n.value]
 
     def neighbors(self, n):
         pts = np.zeros((n, 5, 3), np.float32)

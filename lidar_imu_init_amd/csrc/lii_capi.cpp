@@ -645,8 +645,8 @@ int lii_scan_upload_next(lii_handle h, const void* points, int32_t n, int32_t st
   if (!h || (!points && n > 0) || n < 0 || stride_bytes < 16 || time_offset_bytes < 12 || time_offset_bytes + 4 > stride_bytes)
     return fail(h, LII_ERR_INVALID, "lii_scan_upload_next: bad arguments");
   if (n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_scan_upload_next: n > max_scan_points");
-  if (!h->copy_stream) {
-    HIPCHK(h, h->copy_stream.create(hipStreamNonBlocking));
+  if (!h->copy_stream) HIPCHK(h, h->copy_stream.create(hipStreamNonBlocking));  // (lii_publish_set may have created it for its copies)
+  if (!h->d_scan_next) {
     HIPCHK(h, h->ev_next.create(hipEventDisableTiming));
     HIPCHK(h, h->ev_scan_free.create(hipEventDisableTiming));
     HIPCHK(h, h->d_scan_next.alloc(size_t(h->cfg.max_scan_points)));

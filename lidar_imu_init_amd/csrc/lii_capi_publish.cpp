@@ -1,0 +1,205 @@
+// libliinit_hip — the registered clouds of a scan (host side): lii_publish_set / _now / _fetch / _saved and the two hooks the
+// registration loop calls (publish_enqueue, publish_finish).  Kernel: lii_publish.hip.  Reference: src/laserMapping.cpp:1152-1156
+// (publish_frame_world :561-614, publish_frame_body :616-623, publish_effect_world :625-636, pcl_wait_save :594-613).
+#include "lii_context.h"
+
+using namespace lii_impl;
+
+namespace {
+constexpr int kAllClouds = LII_PUB_DENSE | LII_PUB_DOWN | LII_PUB_EFFECT | LII_PUB_BODY;
+int cloud_index(int cloud) {
+  return cloud == LII_PUB_DENSE ? 0 : cloud == LII_PUB_DOWN ? 1 : cloud == LII_PUB_EFFECT ? 2 : cloud == LII_PUB_BODY ? 3 : -1;
+}
+}  // namespace
+
+int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg* ps, bool first) {
+  lii_context::Publish& P = h->pub;
+  if (!P.on) return LII_OK;
+  hipStream_t s = h->stream;
+  const int slot = P.cur;
+  const int n_scan = h->n_scan;
+  const size_t cap = size_t(h->cfg.max_scan_points);
+  if (n_scan < 0 || size_t(n_scan) > cap || h->n_body < 0 || size_t(h->n_body) > cap) return fail(h, LII_ERR_CAPACITY, "publish: the scan exceeds max_scan_points");
+  // the slot's clouds of two registrations ago may still be on their way to the host: the launch that overwrites them waits for the copy
+  if (P.last_copy[slot] >= 0) HIPCHK(h, hipStreamWaitEvent(s, P.ev_copy[P.last_copy[slot]][slot], 0));
+  if (first && (P.clouds & LII_PUB_BODY) && n_scan > 0)  // publish_frame_body: the de-skewed scan as it is
+    HIPCHK(h, hipMemcpyAsync(P.d_cloud[3][slot], h->d_scan, sizeof(float4) * size_t(n_scan), hipMemcpyDeviceToDevice, s));
+  const bool want_dense = (P.clouds & LII_PUB_DENSE) != 0, want_save = P.save_capacity > 0;
+  const bool want_down = (P.clouds & LII_PUB_DOWN) != 0, want_effect = (P.clouds & LII_PUB_EFFECT) != 0;
+  PublishArgs a = {};
+  a.scan = h->d_scan;
+  a.n_scan = n_scan;
+  a.dense_blocks = (want_dense || want_save) ? (n_scan + 255) / 256 : 0;
+  a.dense = want_dense ? P.d_cloud[0][slot].get() : nullptr;
+  a.save = want_save ? P.d_save.get() : nullptr;
+  a.save_cap = P.save_capacity;
+  a.save_par = P.save_par;
+  a.save_ctl = P.d_save_ctl;
+  a.body = h->d_body;
+  a.n_body = h->n_body;
+  a.n_body_dev = h->n_body_pending ? h->d_nbody.get() : nullptr;
+  a.down = want_down ? P.d_cloud[1][slot].get() : nullptr;
+  a.selected = h->d_selected;
+  a.effect = want_effect ? P.d_cloud[2][slot].get() : nullptr;
+  a.words = P.d_words;
+  P.epoch = P.epoch == 0xFFFFFFFFu ? 1u : P.epoch + 1u;
+  a.epoch = P.epoch;
+  a.counts_dev = P.d_counts + 2 * slot;
+  a.counts_host = P.h_counts + 4 * slot;
+  a.guard = guard;
+  a.test_late = h->test_emit_late ? 1 : 0;
+  a.seq = h->update_seq;
+  const int down_blocks = (want_down || want_effect) ? std::max(1, (h->n_body + 255) / 256) : 0;
+  if (size_t(down_blocks) > P.d_words.size()) return fail(h, LII_ERR_CAPACITY, "publish: more workgroups than prefix words");
+  P.kp_idx = -1;
+  if (a.dense_blocks + down_blocks > 0) {
+    if (h->prof.kp_active) { P.kp_idx = h->prof.kp_n; const int r = kp_mark(h, LII_KP_PUBLISH); if (r != LII_OK) return r; }
+    launch_publish_world(a, down_blocks, ps ? *ps : PoseArg{}, s);
+    HIPCHK(h, hipGetLastError());
+    if (want_save && a.dense_blocks > 0) P.save_par ^= 1;  // (the launch has moved the offset to the other word, whether it appended or not)
+    if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_KINDS); if (r != LII_OK) return r; }
+  }
+  HIPCHK(h, hipEventRecord(P.ev_pub[slot], s));
+  if (P.to_host) {
+    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, P.ev_pub[slot], 0));
+    const int n_of[lii_context::Publish::kClouds] = {n_scan, h->n_body, h->n_body, n_scan};  // (down-sampled / effect: the bound; the counts travel in h_counts)
+    for (int c = 0; c < lii_context::Publish::kClouds; c++) {
+      if (!(P.clouds & (1 << c))) continue;
+      if (n_of[c] > 0)
+        HIPCHK(h, hipMemcpyAsync(P.h_cloud[c][slot], P.d_cloud[c][slot], sizeof(float4) * size_t(n_of[c]), hipMemcpyDeviceToHost, h->copy_stream));
+      HIPCHK(h, hipEventRecord(P.ev_copy[c][slot], h->copy_stream));
+      P.last_copy[slot] = c;
+    }
+  }
+  h->scan_buf_idle = false;  // (the launch and the body copy read the current scan buffer: lii_scan_upload_next orders its transfer behind them)
+  P.n_scan_at[slot] = n_scan;
+  P.clouds_at[slot] = P.clouds;
+  return LII_OK;
+}
+
+void lii_impl::publish_finish(lii_handle h) {
+  lii_context::Publish& P = h->pub;
+  if (!P.on) return;
+  P.have = P.cur;
+  P.cur ^= 1;
+}
+
+extern "C" {
+
+int lii_publish_set(lii_handle h, const lii_publish_opts* opts) {
+  if (!h) return LII_ERR_INVALID;
+  if (opts && (opts->struct_size != sizeof(lii_publish_opts) || (opts->clouds & ~kAllClouds) || (opts->to_host != 0 && opts->to_host != 1) || opts->save_capacity < 0))
+    return fail(h, LII_ERR_INVALID, "lii_publish_set: bad lii_publish_opts (struct_size, unknown cloud bits, to_host, save_capacity)");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_publish_set: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  lii_context::Publish& P = h->pub;
+  if (!opts || (opts->clouds == 0 && opts->save_capacity == 0)) {  // off: the buffers stay for a later order
+    P.on = false;
+    P.have = -1;
+    return LII_OK;
+  }
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_publish_set: single rank only for now (a communicator is attached)");
+  if (h->host_solve) return fail(h, LII_ERR_STATE, "lii_publish_set: single rank only for now - not with LII_TEST=host_solve (the host-driven loop has no control block to publish from)");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (a launch of the previous order may still read what is replaced below)
+  if (h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+  P.on = false;
+  P.have = -1;
+  const size_t cap = size_t(h->cfg.max_scan_points);
+  for (int c = 0; c < lii_context::Publish::kClouds; c++) {
+    if (!(opts->clouds & (1 << c))) continue;
+    for (int k = 0; k < 2; k++) {
+      if (!P.d_cloud[c][k]) HIPCHK(h, P.d_cloud[c][k].alloc(cap));
+      if (opts->to_host && !P.h_cloud[c][k]) HIPCHK(h, P.h_cloud[c][k].alloc(cap, hipHostMallocDefault));
+      if (opts->to_host && !P.ev_copy[c][k]) HIPCHK(h, P.ev_copy[c][k].create(hipEventDisableTiming));
+    }
+  }
+  if (opts->to_host && !h->copy_stream) HIPCHK(h, h->copy_stream.create(hipStreamNonBlocking));
+  if (!P.d_counts) {
+    HIPCHK(h, P.d_counts.alloc(4));
+    HIPCHK(h, hipMemset(P.d_counts, 0, sizeof(int) * 4));
+  }
+  if (!P.h_counts) {
+    HIPCHK(h, P.h_counts.alloc(8, hipHostMallocMapped));
+    std::memset(P.h_counts, 0, sizeof(int) * 8);
+  }
+  if (!P.d_words) {
+    HIPCHK(h, P.d_words.alloc(cap / 256 + 2));
+    HIPCHK(h, hipMemset(P.d_words, 0, sizeof(unsigned long long) * P.d_words.size()));  // (run number 0 is never used)
+  }
+  for (int k = 0; k < 2; k++)
+    if (!P.ev_pub[k]) HIPCHK(h, P.ev_pub[k].create(hipEventDisableTiming));
+  if (opts->save_capacity > 0 && P.d_save.size() != size_t(opts->save_capacity)) {  // the first order that asks for it (another capacity: a new, empty buffer)
+    HIPCHK(h, P.d_save.grow(size_t(opts->save_capacity)));
+    if (!P.d_save_ctl) HIPCHK(h, P.d_save_ctl.alloc(4));
+    HIPCHK(h, hipMemset(P.d_save_ctl, 0, sizeof(int) * 4));
+    P.save_par = 0;
+  }
+  P.clouds = opts->clouds;
+  P.to_host = opts->to_host;
+  P.save_capacity = opts->save_capacity;
+  P.cur = 0;
+  P.last_copy[0] = P.last_copy[1] = -1;  // (both streams were drained above)
+  P.on = true;
+  return LII_OK;
+}
+
+int lii_publish_now(lii_handle h, const lii_state* state) {
+  if (!h || !state) return fail(h, LII_ERR_INVALID, "lii_publish_now: bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_publish_now: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  lii_context::Publish& P = h->pub;
+  if (!P.on) return fail(h, LII_ERR_STATE, "lii_publish_now: nothing is ordered (lii_publish_set)");
+  { const int rcm = scan_materialize(h); if (rcm != LII_OK) return rcm; }
+  if ((P.clouds & (LII_PUB_DOWN | LII_PUB_EFFECT)) && h->n_body <= 0)
+    return fail(h, LII_ERR_STATE, "lii_publish_now: no down-sampled scan (call lii_downsample / lii_downsample_skip)");
+  const PoseArg ps = pose_of(*state);
+  const int rc = publish_enqueue(h, nullptr, &ps, true);
+  if (rc != LII_OK) return rc;
+  publish_finish(h);
+  return LII_OK;
+}
+
+int lii_publish_fetch(lii_handle h, int32_t cloud, const float** host_float4, const void** dev_float4, int32_t* n) {
+  if (!h || !n) return fail(h, LII_ERR_INVALID, "lii_publish_fetch: bad arguments");
+  const int c = cloud_index(cloud);
+  if (c < 0) return fail(h, LII_ERR_INVALID, "lii_publish_fetch: unknown cloud");
+  lii_context::Publish& P = h->pub;
+  if (!P.on || P.have < 0) return fail(h, LII_ERR_STATE, "lii_publish_fetch: no registration since the order (lii_publish_set)");
+  const int slot = P.have;
+  if (!(P.clouds_at[slot] & cloud)) return fail(h, LII_ERR_STATE, "lii_publish_fetch: this cloud was not ordered");
+  // this cloud's event only: neither the handle's stream nor a pre-armed launch behind it is touched
+  HIPCHK(h, hipEventSynchronize(P.to_host ? P.ev_copy[c][slot] : P.ev_pub[slot]));
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const volatile int* hc = P.h_counts + 4 * slot;
+  *n = (c == 0 || c == 3) ? P.n_scan_at[slot] : hc[c == 1 ? 0 : 1];
+  if (host_float4) *host_float4 = P.to_host ? reinterpret_cast<const float*>(P.h_cloud[c][slot].get()) : nullptr;
+  if (dev_float4) *dev_float4 = P.d_cloud[c][slot].get();
+  return LII_OK;
+}
+
+int lii_publish_saved(lii_handle h, float* out_float4, int32_t capacity, int32_t* n, int32_t clear) {
+  if (!h || !n) return fail(h, LII_ERR_INVALID, "lii_publish_saved: bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_publish_saved: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  lii_context::Publish& P = h->pub;
+  if (!P.d_save) return fail(h, LII_ERR_STATE, "lii_publish_saved: no save buffer (lii_publish_opts::save_capacity)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int ctl[4] = {0, 0, 0, 0};
+  HIPCHK(h, hipMemcpy(ctl, P.d_save_ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  const int cnt = ctl[P.save_par];
+  *n = cnt;
+  if (cnt < 0 || size_t(cnt) > P.d_save.size()) return fail(h, LII_ERR_HIP, "lii_publish_saved: append offset out of range");
+  if (out_float4) {
+    if (capacity < cnt) return fail(h, LII_ERR_CAPACITY, "lii_publish_saved: capacity too small");
+    if (cnt > 0) HIPCHK(h, hipMemcpy(out_float4, P.d_save, sizeof(float4) * size_t(cnt), hipMemcpyDeviceToHost));
+  }
+  if (clear) {
+    HIPCHK(h, hipMemset(P.d_save_ctl, 0, sizeof(int) * 4));
+    P.save_par = 0;
+  }
+  if (ctl[2]) return fail(h, LII_ERR_CAPACITY, "lii_publish_saved: the save buffer overflowed - at least one scan was not appended (what it held is intact)");
+  return LII_OK;
+}
+
+}  // extern "C"

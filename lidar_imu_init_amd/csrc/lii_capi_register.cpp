@@ -210,6 +210,9 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     g = grid_view(h);
     if (h->diag) h->prof.host_map_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_me0).count();
   }
+  // lii_publish_set: the registered clouds go out now as well - behind the passes and the map update, in front of a pre-armed prologue.
+  // The launch reads the final state from the control block and does nothing if the loop has parked (then it is enqueued again below).
+  if (h->pub.on) { rc = publish_enqueue(h, h->d_ctrl, nullptr, true); if (rc != LII_OK) return rc; }
   // THE NEXT SCAN'S PROLOGUE, pre-armed (lii_launch.h: DeskewGate): the job announced the scan the next call will bring - its de-skew +
   // filter-insert launch goes out now, behind this update's passes (and its map update), and waits on the device for the record
   // the next lii_scan_register writes.
@@ -248,8 +251,10 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   // searches - and as many passes behind it as the longer of the last two updates ran; should that not be enough (the next search
   // comes at another pass as well, or the update runs longer) it parks again and is continued again.  (Round 3 enqueued every
   // remaining pass with every k-NN launch: up to nine launches that only read a flag, ~ 20 us on a scan that parks.)
+  bool parked_once = false;
   for (int round = 0; h->h_res->done == (h->update_seq | kLoopParked); round++) {
     if (round > 2 * opts->max_iterations) return fail(h, LII_ERR_HIP, "device loop parked again and again");
+    parked_once = true;
     const int from = h->h_res->parked_it;
     const bool search = h->h_res->parked_search != 0;
     h->plan_parked++;
@@ -272,6 +277,11 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     rc = wait_result(true);
     if (rc != LII_OK) return rc;
   }
+  if (h->pub.on && parked_once) {  // (the launch behind the planned passes saw a parked loop and did nothing: once more, behind the passes that ended it)
+    if (h->pub.kp_idx >= 0) h->prof.kp_kind[size_t(h->pub.kp_idx)] = LII_KP_KINDS * 64;  // (lii_set_profiling(h, 3): that launch did not execute)
+    rc = publish_enqueue(h, h->d_ctrl, nullptr, false);
+    if (rc != LII_OK) return rc;
+  }
   h->unfinished_known = !h->net.comm;
   if (!h->net.comm && h->wide_enabled) {  // (the launch plan of the completions, see enqueue_pass)
     // (two scans in a row decide: a stream on which one scan in eight crosses the capacity - bench --edge - would pay for a launch that
@@ -282,7 +292,8 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     if (wide) h->wide_scans++;
   }
   h->staging_busy = false;  // the wait above covers everything enqueued before the stopping pass
-  h->scan_buf_idle = true;  // ... every launch that read or wrote the current scan buffer among it (what was enqueued behind - drained passes, the map update, a pre-armed launch on the OTHER buffer - does not touch it)
+  h->scan_buf_idle = !h->pub.on;  // ... every launch that read or wrote the current scan buffer among it (what was enqueued behind - drained passes, the map update, a pre-armed launch on the OTHER buffer - does not touch it;
+                                   // the launch and the body copy of a standing lii_publish_set order DO read it behind the stopping pass: with one, lii_scan_upload_next puts its event pair between the streams)
   const IekfResult* hr = h->h_res;
   h->have_search = true;
 #ifdef LII_SOLVE_TRACE
@@ -331,6 +342,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   if (hr->singular) return fail(h, LII_ERR_INVALID, "singular covariance / normal matrix in the device solve");
   if (hr->it < 0) return fail(h, LII_ERR_HIP, "device loop ended without a result");
   std::memcpy(state, hr->st, sizeof(lii_state));
+  publish_finish(h);  // (the clouds of this registration are the ones lii_publish_fetch serves from here on)
   h->last_pivoted_passes = 0;
   for (int q = 0; q < 16 && q < hr->it; q++) h->last_pivoted_passes += (hr->search_log[q] >> 1) & 1;
   {  // the next update's plan: this one's pattern; passes it did not reach keep their launch

@@ -5,6 +5,7 @@
 //   lii_capi_comm.cpp      the communicator of a sharded job (node-local mailbox / RCCL)
 //   lii_capi_calib.cpp     the LI_init evaluators' entry points
 //   lii_capi_imu.cpp       IMU forward propagation: lii_imu_*, lii_cv_propagate, lii_scan_register_imu, lii_scan_register_cv
+//   lii_capi_publish.cpp   the registered clouds of a scan: lii_publish_*
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -270,6 +271,30 @@ struct lii_context {
     int* d_n_poses() const { return reinterpret_cast<int*>(d_buf.get() + 2 * lii::kImuCarryDoubles); }
     double* d_state() const { return d_buf.get() + 2 * lii::kImuCarryDoubles + 8; }
   } imu;
+  // ---- the registered clouds of a scan (lii_capi_publish.cpp, lii_publish.hip): a standing order, off by default.  Nothing here
+  // exists before the first lii_publish_set; the clouds land in buffers of their own, two deep (slot `cur` is the one the
+  // registration under way writes, `have` the one of the last finished registration), aliased onto nothing else of the handle.
+  struct Publish {
+    static constexpr int kClouds = 4;  // bit k of lii_publish_opts::clouds: dense, down-sampled, effect, body
+    bool on = false;
+    int clouds = 0, to_host = 0, save_capacity = 0;
+    DevBuf<float4> d_cloud[kClouds][2];     // max_scan_points each (the ordered ones)
+    PinnedBuf<float4> h_cloud[kClouds][2];  // to_host: their pinned copies, filled on the copy stream
+    DevBuf<int> d_counts;                   // per slot: [0] points of the down-sampled cloud, [1] of the effect cloud
+    PinnedBuf<int> h_counts;                // ... and in mapped host memory (4 ints per slot)
+    DevBuf<unsigned long long> d_words;     // k_publish_world's in-launch prefix: one word per 256 down-sampled points
+    unsigned int epoch = 0;                 // launches so far
+    lii::Event ev_pub[2];                   // the slot's launch (and body copy) has completed (handle's stream)
+    lii::Event ev_copy[kClouds][2];         // the slot's cloud has arrived in h_cloud (copy stream)
+    int last_copy[2] = {-1, -1};            // the cloud whose ev_copy was recorded last for the slot (-1: no copy enqueued yet)
+    DevBuf<float4> d_save;                  // pcl_wait_save: save_capacity points (created by the first order that asks for it)
+    DevBuf<int> d_save_ctl;                 // [save_par]: append offset, [save_par ^ 1]: written by the next launch, [2]: sticky overflow flag
+    int save_par = 0;
+    int cur = 0, have = -1;
+    int n_scan_at[2] = {0, 0};              // points of the dense / body cloud in the slot
+    int clouds_at[2] = {0, 0};              // the clouds the slot holds
+    int kp_idx = -1;                        // lii_set_profiling(h, 3): the mark of the launch enqueued behind the planned passes
+  } pub;
   void* ingest = nullptr;  // lii_ingest.hip state (frames of the last driver message)
   bool ingest_sort_always = false;  // LII_INGEST_SORT=always: the ingest never leaves the time sort out (IngestRing::never_predict)
 
@@ -372,6 +397,11 @@ struct CvFeed {
 int scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report, const ImuFeed* feed,
                       const CvFeed* cv = nullptr);
 int imu_buffers(lii_handle h);  // creates lii_context::imu's buffers on first use
+// lii_capi_publish.cpp: the standing order of lii_publish_set.  publish_enqueue puts the launch (+ event, + copies to the host) for slot
+// pub.cur on the stream - guard != nullptr: behind the passes of the update under way, pose from the control block; else at `ps` -,
+// publish_finish makes that slot the one lii_publish_fetch serves.
+int publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg* ps, bool first);
+void publish_finish(lii_handle h);
 // lii_capi_comm.cpp
 void comm_drop(lii_handle h);
 void partition_refresh(lii_handle h);  // the voxel filter's view of the job after the communicator or its partition changed

@@ -81,6 +81,17 @@ struct PoseArg {
   double TLI[3];
 };
 
+// pointBodyToWorld (src/laserMapping.cpp:209-220): fp64 arithmetic, float result
+__device__ __forceinline__ void body_to_world(const PoseArg& ps, const float4 pb, float& wx, float& wy, float& wz) {
+  double bx = pb.x, by = pb.y, bz = pb.z;
+  double ix = ps.RLI[0] * bx + ps.RLI[1] * by + ps.RLI[2] * bz + ps.TLI[0];
+  double iy = ps.RLI[3] * bx + ps.RLI[4] * by + ps.RLI[5] * bz + ps.TLI[1];
+  double iz = ps.RLI[6] * bx + ps.RLI[7] * by + ps.RLI[8] * bz + ps.TLI[2];
+  wx = (float)(ps.R[0] * ix + ps.R[1] * iy + ps.R[2] * iz + ps.p[0]);
+  wy = (float)(ps.R[3] * ix + ps.R[4] * iy + ps.R[5] * iz + ps.p[1]);
+  wz = (float)(ps.R[6] * ix + ps.R[7] * iy + ps.R[8] * iz + ps.p[2]);
+}
+
 // The pose a per-point kernel works with lives in DEVICE MEMORY on every path (the control block of the device-driven loop, or the
 // handle's pose slot, which a host-driven pass uploads first) and is read in one batch of loads: one round
 // trip.  Rounds 1 - 4 also carried a pose by value in the kernel arguments and chose with `cond ? *pose : by_value`: the compiler

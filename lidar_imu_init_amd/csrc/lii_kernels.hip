@@ -529,16 +529,7 @@ __device__ __forceinline__ double pose_element(const PoseArg& ps, int t) {
   for (int e = 0; e < 3; e++) { v = t == 9 + e ? ps.p[e] : v; v = t == 21 + e ? ps.TLI[e] : v; }
   return v;
 }
-// pointBodyToWorld (src/laserMapping.cpp:209-220): fp64 arithmetic, float result
-__device__ __forceinline__ void body_to_world(const PoseArg& ps, const float4 pb, float& wx, float& wy, float& wz) {
-  double bx = pb.x, by = pb.y, bz = pb.z;
-  double ix = ps.RLI[0] * bx + ps.RLI[1] * by + ps.RLI[2] * bz + ps.TLI[0];
-  double iy = ps.RLI[3] * bx + ps.RLI[4] * by + ps.RLI[5] * bz + ps.TLI[1];
-  double iz = ps.RLI[6] * bx + ps.RLI[7] * by + ps.RLI[8] * bz + ps.TLI[2];
-  wx = (float)(ps.R[0] * ix + ps.R[1] * iy + ps.R[2] * iz + ps.p[0]);
-  wy = (float)(ps.R[3] * ix + ps.R[4] * iy + ps.R[5] * iz + ps.p[1]);
-  wz = (float)(ps.R[6] * ix + ps.R[7] * iy + ps.R[8] * iz + ps.p[2]);
-}
+// (body_to_world - pointBodyToWorld - lives in lii_device.h: lii_publish.hip uses it as well)
 // The first scan seeds the map (src/laserMapping.cpp:921-929): the down-sampled cloud in the world frame, as map points (w = 0)
 __global__ __launch_bounds__(256) void k_body_to_map(const float4* __restrict__ body, int n, PoseArg ps, float4* __restrict__ dst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -265,6 +265,30 @@ void launch_gather_live(const float4* pts, const uint2* cells, const unsigned in
 void launch_box_tomb_cells(const float4* pts, const uint2* cells, int n_entries, const float* boxes, int n_boxes, unsigned char* tomb, unsigned int* tp,
                            unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s);
 
+// the registered clouds of a scan (lii_publish.hip: k_publish_world)
+struct PublishArgs {
+  const float4* scan;       // the de-skewed scan (dense_blocks workgroups of 256 points)
+  int n_scan, dense_blocks;
+  float4* dense;            // LII_PUB_DENSE (nullptr: not ordered)
+  float4* save;             // the save buffer (nullptr: none), save_cap points,
+  int save_cap, save_par;
+  int* save_ctl;            // ... [save_par]: its append offset as this launch finds it, [save_par ^ 1]: as it leaves it, [2]: sticky "a scan did not fit"
+  const float4* body;       // the down-sampled cloud: at most n_body points, *n_body_dev of them if != nullptr
+  int n_body;
+  const int* n_body_dev;
+  float4* down;             // LII_PUB_DOWN (nullptr: not ordered)
+  const unsigned char* selected;
+  float4* effect;           // LII_PUB_EFFECT (nullptr: not ordered)
+  unsigned long long* words;  // one word per workgroup of the down-sampled cloud (prefix_below)
+  unsigned int epoch;         // the number of this launch (never 0)
+  int* counts_dev;          // [0] points of the down-sampled cloud, [1] of the effect cloud: device memory ...
+  int* counts_host;         // ... and mapped host memory
+  const IekfCtrl* guard;    // != nullptr: pose from the control block, and nothing is done unless update `seq` has stopped
+  int seq;
+  int test_late;            // LII_TEST=emit_late: every seventh workgroup of the down-sampled cloud publishes its word late (as k_vhash_emit / k_map_decide)
+};
+void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s);
+
 // rocPRIM wrappers (lii_sort.hip)
 size_t sort_temp_bytes(int max_n);
 void sort_pairs_u64(void* temp, size_t temp_bytes, const unsigned long long* kin, unsigned long long* kout,

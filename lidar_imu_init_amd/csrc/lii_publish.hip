@@ -1,0 +1,106 @@
+// libliinit_hip - the registered clouds of a scan (lii_publish_*): what laserMapping's loop hands out BEHIND the update
+// (src/laserMapping.cpp:1152-1156): publish_frame_world (:561-614, with the pcl_wait_save append of :594-613), publish_effect_world
+// (:625-636).  One launch: pointBodyToWorld (:209-220; body_to_world, lii_device.h - fp64 arithmetic, float result, no FMA contraction
+// in this unit) at the state the stopping pass left in the control block, over the de-skewed scan and over the down-sampled cloud,
+// whose selected points (laserCloudOri) are compacted in ascending index on the way.
+#include "lii_launch.h"
+
+namespace lii {
+namespace {
+
+// selected points among the 256 of down-sampled block q (every lane calls it; contains a barrier)
+__device__ __forceinline__ unsigned int publish_count(bool sel, unsigned int* s_c /*[4]*/, unsigned long long* mask_out) {
+  const unsigned long long m = __ballot(sel);
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = (unsigned int)__popcll(m);
+  __syncthreads();
+  *mask_out = m;
+  return s_c[0] + s_c[1] + s_c[2] + s_c[3];
+}
+
+}  // namespace
+
+// Workgroups [0, a.dense_blocks): the de-skewed scan -> a.dense (LII_PUB_DENSE) and / or behind the points of the save buffer;
+// the workgroups behind them: the down-sampled cloud -> a.down (LII_PUB_DOWN) and its selected points -> a.effect (LII_PUB_EFFECT).
+// guard != nullptr: the launch was enqueued behind the passes of iterated update `seq` before the host knew how it ends - the pose is
+// the control block's (IekfCtrl::st leads it), and the launch does nothing unless that update has stopped regularly (the test
+// k_map_decide makes): the host enqueues it again behind a loop it had to continue.
+// The effect cloud's places come from an in-launch prefix of the workgroups' counts (prefix_below, lii_device.h) and wavefront
+// ballots: ascending index, the same on every run - never the arrival order of a counter.
+// The save buffer's append offset ping-pongs between two words (a.save_ctl[par] is read by everybody, [par ^ 1] written by one
+// lane: no lane reads what another writes in this launch); a scan that does not fit writes nothing and raises a.save_ctl[2].
+__global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps_val) {
+  const IekfCtrl* __restrict__ guard = a.guard;
+  const PoseArg ps = load_pose(guard != nullptr, reinterpret_cast<const PoseArg*>(guard), ps_val);
+  const bool go = !guard || (guard->stop == 1 && guard->singular == 0 && guard->seq == a.seq);  // uniform over the launch
+  if ((int)blockIdx.x < a.dense_blocks) {
+    int off = 0;
+    bool fits = false;
+    if (a.save) {
+      off = a.save_ctl[a.save_par];
+      fits = go && off >= 0 && (long long)off + a.n_scan <= (long long)a.save_cap;
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.save_ctl[a.save_par ^ 1] = fits ? off + a.n_scan : off;
+        if (go && !fits) a.save_ctl[2] = 1;
+      }
+    }
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (!go || i >= a.n_scan) return;
+    const float4 p = a.scan[i];
+    float wx, wy, wz;
+    body_to_world(ps, p, wx, wy, wz);
+    const float4 o = make_float4(wx, wy, wz, p.w);
+    if (a.dense) a.dense[i] = o;
+    if (fits) a.save[(size_t)off + i] = o;
+    return;
+  }
+  if (!go) return;  // (every workgroup of the launch takes the same way: nobody waits for a word that never comes)
+  const int b = (int)blockIdx.x - a.dense_blocks;
+  const int n_mem = a.n_body_dev ? *a.n_body_dev : a.n_body;
+  const int n = n_mem < a.n_body ? n_mem : a.n_body;  // a.n_body: the launch bound (the buffers' capacity holds it)
+  const int j = b * 256 + (int)threadIdx.x;
+  const bool live = j < n;
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live) {
+    const float4 p = a.body[j];
+    float wx, wy, wz;
+    body_to_world(ps, p, wx, wy, wz);
+    o = make_float4(wx, wy, wz, p.w);
+    if (a.down) a.down[j] = o;
+  }
+  const int n_down_blocks = (int)gridDim.x - a.dense_blocks;
+  if (!a.effect) {
+    if (b == n_down_blocks - 1 && threadIdx.x == 0) { a.counts_dev[0] = n; a.counts_dev[1] = 0; a.counts_host[0] = n; a.counts_host[1] = 0; }
+    return;
+  }
+  __shared__ unsigned int s_c[4], s_r[4], s_sum[12];
+  const bool sel = live && a.selected[j] != 0;
+  unsigned long long mask;
+  const unsigned int tot = publish_count(sel, s_c, &mask);
+  // the workgroup's word goes out before it looks at anybody else's (a << 16 | b of prefix_below: a = selected, b = 0)
+  const bool hold = a.test_late != 0 && ((unsigned int)b % 7u) == 3u;  // LII_TEST=emit_late, as k_vhash_emit
+  const unsigned long long word = ((unsigned long long)a.epoch << 32) | (tot << 16);
+  if (threadIdx.x == 0 && !hold) __hip_atomic_store(a.words + b, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint2 below = prefix_below(a.words, a.epoch, b, s_sum, a.test_late != 0, [&](int q) -> unsigned int {
+    const int jq = q * 256 + (int)threadIdx.x;
+    unsigned long long mq;
+    return publish_count(jq < n && a.selected[jq] != 0, s_r, &mq) << 16;  // (nothing the count reads changes during this launch)
+  });
+  if (threadIdx.x == 0 && hold) __hip_atomic_store(a.words + b, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned int base = below.x;
+  if (b == n_down_blocks - 1 && threadIdx.x == 0) {
+    const int ne = (int)(base + tot);
+    a.counts_dev[0] = n; a.counts_dev[1] = ne;
+    a.counts_host[0] = n; a.counts_host[1] = ne;
+  }
+  for (int k = 0; k < w; k++) base += s_c[k];
+  if (sel) a.effect[base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull))] = o;
+}
+
+void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s) {
+  const int blocks = a.dense_blocks + down_blocks;
+  if (blocks <= 0) return;
+  hipLaunchKernelGGL(k_publish_world, dim3((unsigned int)blocks), dim3(256), 0, s, a, ps);
+}
+
+}  // namespace lii
