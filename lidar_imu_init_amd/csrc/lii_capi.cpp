@@ -1,5 +1,5 @@
 // libliinit_hip — C-ABI implementation (host side): life cycle of the handle, scan in / de-skew / voxel grid / downloads, profiling.
-// Declarations and the reference code each entry point replaces: include/liinit_hip.h.  Device work: lii_scan.hip, lii_kernels.hip,
+// Declarations and the reference code each entry point replaces: include/liinit_hip.h.  Device work: lii_scan.hip, lii_knn.hip, lii_fit.hip,
 // lii_vsort.hip, lii_sort.hip on ONE stream per handle.  The other entry points: lii_capi_map.cpp, lii_capi_register.cpp,
 // lii_capi_comm.cpp, lii_capi_calib.cpp (lii_context.h).
 // There is deliberately no CPU implementation of any stage here: without a usable gfx950 device

@@ -1,5 +1,5 @@
 // libliinit_hip — the device-resident local map (host side): index (re)build, in-place updates, the lii_map_* entry points and
-// lii_map_incremental.  Kernels: lii_map.hip, lii_kernels.hip (index), lii_sort.hip.  Reference: include/ikd-Tree/ikd_Tree.cpp
+// lii_map_incremental.  Kernels: lii_map.hip, lii_mapindex.hip (index), lii_sort.hip.  Reference: include/ikd-Tree/ikd_Tree.cpp
 // (Build :336-347, Add_Points :381-456, Delete_Point_Boxes :500-516), src/laserMapping.cpp:516-559 (map_incremental).
 #include "lii_context.h"
 

@@ -1,5 +1,5 @@
 // libliinit_hip — the registration loop (host side): lii_iekf_iterate / lii_iekf_update / lii_scan_register and the neighbour
-// download.  Kernels: lii_kernels.hip (k-NN, fit + reduce), lii_iekf.hip (final sum + 24-state solve), lii_scan.hip (prologue of
+// download.  Kernels: lii_knn.hip (k-NN), lii_fit.hip (fit + reduce), lii_iekf.hip (final sum + 24-state solve), lii_scan.hip (prologue of
 // lii_scan_register).  Reference: src/laserMapping.cpp:909-1134.
 #include "lii_context.h"
 #include <cstddef>

@@ -43,6 +43,11 @@ __device__ __forceinline__ void mat3t_vec(const double A[9], const double v[3], 
   for (int r = 0; r < 3; r++) o[r] = A[r] * v[0] + A[3 + r] * v[1] + A[6 + r] * v[2];
 }
 
+// order-preserving float -> uint map (so that integer atomics give float min / max)
+__device__ __forceinline__ unsigned int f2ord(float f) {
+  unsigned int u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 // order-preserving uint -> float (the inverse of the map the min / max reductions of a scan use)
 __device__ __forceinline__ float ord2f(unsigned int o) {
   unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
@@ -202,15 +207,7 @@ struct WinKeep {
   const unsigned long long* key_of_id;
   int x0, y0, z0, nx, ny, nz;
 };
-__device__ __forceinline__ long long win_index_of_entry(const WinKeep& w, unsigned int e) {  // -1: outside the window
-  const unsigned long long k = w.key_of_id[e >> 9];
-  const int bb = kCellBias >> kCoarseShift;
-  const int bx = (int)(k & 0x3FFFF) - bb, by = (int)((k >> 18) & 0x3FFFF) - bb, bz = (int)((k >> 36) & 0x3FFFF) - bb;
-  const unsigned int l = e & 511u;
-  const unsigned int ux = (unsigned)(bx * 8 + (int)(l & 7u) - w.x0), uy = (unsigned)(by * 8 + (int)((l >> 3) & 7u) - w.y0), uz = (unsigned)(bz * 8 + (int)(l >> 6) - w.z0);
-  if (ux < (unsigned)w.nx && uy < (unsigned)w.ny && uz < (unsigned)w.nz) return ((long long)uz * w.ny + uy) * w.nx + ux;
-  return -1;
-}
+// (win_index_of_entry - where a cell entry sits in the window - is in lii_grid.h)
 
 struct RegistrationBuffers {
   const float4* body;   // down-sampled LiDAR-frame points (x,y,z,t)

@@ -72,10 +72,6 @@ __device__ __forceinline__ T rd(const uint8_t* p) {  // unaligned-safe field rea
   memcpy(&v, p, sizeof(T));
   return v;
 }
-__device__ __forceinline__ unsigned int ford(float f) {  // order-preserving float -> uint
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct Pc2Arg {
   lii_pc2_fields f;
@@ -221,7 +217,7 @@ __global__ void k_ingest_compact(const float4* __restrict__ pts, const unsigned 
   unsigned int kkey = 0xFFFFFFFFu, kidx = 0u;  // padding beyond the kept count sorts last
   if (keep[i]) {
     const unsigned int r = rank[i] - 1u;
-    key[r] = ford(pts[i].w);
+    key[r] = f2ord(pts[i].w);
     idx[r] = (unsigned)i;
   }
   // slots [kept, n) are filled by the tail threads so that the sort can run over the fixed length n

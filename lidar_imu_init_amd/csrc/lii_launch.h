@@ -1,4 +1,4 @@
-// Host-callable launchers of the kernels in lii_kernels.hip / lii_sort.hip (internal; not the C-ABI).
+// Host-callable launchers of the library's kernels, grouped by the unit that defines them (internal; not the C-ABI).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -31,7 +31,7 @@ void ingest_destroy(void* slot);  // lii_ingest.hip
 struct UndistArgH { double endR[9], endp[3], RLI[9], TLI[3]; };
 struct CvArgH { double omega[3], vel[3], endR[9]; };
 
-// map index
+// map index (lii_mapindex.hip)
 void launch_map_keys(const float4* pts, int n, float inv_cs, unsigned long long* keys, unsigned int* idx, hipStream_t s);
 void launch_map_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
 void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s);  // pointBodyToWorld over a cloud: dst[i] = (world xyz, 0)
@@ -41,7 +41,7 @@ void launch_win_bbox(const BlockEntry* blocks, unsigned int cap, unsigned int* b
 void launch_win_fill(const BlockEntry* blocks, unsigned int cap, const uint2* cells, uint2* win, const int org[3], const int dim[3], hipStream_t s);
 void launch_cells_fill(const unsigned long long* keys, const unsigned int* ranks, int n, BlockEntry* blocks,
                        unsigned int block_mask, uint2* cells, unsigned long long* key_of_id, hipStream_t s);
-// registration
+// registration: the search launch (lii_knn.hip)
 // (`pose`: device memory on every path - a host-driven pass uploads it first)
 // epoch: the number of this search launch (> 0, RegistrationBuffers::flag_*) and of the fit launch behind it; 0: no list of unfinished queries
 // ev_start / ev_stop (both or none): the launch's own dispatch carries the two events (hipExtLaunchKernelGGL: the time stamps of the
@@ -49,14 +49,16 @@ void launch_cells_fill(const unsigned long long* keys, const unsigned int* ranks
 void launch_knn(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
                 const IekfCtrl* ctrl, int forced, double* search_pose_out, hipStream_t s, int epoch,
                 hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// registration: the fit launch and the completion of unfinished searches (lii_fit.hip)
 #ifdef LII_FALLBACK_TRACE
-void fb_trace_read(unsigned long long out[32]);  // (measurement builds: the completion's phase sums, lii_kernels.hip)
+void fb_trace_read(unsigned long long out[32]);  // (measurement builds: the completion's phase sums)
 #endif
 void launch_knn_complete(const GridView& g, const RegistrationBuffers& rb, hipStream_t s);
 void launch_complete_listed(const GridView& g, const RegistrationBuffers& rb, const IekfCtrl* ctrl, int forced, hipStream_t s, int epoch);  // (k_complete_listed: behind search launch `epoch`)
 void launch_fit_reduce(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
                        const IekfCtrl* ctrl, int forced, int imu_en, double plane_thr, double rinv, hipStream_t s, int epoch);
 void launch_reduce91(const RegistrationBuffers& rb, double* out91, const IekfCtrl* ctrl, int forced, hipStream_t s, int epoch);  // epoch: of the fit launch whose columns it sums
+// final sum + 24-state solve, the ranks' sum of the normal equations (lii_iekf.hip)
 void launch_reduce_solve(const RegistrationBuffers& rb, unsigned long long* gran, IekfCtrl* c, IekfResult* res, const MailboxView& mb,
                          hipStream_t s, int epoch);
 void launch_mailbox_allreduce(double* out91, const MailboxView& mb, hipStream_t s);
@@ -94,14 +96,14 @@ void launch_lists_exchange(const GatherView& gv, const float4* src_add, const fl
 void mailbox_close(MailboxHost* m);
 void launch_loop_resume(IekfCtrl* c, unsigned int plan_mask, hipStream_t s);
 void launch_iekf_solve(IekfCtrl* c, const double* ne, IekfResult* res, hipStream_t s);
-int register_blocks(int n);
-// undistortion
+int register_blocks(int n);  // (lii_fit.hip)
+// undistortion (lii_scan.hip)
 void launch_time_extent(const float4* pts, int n, unsigned long long* extent, unsigned long long* extent_next, float4* copy_to,
                         const void* ctrl_src, void* ctrl_dst, size_t ctrl_bytes, hipStream_t s);
 // the time sort of a scan: key[i] = order-preserving image of t (-0.0 as +0.0), idx[i] = i; then sort_pairs_u32; then dst[i] = src[idx[i]]
 void launch_sort_keys(const float4* pts, int n, unsigned int* key, unsigned int* idx, hipStream_t s);
 void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
-// voxel grid
+// voxel grid (lii_scan.hip)
 void launch_voxel_minmax(const float4* pts, int n, unsigned int* mm, unsigned int* mm_next, hipStream_t s);
 void launch_voxel_keys(const float4* pts, int n, const unsigned int* mm, const unsigned int* bbox_rows, int n_rows, float leaf,
                        unsigned long long* keys, unsigned int* pcl_keys, int* filtered_dev,
@@ -222,7 +224,7 @@ struct CvPropArgs {
 };
 void launch_imu_propagate(const ImuPropArgs& a, hipStream_t s);
 void launch_cv_propagate(const CvPropArgs& a, hipStream_t s);
-// calibration
+// calibration (lii_li_init_dev.hip)
 void launch_calib_eval(int stage, const double* imu, const double* lidar, int n, const double* params, double* out,
                        hipStream_t s);
 

@@ -1,4 +1,4 @@
-// SURVEY.md section 8(f)4 on the device: the two pieces of the LI-Init conditioning chain with real arithmetic volume,
+// LI-Init on the device.  SURVEY.md section 8(f)4: the two pieces of the LI-Init conditioning chain with real arithmetic volume,
 //   k_zero_phase   LI_Init::zero_phase_filt = Butter_filt forward, reversed, again, reversed (include/LI_init/LI_init.cpp:260-315;
 //                  6th-order Butterworth, coefficients LI_init.h:218-224 incl. the asymmetric Coeff_b[4] = 0.0011; 60-sample
 //                  reflection padding; recursion from index 7, stopping 60 before the end - SURVEY.md Appendix A8): the four
@@ -8,7 +8,8 @@
 //   k_xcorr        LI_Init::xcorr_temporal_init (:160-193): O(N^2) cross-correlation of the |omega| series; one lane per lag
 //                  (2N - 1 lanes), each summing its products in the host's index order; the first maximum in lag order wins,
 //                  as the reference's strict `>` does.
-// Both exist so that the calibration can be re-run on device-resident buffers during accumulation without a round trip of the
+//   k_calib_eval   include/LI_init/LI_init.h:91-205 residuals + analytic Jacobians of the three calibration stages (lii_calib.cpp drives them)
+// The first two exist so that the calibration can be re-run on device-resident buffers during accumulation without a round trip of the
 // sequences; at N_s ~ 10^3 the filter is latency (a 1 000-step dependent chain), the correlation is where the device wins.
 #include <hip/hip_runtime.h>
 
@@ -124,6 +125,121 @@ __global__ __launch_bounds__(256) void k_xcorr_argmax(const double* __restrict__
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// LI-Init residual / Jacobian evaluators (include/LI_init/LI_init.h:91-205).  Records are 22 doubles:
+// rot_end[9], ang_vel[3], linear_vel[3], ang_acc[3], linear_acc[3], timestamp.
+// Tangent convention R <- Exp(delta) R  (Appendix B of SURVEY.md):
+//   stage 1/2: r = R w_L - w_I [- (dT + t_d) a_I + b_g];  dr/ddelta = -[R w_L]x, dr/db_g = I, dr/dt_d = -alpha_I
+//   stage 3:   r = R_LL0 R_LI^T a_I - R_LL0 b_a + R_GL0 g - a_L - R_LL0 ([w]x^2 + [alpha]x) T_IL
+//              dr/ddelta_G = -[R_GL0 g]x, dr/db_a = -R_LL0, dr/dT_IL = -R_LL0 ([w]x^2 + [alpha]x)
+// Output per block: dof*dof + dof + 1 doubles (J^T J row-major, J^T r, 0.5 sum r^2), reduced on one block.
+
+template <int STAGE>
+__global__ __launch_bounds__(256) void k_calib_eval(const double* __restrict__ imu, const double* __restrict__ lidar, int n,
+                                                    const double* __restrict__ params, double* __restrict__ out) {
+  constexpr int DOF = STAGE == 1 ? 3 : (STAGE == 2 ? 7 : 9);
+  constexpr int NOUT = DOF * DOF + DOF + 1;
+  __shared__ double sh[256];
+  double acc[NOUT];
+#pragma unroll
+  for (int k = 0; k < NOUT; k++) acc[k] = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const double* I = imu + 22 * (size_t)i;
+    const double* L = lidar + 22 * (size_t)i;
+    double r[3];
+    double J[3][DOF];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < DOF; b++) J[a][b] = 0;
+    if (STAGE == 1 || STAGE == 2) {
+      const double* R = params;
+      double Rw[3];
+      mat3_vec(R, L + 9, Rw);
+#pragma unroll
+      for (int a = 0; a < 3; a++) r[a] = Rw[a] - I[9 + a];
+      // -[Rw]x
+      J[0][1] = Rw[2]; J[0][2] = -Rw[1];
+      J[1][0] = -Rw[2]; J[1][2] = Rw[0];
+      J[2][0] = Rw[1]; J[2][1] = -Rw[0];
+      if (STAGE == 2) {
+        const double* bg = params + 9;
+        double td = params[12];
+        double dT = L[21] - I[21];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+          r[a] = r[a] - (dT + td) * I[15 + a] + bg[a];
+          J[a][(3 + a) % DOF] = 1.0;
+          J[a][6 % DOF] = -I[15 + a];
+        }
+      }
+    } else {
+      const double* RG = params;        // R_GL0
+      const double* ba = params + 9;    // bias_aL
+      const double* Til = params + 12;  // T_IL
+      const double* RLI = params + 15;  // R_LI (fixed)
+      const double* RLL0 = L;           // rot_end
+      const double g[3] = {0, 0, -9.81};  // STD_GRAV (LI_init.h:27)
+      double aI_L[3], t1[3], Rg[3];
+      mat3t_vec(RLI, I + 18, aI_L);  // R_LI^T a_I
+      mat3_vec(RLL0, aI_L, t1);      // R_LL0 R_LI^T a_I
+      mat3_vec(RG, g, Rg);
+      const double* w = L + 9;
+      const double* al = L + 15;
+      double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+      double A[9] = {0, -al[2], al[1], al[2], 0, -al[0], -al[1], al[0], 0};
+      double M[9], RM[9];
+      mat3_mul(W, W, M);
+#pragma unroll
+      for (int e = 0; e < 9; e++) M[e] += A[e];
+      mat3_mul(RLL0, M, RM);
+      double Rb[3], RMt[3];
+      mat3_vec(RLL0, ba, Rb);
+      mat3_vec(RM, Til, RMt);
+#pragma unroll
+      for (int a = 0; a < 3; a++) r[a] = t1[a] - Rb[a] + Rg[a] - L[18 + a] - RMt[a];
+      J[0][1] = Rg[2]; J[0][2] = -Rg[1];
+      J[1][0] = -Rg[2]; J[1][2] = Rg[0];
+      J[2][0] = Rg[1]; J[2][1] = -Rg[0];
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+          J[a][(3 + b) % DOF] = -RLL0[3 * a + b];
+          J[a][(6 + b) % DOF] = -RM[3 * a + b];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < DOF; a++) {
+#pragma unroll
+      for (int b = 0; b < DOF; b++) acc[a * DOF + b] += J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b];
+      acc[DOF * DOF + a] += J[0][a] * r[0] + J[1][a] * r[1] + J[2][a] * r[2];
+    }
+    acc[DOF * DOF + DOF] += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  }
+  // fixed-order block reduction (tree over 256 threads), one output at a time
+#pragma unroll
+  for (int k = 0; k < NOUT; k++) {
+    sh[threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) out[k] = sh[0];
+    __syncthreads();
+  }
+}
+template __global__ void k_calib_eval<1>(const double*, const double*, int, const double*, double*);
+template __global__ void k_calib_eval<2>(const double*, const double*, int, const double*, double*);
+template __global__ void k_calib_eval<3>(const double*, const double*, int, const double*, double*);
+void launch_calib_eval(int stage, const double* imu, const double* lidar, int n, const double* params, double* out,
+                       hipStream_t s) {
+  if (stage == 1) hipLaunchKernelGGL(k_calib_eval<1>, dim3(1), dim3(256), 0, s, imu, lidar, n, params, out);
+  else if (stage == 2) hipLaunchKernelGGL(k_calib_eval<2>, dim3(1), dim3(256), 0, s, imu, lidar, n, params, out);
+  else hipLaunchKernelGGL(k_calib_eval<3>, dim3(1), dim3(256), 0, s, imu, lidar, n, params, out);
+}
 }  // namespace lii
 
 using namespace lii;

@@ -21,62 +21,16 @@
 #include <cstring>
 #include <math.h>
 
-#include "lii_device.h"
+#include "lii_grid.h"
 #include "lii_launch.h"
 
 namespace lii {
 
 namespace {
-constexpr int kBias = 1 << 20;
-constexpr int kCells = 512;
+// a voxel key that no voxel has: the free slot of the add-hash (AddHash::key), and "no group here" in the folds (NOT a slot of the block
+// table: that is kEmptyKey)
 constexpr unsigned long long kInvalidKey = ~0ull;
 
-__device__ __forceinline__ unsigned int d_hash_block(int bx, int by, int bz) {
-  return (__umul24((unsigned)bx, 7919u * 1021u) ^ __umul24((unsigned)by, 104729u * 13u) ^ __umul24((unsigned)bz, 1299709u)) * 2654435761u;
-}
-__device__ __forceinline__ unsigned long long d_pack_block(int bx, int by, int bz) {
-  return ((unsigned long long)(unsigned)bz << 36) | ((unsigned long long)(unsigned)by << 18) | (unsigned long long)(unsigned)bx;
-}
-// FRESH: blocks may be CREATED beside this lookup, in the same launch (k_add_fold8<true, true>: the inserts' cells ride in the fold).  A block
-// whose key is there and whose id is not yet (pad == 0; k_ins_cells' creator stores key -> id -> pad, the pad with release order) is a block
-// of this very launch: it holds no point yet - empty, like a block that is not in the table.  id and pad are ONE aligned 8-byte word: a copy
-// of the entry that shows pad = 1 shows the id that was stored before it, however old the copy of the key beside it is.
-template <bool FRESH = false>
-__device__ __forceinline__ uint2 d_cell_range(const GridView& g, int ix, int iy, int iz) {
-  const int bb = kBias >> kCoarseShift;
-  const int bx = (ix >> kCoarseShift) + bb, by = (iy >> kCoarseShift) + bb, bz = (iz >> kCoarseShift) + bb;
-  const unsigned long long bk = d_pack_block(bx, by, bz);
-  unsigned int sl = d_hash_block(bx, by, bz) & g.block_mask;
-  while (true) {
-    BlockEntry e = g.blocks[sl];
-    if (e.key == bk) {
-      if (FRESH && e.pad == 0u) return make_uint2(0u, 0u);
-      const unsigned local = (((unsigned)iz & 7u) << 6) | (((unsigned)iy & 7u) << 3) | ((unsigned)ix & 7u);
-      return g.cells[(size_t)e.id * kCells + local];
-    }
-    if (e.key == kEmptyKey) return make_uint2(0u, 0u);
-    sl = (sl + 1) & g.block_mask;
-  }
-}
-// the same lookup, also returning the cell's entry index (block id * 512 + local cell; -1: the block is not in the table)
-template <bool FRESH = false>
-__device__ __forceinline__ uint2 d_cell_range_e(const GridView& g, int ix, int iy, int iz, long long& entry) {
-  const int bb = kBias >> kCoarseShift;
-  const int bx = (ix >> kCoarseShift) + bb, by = (iy >> kCoarseShift) + bb, bz = (iz >> kCoarseShift) + bb;
-  const unsigned long long bk = d_pack_block(bx, by, bz);
-  unsigned int sl = d_hash_block(bx, by, bz) & g.block_mask;
-  while (true) {
-    BlockEntry e = g.blocks[sl];
-    if (e.key == bk) {
-      if (FRESH && e.pad == 0u) { entry = -1; return make_uint2(0u, 0u); }
-      const unsigned local = (((unsigned)iz & 7u) << 6) | (((unsigned)iy & 7u) << 3) | ((unsigned)ix & 7u);
-      entry = (long long)e.id * kCells + local;
-      return g.cells[(size_t)entry];
-    }
-    if (e.key == kEmptyKey) { entry = -1; return make_uint2(0u, 0u); }
-    sl = (sl + 1) & g.block_mask;
-  }
-}
 // A cell that loses or gains points goes on the work list of the in-place update (see "in-place map update" below): top bit of
 // tp[e] = listed, low bits = inserts pending for it.
 __device__ __forceinline__ void touch_cell(unsigned int* __restrict__ tp, unsigned int* __restrict__ work, int* __restrict__ ctr, unsigned int work_cap,
@@ -92,11 +46,6 @@ __device__ __forceinline__ void touch_cell(unsigned int* __restrict__ tp, unsign
     const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
     if (at < work_cap) work[at] = e; else ctr[kMapCtrOverflow] = 1;
   }
-}
-// calc_dist — float32, the reference's evaluation order, no FMA (ikd_Tree.cpp:1273-1277, laserMapping.cpp:152-155)
-__device__ __forceinline__ float d_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-  float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 // Thousands of lanes adding to the same counter serialise at ~2.4 ns each (12 us per update for the live-point counter alone):
 // the lanes of a wavefront add up first and issue ONE atomic.
@@ -164,7 +113,7 @@ __device__ __forceinline__ MapDecision map_decide_point(const RegistrationBuffer
       const float mx = (float)(floor(wx / fsd) * fsd + 0.5 * fsd);
       const float my = (float)(floor(wy / fsd) * fsd + 0.5 * fsd);
       const float mz = (float)(floor(wz / fsd) * fsd + 0.5 * fsd);
-      const float dist = d_dist2(wx, wy, wz, mx, my, mz);
+      const float dist = dist2_ref(wx, wy, wz, mx, my, mz);
       const float4 n0 = rb.nbr[i];
       if ((double)fabsf(n0.x - mx) > 0.5 * fsd && (double)fabsf(n0.y - my) > 0.5 * fsd && (double)fabsf(n0.z - mz) > 0.5 * fsd) {
         d.fn = 1;  // PointNoNeedDownsample (:536-541)
@@ -174,7 +123,7 @@ __device__ __forceinline__ MapDecision map_decide_point(const RegistrationBuffer
 #pragma unroll
           for (int k = 0; k < kMatch; k++) {
             const float4 q = rb.nbr[(size_t)k * rb.cap + i];
-            if (need_add && d_dist2(q.x, q.y, q.z, mx, my, mz) < dist) need_add = false;
+            if (need_add && dist2_ref(q.x, q.y, q.z, mx, my, mz) < dist) need_add = false;
           }
         }
         d.fa = need_add ? 1u : 0u;
@@ -207,11 +156,11 @@ __device__ __forceinline__ void add_box(const float4 p, float ds, float (&bmin)[
 // one batch point into the table: its voxel's slot (found or created) and its bid for the voxel's minimum; 0xFFFFFFFF: a non-finite point
 __device__ __forceinline__ unsigned int addh_insert_one(const float4 p, unsigned int index, float ds, const AddHash& tb) {
   const int vx = (int)floorf(p.x / ds), vy = (int)floorf(p.y / ds), vz = (int)floorf(p.z / ds);  // (:390-395, float arithmetic)
-  const unsigned long long key = ((unsigned long long)(unsigned)(vz + kBias) << 42) | ((unsigned long long)(unsigned)(vy + kBias) << 21) |
-                                 (unsigned long long)(unsigned)(vx + kBias);
+  const unsigned long long key = ((unsigned long long)(unsigned)(vz + kCellBias) << 42) | ((unsigned long long)(unsigned)(vy + kCellBias) << 21) |
+                                 (unsigned long long)(unsigned)(vx + kCellBias);
   float bmin[3], bmax[3], mid[3];
   add_box(p, ds, bmin, bmax, mid);
-  const float d = d_dist2(p.x, p.y, p.z, mid[0], mid[1], mid[2]);
+  const float d = dist2_ref(p.x, p.y, p.z, mid[0], mid[1], mid[2]);
   if (!(d == d)) return 0xFFFFFFFFu;  // (a non-finite point takes no part)
   unsigned int slot = ah_hash(key) & tb.mask;
   while (true) {
@@ -305,8 +254,8 @@ __global__ void k_add_keys(const float4* __restrict__ pts, int n, const int* __r
     const float4 p = pts[i];
     // floor(PointToAdd[i].x / downsample_size): float arithmetic (:390-395)
     const int vx = (int)floorf(p.x / ds), vy = (int)floorf(p.y / ds), vz = (int)floorf(p.z / ds);
-    key = ((unsigned long long)(unsigned)(vz + kBias) << 42) | ((unsigned long long)(unsigned)(vy + kBias) << 21) |
-          (unsigned long long)(unsigned)(vx + kBias);
+    key = ((unsigned long long)(unsigned)(vz + kCellBias) << 42) | ((unsigned long long)(unsigned)(vy + kCellBias) << 21) |
+          (unsigned long long)(unsigned)(vx + kCellBias);
   }
   keys[i] = key;
   idx[i] = (unsigned)i;
@@ -332,10 +281,6 @@ __global__ void k_addh_insert(const float4* __restrict__ pts, int n, const int* 
   if (!n_dev || i < *n_dev) slot = addh_insert_one(pts[i], (unsigned int)i, ds, tb);
   tb.slot_of[i] = slot;
 }
-
-namespace {
-__device__ __forceinline__ unsigned int m_hash_block(int bx, int by, int bz) { return d_hash_block(bx, by, bz); }
-}  // namespace
 
 // An insert that found no room (block tables full, no slack left and no tail to move the cell to) is kept for the host: the
 // next read of the counters rebuilds the index with more room and inserts these points again.
@@ -364,10 +309,10 @@ __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __res
   const unsigned int mask = a.mask, tables_cap = a.tables_cap;
   int* ctr = a.ctr;
   const int ix = (int)floorf(p.x * a.inv_cs), iy = (int)floorf(p.y * a.inv_cs), iz = (int)floorf(p.z * a.inv_cs);
-  const int bb = kBias >> kCoarseShift;
+  const int bb = kCellBias >> kCoarseShift;
   const int bx = (ix >> kCoarseShift) + bb, by = (iy >> kCoarseShift) + bb, bz = (iz >> kCoarseShift) + bb;
-  const unsigned long long bk = d_pack_block(bx, by, bz);
-  unsigned int sl = m_hash_block(bx, by, bz) & mask;
+  const unsigned long long bk = pack_block(bx, by, bz);
+  unsigned int sl = hash_block(bx, by, bz) & mask;
   long long id = -1;
   // One loop, no waiting inside it: a lane that finds its block's key but not yet its id (another lane - possibly of this very
   // wavefront - is creating the block) goes round the loop again on the SAME slot.  The lanes of a wavefront execute the loop
@@ -420,7 +365,7 @@ __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __res
     drop_point(a.dropped, a.drop_cap, ctr, p);
     return;
   }
-  const unsigned int e = (unsigned int)id * kCells + ((((unsigned)iz & 7u) << 6) | (((unsigned)iy & 7u) << 3) | ((unsigned)ix & 7u));
+  const unsigned int e = (unsigned int)id * kBlockCells + local_cell(ix, iy, iz);
   *ins_e_out = e;
   touch_cell(a.tp, a.work, ctr, a.work_cap, e);
   atomicAdd(&a.tp[e], 1u);
@@ -441,7 +386,7 @@ __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __res
 // CELLS (round 6; HASHED only): what k_ins_cells did in a launch of its own behind the fold rides here - a leader whose batch point stays
 // finds / creates that point's cell at once (fc.ins_e[i]; every other position of the list gets 0xFFFFFFFF), and the workgroups behind the
 // fold's own (blockIdx >= fc.fold_blocks) do the same for the second insert list, which does not pass through the fold.  Cell lookups of
-// such a launch run beside block creations: d_cell_range<FRESH>.
+// such a launch run beside block creations: cell_range<FRESH>.
 struct FoldCells {
   InsCells a;
   unsigned int* ins_e;     // per position of the folded list
@@ -513,7 +458,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
   long long my_entry = -1;
   if (g.n_pts > 0) {
     if (mine) {
-      r = d_cell_range_e<CELLS>(g, c0[0] + dx, c0[1] + dy, c0[2] + dz, my_entry);
+      r = cell_range<CELLS>(g, c0[0] + dx, c0[1] + dy, c0[2] + dz, my_entry);
       for (unsigned int j0 = r.x; j0 < r.y; j0 += 4u) {  // four candidates per trip, loaded together; visited in index order
         float4 q4[4];
 #pragma unroll
@@ -523,7 +468,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
           const float4 q = q4[u];
           if (j0 + (unsigned)u < r.y && bmin[0] <= q.x && bmax[0] > q.x && bmin[1] <= q.y && bmax[1] > q.y && bmin[2] <= q.z && bmax[2] > q.z) {
             n0++;
-            const float d = d_dist2(q.x, q.y, q.z, mid[0], mid[1], mid[2]);
+            const float d = dist2_ref(q.x, q.y, q.z, mid[0], mid[1], mid[2]);
             if (d < bestd) { bestd = d; best = (int)(j0 + (unsigned)u); }
           }
         }
@@ -532,12 +477,12 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
       for (int cz = c0[2]; cz <= c1[2]; cz++)
         for (int cy = c0[1]; cy <= c1[1]; cy++)
           for (int cx = c0[0]; cx <= c1[0]; cx++) {
-            const uint2 rr = d_cell_range<CELLS>(g, cx, cy, cz);
+            const uint2 rr = cell_range<CELLS>(g, cx, cy, cz);
             for (unsigned int j = rr.x; j < rr.y; j++) {
               const float4 q = g.pts[j];
               if (bmin[0] <= q.x && bmax[0] > q.x && bmin[1] <= q.y && bmax[1] > q.y && bmin[2] <= q.z && bmax[2] > q.z) {
                 n0++;
-                const float d = d_dist2(q.x, q.y, q.z, mid[0], mid[1], mid[2]);
+                const float d = dist2_ref(q.x, q.y, q.z, mid[0], mid[1], mid[2]);
                 if (d < bestd) { bestd = d; best = (int)j; }
               }
             }
@@ -563,7 +508,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
   if (HASHED) {
     // the leader IS the batch point that stays if a batch point does; E stays if it is strictly closer (and then every other
     // existing in-box point goes); a lone E that stays leaves the voxel untouched
-    const float dp = d_dist2(p0.x, p0.y, p0.z, mid[0], mid[1], mid[2]);
+    const float dp = dist2_ref(p0.x, p0.y, p0.z, mid[0], mid[1], mid[2]);
     const bool old_wins = (n0 > 0) && (bestd < dp);
     ev = !old_wins || n0 > 1;
     cur_new = !old_wins;
@@ -582,7 +527,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
     float cx_ = 0, cy_ = 0, cz_ = 0, cd = 0;
     unsigned int n_events = 0;
     auto replay = [&](const float4 p) {
-      const float dp = d_dist2(p.x, p.y, p.z, mid[0], mid[1], mid[2]);
+      const float dp = dist2_ref(p.x, p.y, p.z, mid[0], mid[1], mid[2]);
       if (!ev) {
         const bool old_wins = (n0 > 0) && (bestd < dp);
         float rx = p.x, ry = p.y, rz = p.z;
@@ -632,7 +577,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
       tomb[best] = 1;
       const float4 q = g.pts[best];
       long long e;
-      (void)d_cell_range_e<CELLS>(g, (int)floorf(q.x * g.inv_cs), (int)floorf(q.y * g.inv_cs), (int)floorf(q.z * g.inv_cs), e);
+      (void)cell_range<CELLS>(g, (int)floorf(q.x * g.inv_cs), (int)floorf(q.y * g.inv_cs), (int)floorf(q.z * g.inv_cs), e);
       if (e >= 0) touch_cell(tp, work, ctr, work_cap, (unsigned int)e);
     }
   } else if (n0 > 1) {
@@ -648,7 +593,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
         for (int cy = c0[1]; cy <= c1[1]; cy++)
           for (int cx = c0[0]; cx <= c1[0]; cx++) {
             long long e;
-            const uint2 rr2 = d_cell_range_e<CELLS>(g, cx, cy, cz, e);
+            const uint2 rr2 = cell_range<CELLS>(g, cx, cy, cz, e);
             bool any = false;
             for (unsigned int j = rr2.x; j < rr2.y; j++) {
               const float4 q = g.pts[j];

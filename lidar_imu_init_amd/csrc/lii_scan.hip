@@ -17,11 +17,6 @@ namespace lii {
 
 // ------------------------------------------------------------------------------------------------
 // undistortion
-// order-preserving float -> uint map (so that integer atomics give float min / max)
-__device__ __forceinline__ unsigned int f2ord(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // extent[0] = (ord(t_min) << 32) | index of the first point with that time ; extent[1] = ord(t_max)
 // grid-stride over a small grid, wave shuffle + LDS reduction, ONE pair of atomics per block
 // copy_to != nullptr: the scan is adopted from a caller-owned device buffer on the way (lii_scan_set_device) - one pass
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(256) void k_sort_gather(const float4* __restrict__ 
   const unsigned int j = idx[i];
   if (j < (unsigned int)n) dst[i] = src[j];  // (idx is a permutation of 0 .. n - 1: the sort only moves what k_sort_keys wrote)
 }
-// (ord2f and exp_so3 - Exp(ang_vel, dt), include/so3_math.h:37-59 - live in lii_device.h: lii_imu.hip shares them)
+// (f2ord, ord2f and exp_so3 - Exp(ang_vel, dt), include/so3_math.h:37-59 - live in lii_device.h: lii_imu.hip shares them)
 struct UndistArg {
   double endR[9], endp[3], RLI[9], TLI[3];
 };
