@@ -189,6 +189,37 @@ int lii_downsample(lii_handle h, float leaf, int32_t* n_down, int32_t* filtered)
 int lii_downsample_skip(lii_handle h, int32_t* n_down);
 int lii_scan_download(lii_handle h, int32_t which, float* out_float4, int32_t capacity, int32_t* n);
 
+/* ---------------------------------------------------------------- the intensity channel (optional, off until asked for)
+ * What the reference hands on with every point (pointBodyToWorld copies it, src/laserMapping.cpp:219; PCL's VoxelGrid averages it with
+ * every other field) travels BESIDE the float4 clouds: one float per point in buffers of the handle's own, created by the first call that
+ * attaches intensities.  Every stage that reorders, drops, merges or republishes points carries it: the ingest's filters, sort and cut,
+ * the time sort (lii_scan_sort, scan_sorted = 2), the voxel filter in all its forms (per output voxel PCL's centroid: the members'
+ * intensities added in input order from 0.f, divided by the count - the arithmetic of x, y, z, t; the unfiltered pass-through and
+ * lii_downsample_skip copy), and lii_publish_* (LII_PUB_INTENSITY).  A scan without intensities enqueues the launches and gives the bits it
+ * did before the channel existed.
+ *   lii_scan_intensity_upload      attaches intensities to the CURRENT scan from the caller's AoS (pcl::PointXYZINormal: stride 48, offset 32).
+ *                                  n must be the current scan's point count (else LII_ERR_INVALID); no scan: LII_ERR_STATE.
+ *   lii_scan_intensity_set_device  the same from device memory (n floats, copied on the handle's stream; the caller's buffer is only read).
+ *   lii_ingest_set_intensity       a STANDING ORDER on the ingest (off by default): every lii_ingest_pcl2 / lii_ingest_livox / *_begin call
+ *                                  from then on also forms the intensity of every frame point (one launch behind the cut), and
+ *                                  lii_frame_select makes the frame's intensities those of the current scan.  VELO, OUSTER and PANDAR hold a
+ *                                  float, copied bit for bit; ROBOSENSE `intensity` and Livox `reflectivity` are uint8, converted to float
+ *                                  (src/preprocess.cpp:69,149,198,222,262); L515 has no such field: 0.0f.
+ *   lii_scan_intensity_download    which = 0: the current scan's intensities in the scan's current order; which = 1: the down-sampled
+ *                                  cloud's, in the order lii_scan_download(h, 1) returns its points (PCL's).  Nothing attached (for 1: not
+ *                                  attached when the voxel filter ran): LII_ERR_STATE.  out may be NULL (*n only).
+ * LIFETIME.  Intensities belong to the current scan, and whatever REPLACES the current scan detaches them: lii_scan_upload,
+ * lii_scan_set_device, lii_scan_advance (a scan that arrived through lii_scan_upload_next has none), lii_frame_select of a frame ingested
+ * without the order, and a job that adopts lii_scan_job::scan_dev.  A caller registering a device-resident scan WITH intensity hands it over
+ * with lii_scan_set_device + lii_scan_intensity_set_device and leaves job->scan_dev NULL; jobs with scan_dev / next_scan_dev - and with them
+ * the pre-armed prologue - know nothing of the channel.  De-skew and sort keep them (the same points, moved).
+ * With a communicator attached, or under LII_TEST=host_solve, the attaching calls (and lii_ingest_set_intensity(h, 1)) return LII_ERR_STATE.
+ * Like every entry point they end a pre-armed launch first. */
+int lii_scan_intensity_upload(lii_handle h, const void* points, int32_t n, int32_t stride_bytes, int32_t intensity_offset_bytes);
+int lii_scan_intensity_set_device(lii_handle h, const void* dev_float, int32_t n);
+int lii_ingest_set_intensity(lii_handle h, int32_t on);
+int lii_scan_intensity_download(lii_handle h, int32_t which, float* out, int32_t capacity, int32_t* n);
+
 /* ---------------------------------------------------------------- ingest: driver message -> device-resident scan frames
  * lii_ingest_pcl2  <- Preprocess::process_cut_frame_pcl2  (src/preprocess.cpp:115-335; callers laserMapping.cpp:363-372)
  * lii_ingest_livox <- Preprocess::process_cut_frame_livox (src/preprocess.cpp:50-113;  callers laserMapping.cpp:326-336)
@@ -204,7 +235,8 @@ int lii_scan_download(lii_handle h, int32_t which, float* out_float4, int32_t ca
  * `data` is sensor_msgs/PointCloud2::data (or the CustomPoint array) as received; the field offsets are what
  * pcl::fromROSMsg derives from msg->fields for the point structs of src/preprocess.h:35-116 (types per lidar_type:
  * VELO time f32 [s] / ring u16; OUSTER t u32 [ns] / ring u8; PANDAR timestamp f64 / ring u16; ROBOSENSE timestamp f64 /
- * ring u16 / intensity u8; intensity is not carried — nothing on the path reads it).  Decode, blind / NaN / ring /
+ * ring u16 / intensity u8; intensity is not part of the float4 records — nothing on the path reads it — and is carried beside them only
+ * under lii_ingest_set_intensity, below).  Decode, blind / NaN / ring /
  * point_filter_num filters, azimuth time synthesis for clouds without per-point time (:163-185), time sort and the
  * sub-frame cut (:296-334) run on the device; the frames stay there.  frames[k].begin_time_s is the value the caller
  * pushes to time_buffer (time_lidar / 1000), offset/count index the handle's frame buffer.
@@ -455,7 +487,8 @@ int lii_map_build_from_scan(lii_handle h, const lii_state* state, int32_t* n_map
  *                   world frame, compacted in ascending index of the device's down-sampled order - the same bits on every run; their
  *                   number is lii_iekf_report::effect_num;
  *   LII_PUB_BODY    publish_frame_body (:616-623): the de-skewed scan as it is (a copy).
- * Every cloud is float4 (x, y, z, t_ms), t_ms carried through unchanged (the scan format has no intensity: a caller joins it by index).
+ * Every cloud is float4 (x, y, z, t_ms), t_ms carried through unchanged.  The float4 records have no intensity: with LII_PUB_INTENSITY the
+ * intensities of the registered scan (lii_scan_intensity_*, lii_ingest_set_intensity) are published beside the clouds, point for point.
  * lii_publish_set places a STANDING ORDER on the handle (off by default): from then on every call that reaches its update -
  * lii_scan_register, lii_scan_register_imu, lii_scan_register_cv, lii_iekf_update - enqueues one more launch behind its passes (behind
  * the map update of lii_scan_job::map_update, in front of a pre-armed prologue of lii_scan_job::next_scan_dev), which reads the final
@@ -480,11 +513,24 @@ int lii_map_build_from_scan(lii_handle h, const lii_state* state, int32_t* n_map
  *   lii_publish_saved  the save buffer's points so far -> out_float4 (may be NULL: *n only), and, with clear != 0, an empty buffer
  *                      (:603-612, the flush every pcd_save_interval scans; writing the PCD file is the caller's).  capacity < *n:
  *                      LII_ERR_CAPACITY, nothing is cleared.  A scan that did not fit since the last clear: the points are returned
- *                      and the call reports LII_ERR_CAPACITY.  Uses the handle's stream (not from while_waiting). */
-enum { LII_PUB_DENSE = 1, LII_PUB_DOWN = 2, LII_PUB_EFFECT = 4, LII_PUB_BODY = 8 };
+ *                      and the call reports LII_ERR_CAPACITY.  Uses the handle's stream (not from while_waiting).
+ *   LII_PUB_INTENSITY  a bit of lii_publish_opts::clouds, valid only together with at least one of DENSE / DOWN / BODY (alone:
+ *                      LII_ERR_INVALID): the launch also hands on the intensities of the ordered clouds - dense and body: the scan's, in
+ *                      the scan's order (sorted when the job sorts); down: the voxel filter's per-voxel means, row for row with the DOWN
+ *                      cloud - into buffers of their own, two deep like the clouds, to_host honoured.
+ *   lii_publish_fetch_intensity  cloud = LII_PUB_DENSE, LII_PUB_DOWN or LII_PUB_BODY: order, *n and lifetime are those of the cloud
+ *                      lii_publish_fetch returns; it waits for the intensities' event only and MAY BE CALLED FROM while_waiting.
+ *                      LII_PUB_EFFECT is NOT SERVED (LII_ERR_INVALID): the reference overwrites that cloud's intensity with sqrt(R_inv) =
+ *                      sqrt(1000) (src/laserMapping.cpp:1051) - nothing of the sensor's is left to deliver.  The bit not ordered, the cloud not
+ *                      ordered, or the registered scan had no intensities: LII_ERR_STATE.
+ *   lii_publish_saved_intensity  with the bit set and save_capacity > 0 an intensity buffer of the same capacity is appended to in lock-step
+ *                      with the save buffer - the same offset, the same fits / does-not-fit decision, by the same launch; a scan registered
+ *                      without intensities appends 0.0f, so the two stay aligned.  This call reads it (out may be NULL: *n only; errors as
+ *                      lii_publish_saved); the clearing call stays lii_publish_saved(..., clear = 1), which empties both. */
+enum { LII_PUB_DENSE = 1, LII_PUB_DOWN = 2, LII_PUB_EFFECT = 4, LII_PUB_BODY = 8, LII_PUB_INTENSITY = 16 };
 typedef struct lii_publish_opts {
   uint32_t struct_size;   /* sizeof(lii_publish_opts) */
-  int32_t clouds;         /* LII_PUB_DENSE 1 | LII_PUB_DOWN 2 | LII_PUB_EFFECT 4 | LII_PUB_BODY 8 */
+  int32_t clouds;         /* LII_PUB_DENSE 1 | LII_PUB_DOWN 2 | LII_PUB_EFFECT 4 | LII_PUB_BODY 8 | LII_PUB_INTENSITY 16 */
   int32_t to_host;        /* 1: also copy each cloud to pinned host memory on the copy stream */
   int32_t save_capacity;  /* > 0: append the dense world cloud of every scan to a save buffer of that many points */
 } lii_publish_opts;
@@ -492,6 +538,8 @@ int lii_publish_set(lii_handle h, const lii_publish_opts* opts);
 int lii_publish_now(lii_handle h, const lii_state* state);
 int lii_publish_fetch(lii_handle h, int32_t cloud, const float** host_float4, const void** dev_float4, int32_t* n);
 int lii_publish_saved(lii_handle h, float* out_float4, int32_t capacity, int32_t* n, int32_t clear);
+int lii_publish_fetch_intensity(lii_handle h, int32_t cloud, const float** host_float, const void** dev_float, int32_t* n);
+int lii_publish_saved_intensity(lii_handle h, float* out, int32_t capacity, int32_t* n);
 
 /* ---------------------------------------------------------------- LI-Init batch calibration evaluators
  * CalibState record (include/LI_init/LI_init.h:31-89). */

@@ -67,6 +67,7 @@ class lii_publish_opts(C.Structure):
 
 
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
+PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
 
 class lii_imu_sample(C.Structure):
@@ -165,6 +166,12 @@ _DECLS = {
     "lii_publish_now": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lii_publish_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "lii_publish_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "lii_publish_fetch_intensity": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "lii_publish_saved_intensity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_scan_intensity_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "lii_scan_intensity_set_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "lii_ingest_set_intensity": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_scan_intensity_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_calib_set_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_calib_eval": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
@@ -225,6 +232,13 @@ def load_library():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+class _DeviceFloat:
+    """... and a buffer of n float32 (the intensity channel)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr="<f4", data=(int(ptr), False), version=2)
 
 
 class _DeviceFloat4:
@@ -463,6 +477,39 @@ class Registrar:
         self._check(self.L.lii_scan_download(self.h, which, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
+    # ------------------------------------------------------------------ the intensity channel (optional; off until asked for)
+    def scan_intensity_upload(self, intensity):
+        """Attaches intensities to the current scan: (n,) float32, or the (n, 12) PointXYZINormal records (column 8)."""
+        a = np.ascontiguousarray(intensity, np.float32)
+        assert a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 12)
+        off = 0 if a.ndim == 1 else 32
+        self._check(self.L.lii_scan_intensity_upload(self.h, _ptr(a), len(a), a.strides[0] if len(a) else 4, off))
+
+    def device_intensity(self, intensity):
+        """Copies (n,) float32 into a caller-owned device buffer; returns an opaque (ptr, n) for scan_intensity_set_device."""
+        a = np.ascontiguousarray(intensity, np.float32).reshape(-1)
+        p = C.c_void_p()
+        self._check(self.L.lii_dev_alloc(self.h, max(a.nbytes, 16), C.byref(p)))
+        self._dev_bufs.append(p)
+        if len(a):
+            self._check(self.L.lii_dev_upload(self.h, p, _ptr(a), a.nbytes))
+        return (p, len(a))
+
+    def scan_intensity_set_device(self, dev):
+        self._check(self.L.lii_scan_intensity_set_device(self.h, dev[0], dev[1]))
+
+    def ingest_set_intensity(self, on=True):
+        """The standing order: every ingest call from now on also forms its frames' intensities; frame_select attaches them."""
+        self._check(self.L.lii_ingest_set_intensity(self.h, int(bool(on))))
+
+    def scan_intensity_download(self, which=0):
+        """which=0: the current scan's intensities; 1: the down-sampled cloud's, in the order scan_download(1) returns its points."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_scan_intensity_download(self.h, which, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.float32)
+        self._check(self.L.lii_scan_intensity_download(self.h, which, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
     # ------------------------------------------------------------------ ingest
     def _ingest(self, fn, data, n_points, fields, lidar_type, n_scans, point_filter_num, blind, stamp_s, cut_frame_num,
                 scan_count):
@@ -682,7 +729,8 @@ class Registrar:
 
     # ------------------------------------------------------------------ the registered clouds (publish_frame_world / pcd_save)
     def publish_set(self, clouds=0, to_host=False, save_capacity=0):
-        """The standing order (lii_publish_set): clouds = PUB_DENSE | PUB_DOWN | PUB_EFFECT | PUB_BODY; nothing ordered: off."""
+        """The standing order (lii_publish_set): clouds = PUB_DENSE | PUB_DOWN | PUB_EFFECT | PUB_BODY (| PUB_INTENSITY: the
+        intensities of DENSE / DOWN / BODY beside them); nothing ordered: off."""
         if not clouds and not save_capacity:
             self._check(self.L.lii_publish_set(self.h, None))
             return
@@ -705,6 +753,29 @@ class Registrar:
             return a.copy() if copy else a
         import torch  # (device only: the buffer is read through torch, the project's plumbing)
         return torch.as_tensor(_DeviceFloat4(dp.value, n.value), device="cuda").cpu().numpy().copy()
+
+    def publish_fetch_intensity(self, cloud, copy=True):
+        """The intensities of one cloud (PUB_DENSE, PUB_DOWN or PUB_BODY) of the last finished registration as (n,) float32, row for row
+        with publish_fetch(cloud); the same lifetime, callable from while_waiting of the next call."""
+        hp, dp, n = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self._check(self.L.lii_publish_fetch_intensity(self.h, int(cloud), C.byref(hp), C.byref(dp), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.float32)
+        if hp.value:
+            a = np.ctypeslib.as_array(C.cast(hp, C.POINTER(C.c_float)), shape=(n.value,))
+            return a.copy() if copy else a
+        import torch  # (device only: the buffer is read through torch, the project's plumbing)
+        return torch.as_tensor(_DeviceFloat(dp.value, n.value), device="cuda").cpu().numpy().copy()
+
+    def publish_saved_intensity(self):
+        """The save buffer's intensities as (n,) float32, point for point with publish_saved(); LIIError(-4) as publish_saved."""
+        n = C.c_int32(0)
+        rc = self.L.lii_publish_saved_intensity(self.h, None, 0, C.byref(n))
+        if rc not in (0, -4):
+            self._check(rc)
+        out = np.zeros(max(n.value, 1), np.float32)
+        self._check(self.L.lii_publish_saved_intensity(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
 
     def publish_saved(self, clear=False):
         """The save buffer (pcl_wait_save) as an (n, 4) float32 array; LIIError(-4) if a scan did not fit since the last clear."""

@@ -158,11 +158,25 @@ void prearm_cancel(lii_handle h) {
   if (gate_move(h->pre.state, h->pre.seq, lii::kGateCancel)) h->pre.n_cancelled++;
   else h->pre.n_expired++;  // (the launch had given up already)
 }
+// The intensity channel: whatever replaces the current scan detaches its intensities (those of the down-sampled cloud go with them).
+void intensity_detach(lii_handle h) {
+  h->inten.have = false;
+  h->inten.body_have = false;
+}
+int intensity_buffers(lii_handle h) {
+  const size_t cap = size_t(h->cfg.max_scan_points);
+  if (!h->inten.d_scan) HIPCHK(h, h->inten.d_scan.alloc(cap));
+  if (!h->inten.d_body) HIPCHK(h, h->inten.d_body.alloc(cap));
+  return LII_OK;
+}
 int scan_materialize(lii_handle h) {
   if (!h->scan_pending) return LII_OK;
   const float4* src = h->scan_pending;
   const int n = h->scan_pending_n;
-  return lii_scan_set_device(h, src, n);  // (clears the pending frame through extent_discard, then copies from `src`)
+  const bool keep = h->inten.have;  // (the frame's intensities were copied when it was selected: the same scan moves, nothing replaces it)
+  const int rc = lii_scan_set_device(h, src, n);  // (clears the pending frame through extent_discard, then copies from `src`)
+  if (rc == LII_OK) h->inten.have = keep;
+  return rc;
 }
 int scan_sort_into(lii_handle h, const float4* src, int n) {
   if (n <= 0) return LII_OK;
@@ -182,12 +196,15 @@ int scan_sort_into(lii_handle h, const float4* src, int n) {
     if (!in_place) HIPCHK(h, hipMemcpyAsync(h->d_scan, src, sizeof(float4), hipMemcpyDeviceToDevice, s));
     return LII_OK;
   }
+  const bool wi = h->inten.have;  // the scan's intensities move by the same permutation, inside the gather launch
+  if (wi && !h->inten.d_sort_out) HIPCHK(h, h->inten.d_sort_out.alloc(size_t(h->cfg.max_scan_points)));
   launch_sort_keys(src, n, b.d_key_a, b.d_idx_a, s);
   sort_pairs_u32(b.d_temp, b.d_temp.size(), b.d_key_a, b.d_key_b, b.d_idx_a, b.d_idx_b, n, s);
-  launch_sort_gather(src, b.d_idx_b, n, in_place ? b.d_out.get() : h->d_scan.get(), s);
+  launch_sort_gather(src, b.d_idx_b, n, in_place ? b.d_out.get() : h->d_scan.get(), s, wi ? h->inten.d_scan.get() : nullptr, wi ? h->inten.d_sort_out.get() : nullptr);
   HIPCHK(h, hipGetLastError());
   // (the stream orders everything that read or writes either buffer; the other scan buffer of lii_scan_upload_next is not involved)
   if (in_place) std::swap(h->d_scan, b.d_out);
+  if (wi) std::swap(h->inten.d_scan, h->inten.d_sort_out);
   return LII_OK;
 }
 unsigned long long* extent_of_scan(lii_handle h) {
@@ -295,6 +312,7 @@ int lii_internal_scan_defer(lii_handle h, const void* dev_float4, int32_t n) {
   if (!h || (!dev_float4 && n > 0) || n < 0) return fail(h, LII_ERR_INVALID, "lii_frame_select: bad frame");
   if (n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_frame_select: frame larger than max_scan_points");
   extent_discard(h);
+  intensity_detach(h);  // (lii_frame_select attaches the frame's own behind this, if the ingest formed them)
   h->scan_buf_idle = false;
   h->bbox_rows = 0;
   h->scan_pending = n > 0 ? static_cast<const float4*>(dev_float4) : nullptr;
@@ -303,6 +321,17 @@ int lii_internal_scan_defer(lii_handle h, const void* dev_float4, int32_t n) {
   h->n_body = 0;
   h->n_body_pending = false;
   h->have_search = false;
+  return LII_OK;
+}
+
+int lii_internal_intensity_refused(lii_context* h) { return h && (h->net.comm || h->net.n_ranks > 1 || h->host_solve) ? 1 : 0; }
+int lii_internal_scan_intensity_adopt(lii_handle h, const float* dev_float, int32_t n) {
+  if (!h) return LII_ERR_INVALID;
+  intensity_detach(h);
+  if (!dev_float || n <= 0 || n != h->n_scan) return LII_OK;
+  { const int rc = intensity_buffers(h); if (rc != LII_OK) return rc; }
+  HIPCHK(h, hipMemcpyAsync(h->inten.d_scan, dev_float, sizeof(float) * size_t(n), hipMemcpyDeviceToDevice, h->stream));
+  h->inten.have = true;
   return LII_OK;
 }
 
@@ -632,6 +661,7 @@ int lii_scan_upload(lii_handle h, const void* points, int32_t n, int32_t stride_
   HIPCHK(h, hipEventRecord(h->ev_stage, h->stream));
   h->n_scan = n;
   extent_discard(h);
+  intensity_detach(h);
   h->bbox_rows = 0;
   h->n_body = 0;
   h->n_body_pending = false;
@@ -698,6 +728,7 @@ int lii_scan_advance(lii_handle h) {
   h->n_scan = h->n_scan_next;
   h->n_scan_next = -1;
   extent_discard(h);
+  intensity_detach(h);  // (lii_scan_upload_next carries no intensity)
   h->bbox_rows = 0;
   h->n_body = 0;
   h->n_body_pending = false;
@@ -727,6 +758,7 @@ int lii_scan_set_device(lii_handle h, const void* dev_float4, int32_t n) {
   if (!h || (!dev_float4 && n > 0) || n < 0) return fail(h, LII_ERR_INVALID, "lii_scan_set_device: bad arguments");
   if (n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, "lii_scan_set_device: n > max_scan_points");
   extent_discard(h);
+  intensity_detach(h);
   h->bbox_rows = 0;
   if (n > 0) {  // copy + time extent of the scan in one pass (the de-skew that usually follows needs the extent)
     launch_time_extent(static_cast<const float4*>(dev_float4), n, h->d_extent + 2 * h->extent_sel,
@@ -804,6 +836,9 @@ int lii_downsample_skip(lii_handle h, int32_t* n_down) {
   if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
   if (h->n_scan > 0)
     HIPCHK(h, hipMemcpyAsync(h->d_body, h->d_scan, sizeof(float4) * size_t(h->n_scan), hipMemcpyDeviceToDevice, h->stream));
+  if (h->inten.have && h->n_scan > 0)  // (the cloud passes as it is: so do its intensities)
+    HIPCHK(h, hipMemcpyAsync(h->inten.d_body, h->inten.d_scan, sizeof(float) * size_t(h->n_scan), hipMemcpyDeviceToDevice, h->stream));
+  h->inten.body_have = h->inten.have;
   h->n_body = h->n_scan;
   h->n_body_pending = false;
   h->have_search = false;
@@ -820,6 +855,11 @@ int lii_downsample(lii_handle h, float leaf, int32_t* n_down, int32_t* filtered)
   h->have_search = false;
   h->n_body_pending = false;
   const int n = h->n_scan;
+  if (h->inten.have && lii_internal_intensity_refused(h)) intensity_detach(h);  // (a communicator attached behind the intensities: the channel is single rank only)
+  // the scan carries intensities: the centroid launch of either filter forms the voxels' as well (its INT instantiation)
+  const float* const inten = h->inten.have ? h->inten.d_scan.get() : nullptr;
+  float* const inten_out = h->inten.have ? h->inten.d_body.get() : nullptr;
+  h->inten.body_have = h->inten.have;
   if (n <= 0) {
     h->n_body = 0;
     if (n_down) *n_down = 0;
@@ -877,7 +917,7 @@ int lii_downsample(lii_handle h, float leaf, int32_t* n_down, int32_t* filtered)
   const bool by_voxel = inserted && h->vh.part_world > 1;  // this rank emits ITS voxels only
   if (use_hash) {
     if (++h->vh_epoch == 0u) h->vh_epoch = 1u;
-    launch_voxel_hash(h->vh, h->d_scan, n, mm, h->d_bbox_rows, h->bbox_rows, leaf, h->d_body, h->d_nbody, h->d_nbody + 1, h->d_vpcl_out, hash_stages, h->vh_epoch, s, h->test_emit_late ? 1 : 0);
+    launch_voxel_hash(h->vh, h->d_scan, n, mm, h->d_bbox_rows, h->bbox_rows, leaf, h->d_body, h->d_nbody, h->d_nbody + 1, h->d_vpcl_out, hash_stages, h->vh_epoch, s, h->test_emit_late ? 1 : 0, inten, inten_out);
     if (!h->vh_pinned && !by_voxel && !h->vh_flag_pending && (++h->vh_watch & 15) == 0) {  // (every 16th scan: the copy costs a packet on the stream)
       HIPCHK(h, hipMemcpyAsync(h->h_vh_crowded, h->vh.crowded, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
       HIPCHK(h, hipMemsetAsync(h->vh.crowded, 0, sizeof(unsigned int), s));
@@ -896,7 +936,7 @@ int lii_downsample(lii_handle h, float leaf, int32_t* n_down, int32_t* filtered)
     vb.comp = h->d_vcomp; vb.splitters = h->d_vsplit; vb.hist = h->d_vhist; vb.bucket_of = h->d_vbucket;
     vb.max_run = h->voxel_sort ? nullptr : h->vh.crowded;
     if (!h->voxel_sort) HIPCHK(h, hipMemsetAsync(h->vh.crowded, 0, sizeof(unsigned int), s));
-    launch_voxel_sort_centroids(vb, h->d_scan, n, h->d_body, h->d_nbody, s);
+    launch_voxel_sort_centroids(vb, h->d_scan, n, h->d_body, h->d_nbody, s, inten, inten_out);
     if (!h->voxel_sort && !h->vh_flag_pending && (++h->vh_watch & 15) == 0) {  // how crowded are the voxels now?
       HIPCHK(h, hipMemcpyAsync(h->h_vh_crowded, h->vh.crowded, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
       HIPCHK(h, hipMemsetAsync(h->vh.crowded, 0, sizeof(unsigned int), s));
@@ -937,6 +977,65 @@ int lii_scan_download(lii_handle h, int32_t which, float* out_float4, int32_t ca
     if (!perm) std::memcpy(out_float4, h->h_stage, sizeof(float4) * size_t(cnt));
     else
       for (int r = 0; r < cnt; r++) std::memcpy(out_float4 + 4 * size_t(r), &h->h_stage[perm[r]], sizeof(float4));
+  }
+  return LII_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the intensity channel
+// (what the attaching calls share: the checks of the contract, the buffers on first use)
+static int intensity_attach_check(lii_handle h, const void* src, int32_t n, const char* who) {
+  if (!h || (!src && n > 0) || n < 0) return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (lii_internal_intensity_refused(h)) return fail(h, LII_ERR_STATE, std::string(who) + ": single rank only for now (a communicator is attached, or LII_TEST=host_solve)");
+  if (h->n_scan <= 0) return fail(h, LII_ERR_STATE, std::string(who) + ": no scan (lii_scan_upload / lii_scan_set_device / lii_scan_advance / lii_frame_select)");
+  if (n != h->n_scan) return fail(h, LII_ERR_INVALID, std::string(who) + ": n is not the current scan's point count");
+  return intensity_buffers(h);
+}
+int lii_scan_intensity_upload(lii_handle h, const void* points, int32_t n, int32_t stride_bytes, int32_t intensity_offset_bytes) {
+  if (h) h->scan_buf_idle = false;
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (h && (stride_bytes < 4 || intensity_offset_bytes < 0 || intensity_offset_bytes + 4 > stride_bytes))
+    return fail(h, LII_ERR_INVALID, "lii_scan_intensity_upload: bad arguments");
+  { const int rc = intensity_attach_check(h, points, n, "lii_scan_intensity_upload"); if (rc != LII_OK) return rc; }
+  HIPCHK(h, hipEventSynchronize(h->ev_stage));  // the previous upload has left the staging buffer
+  float* st = reinterpret_cast<float*>(h->h_stage.get());
+  const char* src = static_cast<const char*>(points);
+  for (int i = 0; i < n; i++) std::memcpy(st + i, src + size_t(i) * stride_bytes + intensity_offset_bytes, 4);
+  HIPCHK(h, hipMemcpyAsync(h->inten.d_scan, st, sizeof(float) * size_t(n), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev_stage, h->stream));
+  h->inten.have = true;
+  h->inten.body_have = false;  // (a down-sampled cloud made before belongs to the scan without them)
+  return LII_OK;
+}
+int lii_scan_intensity_set_device(lii_handle h, const void* dev_float, int32_t n) {
+  if (h) h->scan_buf_idle = false;
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  { const int rc = intensity_attach_check(h, dev_float, n, "lii_scan_intensity_set_device"); if (rc != LII_OK) return rc; }
+  HIPCHK(h, hipMemcpyAsync(h->inten.d_scan, dev_float, sizeof(float) * size_t(n), hipMemcpyDeviceToDevice, h->stream));
+  h->inten.have = true;
+  h->inten.body_have = false;
+  return LII_OK;
+}
+int lii_scan_intensity_download(lii_handle h, int32_t which, float* out, int32_t capacity, int32_t* n) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !n || (which != 0 && which != 1)) return fail(h, LII_ERR_INVALID, "lii_scan_intensity_download: bad arguments");
+  if (which == 0 ? !h->inten.have : !h->inten.body_have)
+    return fail(h, LII_ERR_STATE, which == 0 ? "lii_scan_intensity_download: the current scan has no intensities attached"
+                                             : "lii_scan_intensity_download: the down-sampled cloud has no intensities (attach them before the voxel filter)");
+  if (which != 0) { const int rc0 = resolve_n_body(h); if (rc0 != LII_OK) return rc0; }
+  const int cnt = which == 0 ? h->n_scan : h->n_body;
+  *n = cnt;
+  if (!out) return LII_OK;
+  if (capacity < cnt) return fail(h, LII_ERR_CAPACITY, "lii_scan_intensity_download: capacity too small");
+  if (cnt > 0) {
+    const int* perm = nullptr;  // (the down-sampled cloud: in the order lii_scan_download(h, 1) returns its points)
+    if (which != 0) { const int rc1 = pcl_order(h, &perm); if (rc1 != LII_OK) return rc1; }
+    HIPCHK(h, hipEventSynchronize(h->ev_stage));
+    const float* st = reinterpret_cast<const float*>(h->h_stage.get());
+    HIPCHK(h, hipMemcpyAsync(h->h_stage, which == 0 ? h->inten.d_scan.get() : h->inten.d_body.get(), sizeof(float) * size_t(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!perm) std::memcpy(out, st, sizeof(float) * size_t(cnt));
+    else
+      for (int r = 0; r < cnt; r++) out[r] = st[perm[r]];
   }
   return LII_OK;
 }

@@ -10,6 +10,9 @@ constexpr int kAllClouds = LII_PUB_DENSE | LII_PUB_DOWN | LII_PUB_EFFECT | LII_P
 int cloud_index(int cloud) {
   return cloud == LII_PUB_DENSE ? 0 : cloud == LII_PUB_DOWN ? 1 : cloud == LII_PUB_EFFECT ? 2 : cloud == LII_PUB_BODY ? 3 : -1;
 }
+// LII_PUB_INTENSITY: the clouds that come with intensities, and their index in Publish::d_int
+constexpr int kIntOf[lii_context::Publish::kIntClouds] = {LII_PUB_DENSE, LII_PUB_DOWN, LII_PUB_BODY};
+int int_index(int cloud) { return cloud == LII_PUB_DENSE ? 0 : cloud == LII_PUB_DOWN ? 1 : cloud == LII_PUB_BODY ? 2 : -1; }
 }  // namespace
 
 int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg* ps, bool first) {
@@ -24,6 +27,11 @@ int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg
   if (P.last_copy[slot] >= 0) HIPCHK(h, hipStreamWaitEvent(s, P.ev_copy[P.last_copy[slot]][slot], 0));
   if (first && (P.clouds & LII_PUB_BODY) && n_scan > 0)  // publish_frame_body: the de-skewed scan as it is
     HIPCHK(h, hipMemcpyAsync(P.d_cloud[3][slot], h->d_scan, sizeof(float4) * size_t(n_scan), hipMemcpyDeviceToDevice, s));
+  // LII_PUB_INTENSITY: which clouds of this slot get intensities - none when the registered scan has none (the save buffer then gets zeros)
+  const bool scan_int = P.intensity && h->inten.have && n_scan > 0;
+  const int int_clouds = !scan_int ? 0 : (P.clouds & (LII_PUB_DENSE | LII_PUB_BODY)) | ((P.clouds & LII_PUB_DOWN) && h->inten.body_have ? LII_PUB_DOWN : 0);
+  if (first && (int_clouds & LII_PUB_BODY))
+    HIPCHK(h, hipMemcpyAsync(P.d_int[2][slot], h->inten.d_scan, sizeof(float) * size_t(n_scan), hipMemcpyDeviceToDevice, s));
   const bool want_dense = (P.clouds & LII_PUB_DENSE) != 0, want_save = P.save_capacity > 0;
   const bool want_down = (P.clouds & LII_PUB_DOWN) != 0, want_effect = (P.clouds & LII_PUB_EFFECT) != 0;
   PublishArgs a = {};
@@ -32,6 +40,11 @@ int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg
   a.dense_blocks = (want_dense || want_save) ? (n_scan + 255) / 256 : 0;
   a.dense = want_dense ? P.d_cloud[0][slot].get() : nullptr;
   a.save = want_save ? P.d_save.get() : nullptr;
+  a.scan_int = scan_int ? h->inten.d_scan.get() : nullptr;
+  a.dense_int = (int_clouds & LII_PUB_DENSE) ? P.d_int[0][slot].get() : nullptr;
+  a.save_int = want_save ? P.d_save_int.get() : nullptr;  // (once it exists it is appended to by every order: 0.0f where there is nothing to hand on)
+  a.body_int = (int_clouds & LII_PUB_DOWN) ? h->inten.d_body.get() : nullptr;
+  a.down_int = (int_clouds & LII_PUB_DOWN) ? P.d_int[1][slot].get() : nullptr;
   a.save_cap = P.save_capacity;
   a.save_par = P.save_par;
   a.save_ctl = P.d_save_ctl;
@@ -63,6 +76,13 @@ int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg
   if (P.to_host) {
     HIPCHK(h, hipStreamWaitEvent(h->copy_stream, P.ev_pub[slot], 0));
     const int n_of[lii_context::Publish::kClouds] = {n_scan, h->n_body, h->n_body, n_scan};  // (down-sampled / effect: the bound; the counts travel in h_counts)
+    if (int_clouds) {  // (in front of the clouds' copies: the event recorded last for the slot lies behind them as well)
+      const int n_int[lii_context::Publish::kIntClouds] = {n_scan, h->n_body, n_scan};
+      for (int k = 0; k < lii_context::Publish::kIntClouds; k++)
+        if ((int_clouds & kIntOf[k]) && n_int[k] > 0)
+          HIPCHK(h, hipMemcpyAsync(P.h_int[k][slot], P.d_int[k][slot], sizeof(float) * size_t(n_int[k]), hipMemcpyDeviceToHost, h->copy_stream));
+      HIPCHK(h, hipEventRecord(P.ev_int[slot], h->copy_stream));
+    }
     for (int c = 0; c < lii_context::Publish::kClouds; c++) {
       if (!(P.clouds & (1 << c))) continue;
       if (n_of[c] > 0)
@@ -74,6 +94,7 @@ int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg
   h->scan_buf_idle = false;  // (the launch and the body copy read the current scan buffer: lii_scan_upload_next orders its transfer behind them)
   P.n_scan_at[slot] = n_scan;
   P.clouds_at[slot] = P.clouds;
+  P.int_at[slot] = int_clouds;
   return LII_OK;
 }
 
@@ -88,8 +109,9 @@ extern "C" {
 
 int lii_publish_set(lii_handle h, const lii_publish_opts* opts) {
   if (!h) return LII_ERR_INVALID;
-  if (opts && (opts->struct_size != sizeof(lii_publish_opts) || (opts->clouds & ~kAllClouds) || (opts->to_host != 0 && opts->to_host != 1) || opts->save_capacity < 0))
-    return fail(h, LII_ERR_INVALID, "lii_publish_set: bad lii_publish_opts (struct_size, unknown cloud bits, to_host, save_capacity)");
+  if (opts && (opts->struct_size != sizeof(lii_publish_opts) || (opts->clouds & ~(kAllClouds | LII_PUB_INTENSITY)) ||
+               ((opts->clouds & LII_PUB_INTENSITY) && !(opts->clouds & (LII_PUB_DENSE | LII_PUB_DOWN | LII_PUB_BODY))) || (opts->to_host != 0 && opts->to_host != 1) || opts->save_capacity < 0))
+    return fail(h, LII_ERR_INVALID, "lii_publish_set: bad lii_publish_opts (struct_size, unknown cloud bits, LII_PUB_INTENSITY without DENSE / DOWN / BODY, to_host, save_capacity)");
   if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_publish_set: a registration is under way (lii_scan_job::while_waiting)");
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   lii_context::Publish& P = h->pub;
@@ -114,6 +136,16 @@ int lii_publish_set(lii_handle h, const lii_publish_opts* opts) {
       if (opts->to_host && !P.ev_copy[c][k]) HIPCHK(h, P.ev_copy[c][k].create(hipEventDisableTiming));
     }
   }
+  const bool want_int = (opts->clouds & LII_PUB_INTENSITY) != 0;
+  for (int c = 0; want_int && c < lii_context::Publish::kIntClouds; c++) {
+    if (!(opts->clouds & kIntOf[c])) continue;
+    for (int k = 0; k < 2; k++) {
+      if (!P.d_int[c][k]) HIPCHK(h, P.d_int[c][k].alloc(cap));
+      if (opts->to_host && !P.h_int[c][k]) HIPCHK(h, P.h_int[c][k].alloc(cap, hipHostMallocDefault));
+    }
+  }
+  for (int k = 0; want_int && opts->to_host && k < 2; k++)
+    if (!P.ev_int[k]) HIPCHK(h, P.ev_int[k].create(hipEventDisableTiming));
   if (opts->to_host && !h->copy_stream) HIPCHK(h, h->copy_stream.create(hipStreamNonBlocking));
   if (!P.d_counts) {
     HIPCHK(h, P.d_counts.alloc(4));
@@ -134,8 +166,15 @@ int lii_publish_set(lii_handle h, const lii_publish_opts* opts) {
     if (!P.d_save_ctl) HIPCHK(h, P.d_save_ctl.alloc(4));
     HIPCHK(h, hipMemset(P.d_save_ctl, 0, sizeof(int) * 4));
     P.save_par = 0;
+    P.d_save_int.reset();  // (a new, empty save buffer: its intensities follow below)
   }
-  P.clouds = opts->clouds;
+  if (want_int && opts->save_capacity > 0 && !P.d_save_int) {
+    // the intensities of the save buffer, point for point; what an order without the bit has appended so far has 0.0f
+    HIPCHK(h, P.d_save_int.alloc(size_t(opts->save_capacity)));
+    HIPCHK(h, hipMemset(P.d_save_int, 0, sizeof(float) * size_t(opts->save_capacity)));
+  }
+  P.intensity = want_int;
+  P.clouds = opts->clouds & kAllClouds;
   P.to_host = opts->to_host;
   P.save_capacity = opts->save_capacity;
   P.cur = 0;
@@ -175,6 +214,46 @@ int lii_publish_fetch(lii_handle h, int32_t cloud, const float** host_float4, co
   *n = (c == 0 || c == 3) ? P.n_scan_at[slot] : hc[c == 1 ? 0 : 1];
   if (host_float4) *host_float4 = P.to_host ? reinterpret_cast<const float*>(P.h_cloud[c][slot].get()) : nullptr;
   if (dev_float4) *dev_float4 = P.d_cloud[c][slot].get();
+  return LII_OK;
+}
+
+int lii_publish_fetch_intensity(lii_handle h, int32_t cloud, const float** host_float, const void** dev_float, int32_t* n) {
+  if (!h || !n) return fail(h, LII_ERR_INVALID, "lii_publish_fetch_intensity: bad arguments");
+  const int c = cloud_index(cloud), k = int_index(cloud);
+  // (the effect cloud is not served: the reference overwrites its intensity with sqrt(R_inv), src/laserMapping.cpp:1051 - nothing of the sensor's is left)
+  if (c < 0 || k < 0) return fail(h, LII_ERR_INVALID, "lii_publish_fetch_intensity: LII_PUB_DENSE, LII_PUB_DOWN or LII_PUB_BODY");
+  lii_context::Publish& P = h->pub;
+  if (!P.on || P.have < 0) return fail(h, LII_ERR_STATE, "lii_publish_fetch_intensity: no registration since the order (lii_publish_set)");
+  const int slot = P.have;
+  if (!P.intensity || !(P.clouds_at[slot] & cloud)) return fail(h, LII_ERR_STATE, "lii_publish_fetch_intensity: this cloud was not ordered with LII_PUB_INTENSITY");
+  if (!(P.int_at[slot] & cloud)) return fail(h, LII_ERR_STATE, "lii_publish_fetch_intensity: the registered scan had no intensities attached");
+  // the intensities' event only, as lii_publish_fetch: it may be called from lii_scan_job::while_waiting of the next call
+  HIPCHK(h, hipEventSynchronize(P.to_host ? P.ev_int[slot] : P.ev_pub[slot]));
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const volatile int* hc = P.h_counts + 4 * slot;
+  *n = k == 1 ? hc[0] : P.n_scan_at[slot];
+  if (host_float) *host_float = P.to_host ? P.h_int[k][slot].get() : nullptr;
+  if (dev_float) *dev_float = P.d_int[k][slot].get();
+  return LII_OK;
+}
+
+int lii_publish_saved_intensity(lii_handle h, float* out, int32_t capacity, int32_t* n) {
+  if (!h || !n) return fail(h, LII_ERR_INVALID, "lii_publish_saved_intensity: bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_publish_saved_intensity: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  lii_context::Publish& P = h->pub;
+  if (!P.d_save || !P.d_save_int) return fail(h, LII_ERR_STATE, "lii_publish_saved_intensity: no save buffer with intensities (lii_publish_opts::save_capacity with LII_PUB_INTENSITY)");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int ctl[4] = {0, 0, 0, 0};
+  HIPCHK(h, hipMemcpy(ctl, P.d_save_ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+  const int cnt = ctl[P.save_par];
+  *n = cnt;
+  if (cnt < 0 || size_t(cnt) > P.d_save_int.size()) return fail(h, LII_ERR_HIP, "lii_publish_saved_intensity: append offset out of range");
+  if (out) {
+    if (capacity < cnt) return fail(h, LII_ERR_CAPACITY, "lii_publish_saved_intensity: capacity too small");
+    if (cnt > 0) HIPCHK(h, hipMemcpy(out, P.d_save_int, sizeof(float) * size_t(cnt), hipMemcpyDeviceToHost));
+  }
+  if (ctl[2]) return fail(h, LII_ERR_CAPACITY, "lii_publish_saved_intensity: the save buffer overflowed - at least one scan was not appended (what it held is intact)");
   return LII_OK;
 }
 

@@ -531,6 +531,7 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   const int src_n = from_job ? job->n_scan_dev : h->scan_pending_n;
   bool adopt = src_dev != nullptr && src_n > 0;
   if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": n_scan_dev > max_scan_points");
+  if (from_job) intensity_detach(h);  // (the job's scan_dev replaces the current scan: a scan with intensities is handed over by lii_scan_set_device + lii_scan_intensity_set_device)
   const int n_next = adopt ? src_n : h->n_scan;
   // A gated de-skew launch waits on the stream (the previous call enqueued it for the scan its job announced): it is used when THIS
   // call asks for exactly that, and told to end otherwise - before anything here could wait for the stream.
@@ -679,7 +680,9 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
     h->poses_preloaded = h->ctrl_preloaded = true;
   }
   if (adopt) {
+    const bool keep = h->inten.have;  // (a selected ingest frame moves into the handle's buffer: its intensities, copied when it was selected, stay)
     rc = lii_scan_set_device(h, src_dev, src_n);
+    if (rc == LII_OK) h->inten.have = keep;
     if (rc != LII_OK) { h->ctrl_pending = 0; h->poses_preloaded = h->ctrl_preloaded = false; return rc; }
   }
   if (job->undistort == 1) {

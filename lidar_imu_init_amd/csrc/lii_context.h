@@ -127,6 +127,15 @@ struct lii_context {
     DevBuf<float4> d_out;            // a scan that sits in d_scan is gathered into this buffer, and the two are swapped
     DevBuf<unsigned char> d_temp;    // temporary storage of sort_pairs_u32
   } ssort;
+  // the optional per-point intensity channel (lii_scan_intensity_*, lii_ingest_set_intensity): one float per point beside the float4
+  // clouds, in buffers of their own - created by the first call that attaches intensities (max_scan_points each), never by lii_create
+  struct Intensity {
+    DevBuf<float> d_scan;      // of the current scan, in the scan's current order (valid while `have`)
+    DevBuf<float> d_sort_out;  // the time sort gathers into this buffer, and the two are swapped (created by the first sort that carries intensity)
+    DevBuf<float> d_body;      // of the down-sampled cloud, in the device's order (valid while `body_have`): PCL's centroid of the voxel's members
+    bool have = false;         // the current scan has intensities: whatever replaces the scan clears it (intensity_detach)
+    bool body_have = false;    // the voxel filter / lii_downsample_skip that made the current down-sampled cloud carried them
+  } inten;
   DevBuf<float4> d_body;   // down-sampled body points
   DevBuf<float4> d_world;
   DevBuf<float4> d_nbr;    // 5 x cap
@@ -287,6 +296,14 @@ struct lii_context {
     lii::Event ev_pub[2];                   // the slot's launch (and body copy) has completed (handle's stream)
     lii::Event ev_copy[kClouds][2];         // the slot's cloud has arrived in h_cloud (copy stream)
     int last_copy[2] = {-1, -1};            // the cloud whose ev_copy was recorded last for the slot (-1: no copy enqueued yet)
+    // LII_PUB_INTENSITY: the intensities of the dense / down-sampled / body cloud (index 0 / 1 / 2), two deep like the clouds
+    static constexpr int kIntClouds = 3;
+    bool intensity = false;                 // the bit is ordered
+    DevBuf<float> d_int[kIntClouds][2];     // max_scan_points each (the ordered ones)
+    PinnedBuf<float> h_int[kIntClouds][2];  // to_host: their pinned copies (copy stream, IN FRONT of the slot's cloud copies: last_copy covers them)
+    lii::Event ev_int[2];                   // the slot's intensities have arrived in h_int (copy stream)
+    int int_at[2] = {0, 0};                 // the LII_PUB_* clouds whose intensities the slot holds (0: the registered scan had none)
+    DevBuf<float> d_save_int;               // the save buffer's intensities: appended in lock-step with d_save by the same launch
     DevBuf<float4> d_save;                  // pcl_wait_save: save_capacity points (created by the first order that asks for it)
     DevBuf<int> d_save_ctl;                 // [save_par]: append offset, [save_par ^ 1]: written by the next launch, [2]: sticky overflow flag
     int save_par = 0;
@@ -360,6 +377,8 @@ void extent_discard(lii_handle h);
 // `src` (n points: a caller's device buffer, a frame of the ingest, or d_scan itself) -> d_scan in ascending time order, stable; the
 // launches go on the handle's stream, `src` is only read.  Does not touch the handle's book-keeping of the scan (n_scan, extent, ...).
 int scan_sort_into(lii_handle h, const float4* src, int n);
+void intensity_detach(lii_handle h);  // the current scan has been replaced: its intensities, and those of the down-sampled cloud, are void
+int intensity_buffers(lii_handle h);  // creates lii_context::inten's scan / down-sampled buffers on first use
 int scan_materialize(lii_handle h);  // a frame selected by lii_frame_select and not read yet -> d_scan (lii_scan_set_device)
 bool gate_move(lii::GateState* st, unsigned long long seq, unsigned long long to);  // the state word: armed -> `to`, if still armed
 void prearm_cancel(lii_handle h);  // a gated de-skew launch that waits on the stream is told to end (every entry point that uses the stream calls this first)

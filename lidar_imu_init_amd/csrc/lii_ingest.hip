@@ -64,6 +64,11 @@ struct IngestCtx {
   int n_tail = 0, required_tail = 0;  // what ingest_redo_sorted needs of the message: its raw point count, the cut it asked for
   double stamp_ms_tail = 0;
   int n_under_way = 0;              // points of the message an overlapped call put under way in this context
+  // lii_ingest_set_intensity: the frames' intensities, point for point beside d_frames (size(): as d_pts; created by the first message that
+  // is asked for them), gathered from the raw bytes by the indices the frames are gathered by
+  DevBuf<float> d_fint;
+  bool with_int = false;            // the message in this context was enqueued under the order: d_fint belongs to its frames
+  int int_kind = 0, int_off = 0, int_step = 0;  // how a raw record yields the value (k_frame_intensity), for ingest_redo_sorted as well
 };
 
 template <class T>
@@ -281,6 +286,25 @@ __global__ void k_cut_apply(const float4* __restrict__ pts, const unsigned int* 
   frames[s - 1] = p;
 }
 
+// The frames' intensities (lii_ingest_set_intensity), formed behind the apply launch by the indices it used: frame point s - 1 of a cut
+// message is raw point sorted_idx[s] (k_cut_apply), frame point r of a whole message raw point idx[r] (k_whole_apply) - `first` = 1 / 0.
+// kind 0: a float, copied bit for bit (VELO, OUSTER, PANDAR); 1: a uint8 converted to float (ROBOSENSE intensity, Livox reflectivity:
+// src/preprocess.cpp:69,149,198,222,262); 2: the type has no such field (L515): 0.0f.
+__global__ __launch_bounds__(256) void k_frame_intensity(const uint8_t* __restrict__ raw, int step, int off, int kind, const unsigned int* __restrict__ order,
+                                                         const IngestTable* __restrict__ tab, int n, int first, float* __restrict__ fint) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= tab->n_emitted || r + first >= n + first) return;
+  float v = 0.f;
+  if (kind != 2) {
+    const unsigned int i = order[r + first];
+    if (i < (unsigned int)n) {  // (an index of the compaction: a raw point of this message)
+      const uint8_t* p = raw + (size_t)i * step + off;
+      v = kind == 0 ? rd<float>(p) : (float)rd<uint8_t>(p);
+    }
+  }
+  fint[r] = v;
+}
+
 // Preprocess::process: the kept points in input order are THE cloud - one frame, stamped with the message's own time (the caller
 // pushes header.stamp, laserMapping.cpp:340,377), the first kept point included, curvatures as decoded.
 __global__ void k_whole_apply(const float4* __restrict__ pts, const unsigned int* __restrict__ idx, const unsigned int* __restrict__ rank, int n,
@@ -323,6 +347,7 @@ struct IngestRing {
   // check is done again with the sort before its frames are handed out.  LII_INGEST_SORT=always: never predicted.
   bool predict_sorted = false;
   bool never_predict = false;
+  bool want_int = false;  // lii_ingest_set_intensity: every message enqueued from now on also forms its frames' intensities
   bool diag = false;  // LII_DIAG (the handle's switches, taken when the ring is created)
   long long n_unsorted_skipped = 0, n_redone = 0;
 };
@@ -360,6 +385,16 @@ int ingest_reserve(lii_handle h, IngestCtx* c, int n, size_t raw_bytes) {
   }
   return LII_OK;
 }
+// ... and, under lii_ingest_set_intensity, the frames' intensities: as many as the per-point buffers hold (they grow with them: geometrically)
+int ingest_reserve_intensity(lii_handle h, IngestCtx* c) {
+  if (c->d_fint.size() < c->d_pts.size()) HIPCHK(h, c->d_fint.grow(c->d_pts.size()));
+  return LII_OK;
+}
+void ingest_intensity_launch(IngestCtx* c, const unsigned int* order, int n, int first, hipStream_t s) {
+  if (!c->with_int || n <= 0) return;
+  const IngestTable* d_table = reinterpret_cast<const IngestTable*>(c->d_aux.get());
+  hipLaunchKernelGGL(k_frame_intensity, dim3((n + 255) / 256), dim3(256), 0, s, c->d_raw.get(), c->int_step, c->int_off, c->int_kind, order, d_table, n, first, c->d_fint.get());
+}
 
 IngestRing* ring_of(lii_handle h) {
   void** slot = lii_internal_ingest_slot(h);
@@ -396,6 +431,7 @@ int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int
   c->cut_msg = o->cut_frame_num != 0;
   if (o->cut_frame_num == 0) {  // Preprocess::process: no sort, no cut
     hipLaunchKernelGGL(k_whole_apply, dim3(nb), dim3(256), 0, s, c->d_pts, c->d_idx_a, c->d_rank, n, o->stamp_s * 1000, c->d_frames, d_table, c->h_table);
+    ingest_intensity_launch(c, c->d_idx_a, n, 0, s);
   } else {
     IngestRing* r = ring_of(h);
     c->sort_skipped = r->predict_sorted && !r->never_predict;
@@ -406,6 +442,7 @@ int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int
     c->n_tail = n; c->required_tail = required; c->stamp_ms_tail = o->stamp_s * 1000;
     hipLaunchKernelGGL(k_cut_plan, dim3(1), dim3(64), 0, s, c->d_pts, order, c->d_rank, n, c->stamp_ms_tail, required, d_table, c->h_table);
     hipLaunchKernelGGL(k_cut_apply, dim3(nb), dim3(256), 0, s, c->d_pts, order, d_table, n, c->d_frames, c->d_key_a, c->h_table);
+    ingest_intensity_launch(c, order, n, 1, s);
   }
   HIPCHK(h, hipGetLastError());
   return LII_OK;
@@ -417,6 +454,7 @@ int ingest_redo_sorted(lii_handle h, IngestCtx* c, hipStream_t s) {
   sort_pairs_u32(c->d_temp, c->d_temp.size(), c->d_key_a, c->d_key_b, c->d_idx_a, c->d_idx_b, n, s);
   hipLaunchKernelGGL(k_cut_plan, dim3(1), dim3(64), 0, s, c->d_pts, c->d_idx_b, c->d_rank, n, c->stamp_ms_tail, c->required_tail, d_table, c->h_table);
   hipLaunchKernelGGL(k_cut_apply, dim3(nb), dim3(256), 0, s, c->d_pts, c->d_idx_b, d_table, n, c->d_frames, c->d_key_a, c->h_table);
+  ingest_intensity_launch(c, c->d_idx_b, n, 1, s);  // (the intensities of the frames as they are now)
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(s));
   c->sort_skipped = false;
@@ -484,6 +522,16 @@ int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points,
   const size_t bytes = (size_t)n_points * f->point_step;
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
+  c->with_int = ring_of(h)->want_int;
+  if (c->with_int) {
+    rc = ingest_reserve_intensity(h, c);
+    if (rc != LII_OK) return rc;
+    const int width = o->lidar_type == LII_LIDAR_ROBOSENSE ? 1 : 4;
+    c->int_kind = o->lidar_type == LII_LIDAR_L515 ? 2 : (o->lidar_type == LII_LIDAR_ROBOSENSE ? 1 : 0);
+    if (f->intensity < 0 || f->intensity + width > f->point_step) c->int_kind = 2;  // (a layout without the field)
+    c->int_off = c->int_kind == 2 ? 0 : f->intensity;
+    c->int_step = f->point_step;
+  }
   HIPCHK(h, hipMemcpyAsync(c->d_raw, data, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
     HIPCHK(h, hipEventRecord(ev_copied, s_copy));
@@ -511,6 +559,14 @@ int livox_enqueue(lii_handle h, IngestCtx* c, const void* points, int32_t n_poin
   const size_t bytes = (size_t)n_points * f->point_step;
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
+  c->with_int = ring_of(h)->want_int;
+  if (c->with_int) {
+    rc = ingest_reserve_intensity(h, c);
+    if (rc != LII_OK) return rc;
+    c->int_kind = (f->reflectivity < 0 || f->reflectivity + 1 > f->point_step) ? 2 : 1;
+    c->int_off = c->int_kind == 2 ? 0 : f->reflectivity;
+    c->int_step = f->point_step;
+  }
   HIPCHK(h, hipMemcpyAsync(c->d_raw, points, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
     HIPCHK(h, hipEventRecord(ev_copied, s_copy));
@@ -682,7 +738,18 @@ int lii_frame_select(lii_handle h, int32_t frame) {
   IngestCtx* c = &r->slot[r->front];
   if (!c->have || frame < 0 || frame >= c->table.n_frames) return lii_internal_fail(h, LII_ERR_STATE, "lii_frame_select: no such frame");
   const int first = c->table.first[frame], cnt = c->table.last[frame] - first + 1;
-  return lii_internal_scan_defer(h, c->d_frames + (first - 1), cnt);  // (read in place by lii_scan_register, copied by any other reader)
+  const int rc = lii_internal_scan_defer(h, c->d_frames + (first - 1), cnt);  // (read in place by lii_scan_register, copied by any other reader)
+  if (rc != LII_OK) return rc;
+  // the frame's intensities become the current scan's (a frame ingested without the order has none: the hand-over above detached them)
+  return lii_internal_scan_intensity_adopt(h, c->with_int ? c->d_fint.get() + (first - 1) : nullptr, cnt);
+}
+
+int lii_ingest_set_intensity(lii_handle h, int32_t on) {
+  if (!h || (on != 0 && on != 1)) return lii_internal_fail(h, LII_ERR_INVALID, "lii_ingest_set_intensity: bad arguments");
+  if (on && lii_internal_intensity_refused(h))
+    return lii_internal_fail(h, LII_ERR_STATE, "lii_ingest_set_intensity: single rank only for now (a communicator is attached, or LII_TEST=host_solve)");
+  ring_of(h)->want_int = on != 0;  // (messages under way keep what they were enqueued with)
+  return LII_OK;
 }
 
 }  // extern "C"

@@ -20,6 +20,9 @@ int lii_internal_scan_defer(lii_context* h, const void* dev_float4, int32_t n); 
 int lii_internal_scan_materialize(lii_context* h);  // (lii_capi.cpp) a selected frame nobody has read yet -> the handle's own scan buffer
 int lii_internal_in_wait_hook(lii_context* h);       // (lii_capi.cpp) 1: inside lii_scan_job::while_waiting of a registration under way
 int lii_internal_scan_is_deferred(lii_context* h);  // (lii_capi.cpp) 1: a selected frame that nobody has read yet
+int lii_internal_intensity_refused(lii_context* h);  // (lii_capi.cpp) 1: a communicator is attached or LII_TEST=host_solve - no intensity channel
+// (lii_capi.cpp) lii_frame_select's hand-over of the frame's intensities (dev_float == nullptr: the frame has none); copied on the handle's stream
+int lii_internal_scan_intensity_adopt(lii_context* h, const float* dev_float, int32_t n);
 void lii_internal_prearm_cancel(lii_context* h);  // (lii_capi.cpp) see lii_impl::prearm_cancel
 hipStream_t lii_internal_stream(lii_context* h);
 void** lii_internal_ingest_slot(lii_context* h);
@@ -102,7 +105,8 @@ void launch_time_extent(const float4* pts, int n, unsigned long long* extent, un
                         const void* ctrl_src, void* ctrl_dst, size_t ctrl_bytes, hipStream_t s);
 // the time sort of a scan: key[i] = order-preserving image of t (-0.0 as +0.0), idx[i] = i; then sort_pairs_u32; then dst[i] = src[idx[i]]
 void launch_sort_keys(const float4* pts, int n, unsigned int* key, unsigned int* idx, hipStream_t s);
-void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
+// (inten_src != nullptr: the scan's intensities travel by the same idx, inten_dst[i] = inten_src[idx[i]])
+void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s, const float* inten_src = nullptr, float* inten_dst = nullptr);
 // voxel grid (lii_scan.hip)
 void launch_voxel_minmax(const float4* pts, int n, unsigned int* mm, unsigned int* mm_next, hipStream_t s);
 void launch_voxel_keys(const float4* pts, int n, const unsigned int* mm, const unsigned int* bbox_rows, int n_rows, float leaf,
@@ -125,7 +129,10 @@ int voxel_partition_bound(int n, int world);
 void launch_voxel_hash_clear(const VoxelHashBuffers& vh, size_t slots, hipStream_t s);
 void launch_voxel_hash(const VoxelHashBuffers& vh, const float4* pts, int n, const unsigned int* mm, const unsigned int* bbox_rows,
                        int n_rows, float leaf, float4* out, int* n_out, int* filtered, unsigned int* pcl_out, int stages, unsigned int epoch,
-                       hipStream_t s, int test_late = 0 /* LII_TEST=emit_late: see k_vhash_emit */);
+                       hipStream_t s, int test_late = 0 /* LII_TEST=emit_late: see k_vhash_emit */,
+                       // inten != nullptr: the emit also forms every voxel's intensity - the members' in input order from 0.f, divided by the
+                       // count, PCL's centroid - at the voxel's place in inten_out (the identity pass-through copies)
+                       const float* inten = nullptr, float* inten_out = nullptr);
 // de-skew (k_deskew_imu / k_deskew_cv): where the scan comes from and goes to, what is known about it, what rides along
 struct DeskewPlan {
   const float4* in;     // the scan as it arrived (a caller's device buffer, or == out)
@@ -272,6 +279,14 @@ struct PublishArgs {
   const float4* scan;       // the de-skewed scan (dense_blocks workgroups of 256 points)
   int n_scan, dense_blocks;
   float4* dense;            // LII_PUB_DENSE (nullptr: not ordered)
+  // LII_PUB_INTENSITY (every pointer nullptr: today's launch).  scan_int: the scan's intensities (nullptr: it has none - the save buffer
+  // then gets 0.0f), dense_int: -> the dense cloud's, save_int: -> the save buffer's at the cloud's offset, by the workgroups that own it;
+  // body_int -> down_int: the down-sampled cloud's, by the workgroups of that cloud
+  const float* scan_int;
+  float* dense_int;
+  float* save_int;
+  const float* body_int;
+  float* down_int;
   float4* save;             // the save buffer (nullptr: none), save_cap points,
   int save_cap, save_par;
   int* save_ctl;            // ... [save_par]: its append offset as this launch finds it, [save_par ^ 1]: as it leaves it, [2]: sticky "a scan did not fit"
@@ -313,7 +328,9 @@ size_t voxel_sort_hist_elems(int max_n);
 struct VoxelSortPlan { int buckets, samples, width, strata; };
 VoxelSortPlan voxel_sort_plan(int n);
 // sort + one centroid per voxel: out[0 .. *n_out) in key order, *n_out (device) = number of occupied voxels
-void launch_voxel_sort_centroids(const VoxelSortBuffers& vb, const float4* pts, int n, float4* out, int* n_out, hipStream_t s);
+// (inten != nullptr: the intensity of every voxel as well, summed like the four floats of the point)
+void launch_voxel_sort_centroids(const VoxelSortBuffers& vb, const float4* pts, int n, float4* out, int* n_out, hipStream_t s,
+                                 const float* inten = nullptr, float* inten_out = nullptr);
 void sort_pairs_u32(void* temp, size_t temp_bytes, const unsigned int* kin, unsigned int* kout, const unsigned int* vin,
                     unsigned int* vout, int n, hipStream_t s);
 void inclusive_scan_u32(void* temp, size_t temp_bytes, const unsigned int* in, unsigned int* out, int n, hipStream_t s);

@@ -28,6 +28,11 @@ __device__ __forceinline__ unsigned int publish_count(bool sel, unsigned int* s_
 // ballots: ascending index, the same on every run - never the arrival order of a counter.
 // The save buffer's append offset ping-pongs between two words (a.save_ctl[par] is read by everybody, [par ^ 1] written by one
 // lane: no lane reads what another writes in this launch); a scan that does not fit writes nothing and raises a.save_ctl[2].
+// LII_PUB_INTENSITY: the workgroups of the scan also hand its intensities on - to a.dense_int, and to a.save_int at the offset and under
+// the fits / does-not-fit decision of the cloud's append (this launch owns the offset: one behind it would read a moved one; a scan
+// without intensities appends 0.0f, the two buffers stay aligned) -, those of the down-sampled cloud a.body_int to a.down_int.  With the
+// five pointers null the launch is the INT = false instantiation: the kernel without the channel, instruction for instruction.
+template <bool INT>
 __global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps_val) {
   const IekfCtrl* __restrict__ guard = a.guard;
   const PoseArg ps = load_pose(guard != nullptr, reinterpret_cast<const PoseArg*>(guard), ps_val);
@@ -51,6 +56,11 @@ __global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps
     const float4 o = make_float4(wx, wy, wz, p.w);
     if (a.dense) a.dense[i] = o;
     if (fits) a.save[(size_t)off + i] = o;
+    if (INT && (a.dense_int || a.save_int)) {
+      const float q = a.scan_int ? a.scan_int[i] : 0.f;
+      if (a.dense_int) a.dense_int[i] = q;
+      if (fits && a.save_int) a.save_int[(size_t)off + i] = q;
+    }
     return;
   }
   if (!go) return;  // (every workgroup of the launch takes the same way: nobody waits for a word that never comes)
@@ -66,6 +76,7 @@ __global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps
     body_to_world(ps, p, wx, wy, wz);
     o = make_float4(wx, wy, wz, p.w);
     if (a.down) a.down[j] = o;
+    if (INT && a.down_int) a.down_int[j] = a.body_int[j];
   }
   const int n_down_blocks = (int)gridDim.x - a.dense_blocks;
   if (!a.effect) {
@@ -100,7 +111,8 @@ __global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps
 void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s) {
   const int blocks = a.dense_blocks + down_blocks;
   if (blocks <= 0) return;
-  hipLaunchKernelGGL(k_publish_world, dim3((unsigned int)blocks), dim3(256), 0, s, a, ps);
+  if (a.dense_int || a.save_int || a.down_int) hipLaunchKernelGGL(k_publish_world<true>, dim3((unsigned int)blocks), dim3(256), 0, s, a, ps);
+  else hipLaunchKernelGGL(k_publish_world<false>, dim3((unsigned int)blocks), dim3(256), 0, s, a, ps);
 }
 
 }  // namespace lii

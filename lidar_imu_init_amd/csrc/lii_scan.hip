@@ -90,11 +90,17 @@ __global__ __launch_bounds__(256) void k_sort_keys(const float4* __restrict__ pt
   idx[i] = (unsigned int)i;
 }
 // dst[i] = src[idx[i]], all four floats as they are.  Never in place: dst is another buffer than src.
-__global__ __launch_bounds__(256) void k_sort_gather(const float4* __restrict__ src, const unsigned int* __restrict__ idx, int n, float4* __restrict__ dst) {
+// INT: the scan carries intensities (lii_scan_intensity_*): they move by the same idx, inten_dst another buffer than inten_src.
+template <bool INT>
+__global__ __launch_bounds__(256) void k_sort_gather(const float4* __restrict__ src, const unsigned int* __restrict__ idx, int n, float4* __restrict__ dst,
+                                                     const float* __restrict__ inten_src, float* __restrict__ inten_dst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const unsigned int j = idx[i];
-  if (j < (unsigned int)n) dst[i] = src[j];  // (idx is a permutation of 0 .. n - 1: the sort only moves what k_sort_keys wrote)
+  if (j < (unsigned int)n) {  // (idx is a permutation of 0 .. n - 1: the sort only moves what k_sort_keys wrote)
+    dst[i] = src[j];
+    if (INT) inten_dst[i] = inten_src[j];
+  }
 }
 // (f2ord, ord2f and exp_so3 - Exp(ang_vel, dt), include/so3_math.h:37-59 - live in lii_device.h: lii_imu.hip shares them)
 struct UndistArg {
@@ -775,17 +781,22 @@ __device__ __forceinline__ unsigned int block_rank_of_flag(bool f, unsigned int*
 // *crowded (written by vh_insert when a point goes to a list): the host reads it behind the filter and takes the sort path from
 // then on when voxels hold dozens of points (a large leaf) - the owner orders the members by repeated selection, quadratic in
 // their number.
-template <bool ABS>
+// INT: the scan carries intensities (inten[i] beside pts[i]): the owner adds its members' in the order it adds their points - from 0.f,
+// __fadd_rn, divided by the count: the `intensity` field of PCL's centroid - and writes the voxel's to inten_out at the voxel's place.  It
+// has to happen here: the owner frees the slot, nobody can walk the members afterwards.  INT = false is the code without the channel.
+template <bool ABS, bool INT>
 __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ pts, int n, VhTable tb, unsigned long long* __restrict__ counts,
                                                     unsigned int epoch, float4* __restrict__ out, int* __restrict__ n_out,
                                                     unsigned int* __restrict__ pcl_out, const unsigned int* __restrict__ bbox_rows,
-                                                    int n_rows, float leaf, int* __restrict__ filtered, int test_late) {
+                                                    int n_rows, float leaf, int* __restrict__ filtered, int test_late,
+                                                    const float* __restrict__ inten, float* __restrict__ inten_out) {
   __shared__ unsigned int s_w[4], s_sum[12];
   const int tid = threadIdx.x, i = blockIdx.x * blockDim.x + tid;
   // everything a lane needs of its own point is requested at once: the point, its slot, and (dependent) the slot's line
   const bool in_range = i < n;
   const float4 p0 = in_range ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   const unsigned int slot = in_range ? tb.slot_of[i] : kVhEmpty;
+  const float q0 = (INT && in_range) ? inten[i] : 0.f;
   VoxelArg v;
   v.identity = 0;
   if (ABS) {
@@ -823,6 +834,7 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
   if (tid == 0 && !hold) __hip_atomic_store(counts + blockIdx.x, ((unsigned long long)epoch << 32) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (ABS && v.identity && !ident_part) {  // (uniform) the cloud passes unfiltered; the voxels' owners still hand their slots back
     if (in_range) { out[i] = p0; pcl_out[i] = (unsigned)i; }
+    if (INT && in_range) inten_out[i] = q0;
     if (blockIdx.x == gridDim.x - 1 && tid == 0) *n_out = n;
     if (first) {
       uint4* line = reinterpret_cast<uint4*>(sl);
@@ -832,9 +844,11 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
     return;
   }
   float4 cen = make_float4(0.f, 0.f, 0.f, 0.f);
+  float cen_i = 0.f;
   if (first) {
     const unsigned int cnt = ident_part ? 1u : hd.y + 1u;  // points of the voxel, this one included
     float sx = __fadd_rn(0.f, p0.x), sy = __fadd_rn(0.f, p0.y), sz = __fadd_rn(0.f, p0.z), st = __fadd_rn(0.f, p0.w);
+    float si = INT ? __fadd_rn(0.f, q0) : 0.f;
     unsigned int m[kVhMembers] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y};
 #pragma unroll
     for (int k = 0; k < kVhMembers; k++)
@@ -848,11 +862,13 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
         if (m[k] == (unsigned)i || m[k] == kVhEmpty) continue;
         const float4 p = pts[m[k]];
         sx = __fadd_rn(sx, p.x); sy = __fadd_rn(sy, p.y); sz = __fadd_rn(sz, p.z); st = __fadd_rn(st, p.w);
+        if (INT) si = __fadd_rn(si, inten[m[k]]);
       }
       for (unsigned int j = hd.z; j != kVhEmpty; j = tb.next[j]) {
         if (j == (unsigned)i) continue;
         const float4 p = pts[j];
         sx = __fadd_rn(sx, p.x); sy = __fadd_rn(sy, p.y); sz = __fadd_rn(sz, p.z); st = __fadd_rn(st, p.w);
+        if (INT) si = __fadd_rn(si, inten[j]);
       }
     } else if (cnt > 1u) {
       // the members in input order: every round takes the smallest index above the last one taken (the owner's own index is
@@ -867,12 +883,14 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
         for (unsigned int j = head; j != kVhEmpty; j = tb.next[j]) best = (j > last && j < best) ? j : best;
         const float4 p = pts[best];
         sx = __fadd_rn(sx, p.x); sy = __fadd_rn(sy, p.y); sz = __fadd_rn(sz, p.z); st = __fadd_rn(st, p.w);
+        if (INT) si = __fadd_rn(si, inten[best]);
         last = best;
       }
     }
     const float c = (float)cnt;
     // a single-point voxel reproduces the point exactly (x / 1.0f == x), which is also what the identity path needs
     cen = make_float4(sx / c, sy / c, sz / c, st / c);
+    if (INT) cen_i = si / c;
   }
   // owners in the workgroups below this one; a block whose word is overdue is counted here: which of its points own their voxel
   // (one 16-byte request per point decides it, as above; a slot its owner - a point of another block - has freed already reads
@@ -911,6 +929,7 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
   if (!first) return;
   const unsigned int pos = base + rank;
   out[pos] = cen;
+  if (INT) inten_out[pos] = cen_i;
   if (ident_part) {
     pcl_out[pos] = (unsigned)i;
   } else if (ABS) {
@@ -942,8 +961,10 @@ void launch_time_extent(const float4* pts, int n, unsigned long long* extent, un
 void launch_sort_keys(const float4* pts, int n, unsigned int* key, unsigned int* idx, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_sort_keys, dim3(nblk(n, 256)), dim3(256), 0, s, pts, n, key, idx);
 }
-void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_sort_gather, dim3(nblk(n, 256)), dim3(256), 0, s, src, idx, n, dst);
+void launch_sort_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s, const float* inten_src, float* inten_dst) {
+  if (n <= 0) return;
+  if (inten_src && inten_dst) hipLaunchKernelGGL(k_sort_gather<true>, dim3(nblk(n, 256)), dim3(256), 0, s, src, idx, n, dst, inten_src, inten_dst);
+  else hipLaunchKernelGGL(k_sort_gather<false>, dim3(nblk(n, 256)), dim3(256), 0, s, src, idx, n, dst, nullptr, nullptr);
 }
 void launch_voxel_minmax(const float4* pts, int n, unsigned int* mm, unsigned int* mm_next, hipStream_t s) {
   int nb = nblk(n, 256 * 4);
@@ -1060,13 +1081,18 @@ void launch_voxel_hash_clear(const VoxelHashBuffers& vh, size_t slots, hipStream
 // (the table is keyed by absolute voxel coordinates).  epoch: the number of this filter run (never 0; VoxelHashBuffers::counts).
 void launch_voxel_hash(const VoxelHashBuffers& vh, const float4* pts, int n, const unsigned int* mm, const unsigned int* bbox_rows,
                        int n_rows, float leaf, float4* out, int* n_out, int* filtered, unsigned int* pcl_out, int stages, unsigned int epoch,
-                       hipStream_t s, int test_late) {
+                       hipStream_t s, int test_late, const float* inten, float* inten_out) {
   if (n <= 0) return;
+  const bool wi = inten != nullptr && inten_out != nullptr;
   const VhTable tb = vh_table(&vh, n, (stages & 4) != 0);
   const int nb = nblk(n, 256);
   if (stages & 1) hipLaunchKernelGGL(k_vhash_insert, dim3(nb), dim3(256), 0, s, pts, n, mm, bbox_rows, n_rows, leaf, tb, filtered);
-  if (stages & 2) hipLaunchKernelGGL(k_vhash_emit<false>, dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, nullptr, 0, leaf, filtered, test_late);
-  if (stages & 4) hipLaunchKernelGGL(k_vhash_emit<true>, dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, bbox_rows, n_rows, leaf, filtered, test_late);
+  const float* const no_in = nullptr;
+  float* const no_out = nullptr;
+  if ((stages & 2) && !wi) hipLaunchKernelGGL((k_vhash_emit<false, false>), dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, nullptr, 0, leaf, filtered, test_late, no_in, no_out);
+  if ((stages & 2) && wi) hipLaunchKernelGGL((k_vhash_emit<false, true>), dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, nullptr, 0, leaf, filtered, test_late, inten, inten_out);
+  if ((stages & 4) && !wi) hipLaunchKernelGGL((k_vhash_emit<true, false>), dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, bbox_rows, n_rows, leaf, filtered, test_late, no_in, no_out);
+  if ((stages & 4) && wi) hipLaunchKernelGGL((k_vhash_emit<true, true>), dim3(nb), dim3(256), 0, s, pts, n, tb, vh.counts, epoch, out, n_out, pcl_out, bbox_rows, n_rows, leaf, filtered, test_late, inten, inten_out);
 }
 size_t voxel_hash_slots(int max_n) {
   size_t slots = 1024;

@@ -386,13 +386,15 @@ __global__ __launch_bounds__(512) void k_vsort_small(const u64* __restrict__ key
 // One lane per voxel start accumulates its run sequentially in index order, float32, then divides by the count — the
 // order the oracle uses.  A run may continue past the end of the group (a voxel split by a splitter): the lane just keeps
 // reading the sorted arrays.
-template <int kGroup>
+// INT: the scan carries intensities: every voxel's is summed beside its four floats (the same order, from 0.f) and divided by the count.
+template <int kGroup, bool INT>
 __global__ __launch_bounds__(256) void k_voxel_centroids(const float4* __restrict__ pts, const u64* __restrict__ keys,
                                                           const unsigned int* __restrict__ idx,
                                                           const unsigned int* __restrict__ bucket_start, int B, int n,
                                                           const unsigned int* __restrict__ group_count, float4* __restrict__ out,
                                                           int* __restrict__ n_out, const unsigned int* __restrict__ pcl_in,
-                                                          unsigned int* __restrict__ pcl_out, unsigned int* __restrict__ max_run) {
+                                                          unsigned int* __restrict__ pcl_out, unsigned int* __restrict__ max_run,
+                                                          const float* __restrict__ inten, float* __restrict__ inten_out) {
   __shared__ unsigned int wtot[4], s_sum[4];
   const int tid = threadIdx.x, g = blockIdx.x;
   const int b0 = g * kGroup, b1 = min(b0 + kGroup, B);
@@ -421,17 +423,21 @@ __global__ __launch_bounds__(256) void k_voxel_centroids(const float4* __restric
     if (flag) {
       const float4 p0 = pts[id0];
       float sx = __fadd_rn(0.f, p0.x), sy = __fadd_rn(0.f, p0.y), sz = __fadd_rn(0.f, p0.z), st = __fadd_rn(0.f, p0.w);
+      float si = INT ? __fadd_rn(0.f, inten[id0]) : 0.f;
       unsigned int j = i + 1;
       if (k_next == k) {  // the run goes on (a second point of the voxel follows): the general walk
         for (; j < (unsigned int)n && keys[j] == k; j++) {
-          const float4 p = pts[idx[j]];
+          const unsigned int idj = idx[j];
+          const float4 p = pts[idj];
           sx = __fadd_rn(sx, p.x); sy = __fadd_rn(sy, p.y); sz = __fadd_rn(sz, p.z); st = __fadd_rn(st, p.w);
+          if (INT) si = __fadd_rn(si, inten[idj]);
         }
       }
       if (max_run && j - i > 8u) atomicMax(max_run, j - i);  // (the host picks the hashed filter for sparse voxels: lii_capi.cpp)
       const float c = (float)(j - i);
       // a single-point voxel reproduces the point exactly (x / 1.0f == x), which is also what the identity path needs
       out[slot] = make_float4(sx / c, sy / c, sz / c, st / c);
+      if (INT) inten_out[slot] = si / c;
       pcl_out[slot] = pcl_in[id0];
     }
   }
@@ -459,14 +465,27 @@ VoxelSortPlan voxel_sort_plan(int n) {
   return p;
 }
 
-void launch_voxel_sort_centroids(const VoxelSortBuffers& vb, const float4* pts, int n, float4* out, int* n_out, hipStream_t s) {
+namespace {
+template <int kG>
+void launch_centroids(int blocks, hipStream_t s, const VoxelSortBuffers& vb, const float4* pts, const unsigned int* bucket_start, int B, int n,
+                      const unsigned int* group_count, float4* out, int* n_out, const float* inten, float* inten_out) {
+  if (inten && inten_out)
+    hipLaunchKernelGGL((k_voxel_centroids<kG, true>), dim3(blocks), dim3(256), 0, s, pts, vb.keys_out, vb.idx_out, bucket_start, B, n, group_count, out, n_out,
+                       vb.pcl_in, vb.pcl_out, vb.max_run, inten, inten_out);
+  else
+    hipLaunchKernelGGL((k_voxel_centroids<kG, false>), dim3(blocks), dim3(256), 0, s, pts, vb.keys_out, vb.idx_out, bucket_start, B, n, group_count, out, n_out,
+                       vb.pcl_in, vb.pcl_out, vb.max_run, static_cast<const float*>(nullptr), static_cast<float*>(nullptr));
+}
+}  // namespace
+
+void launch_voxel_sort_centroids(const VoxelSortBuffers& vb, const float4* pts, int n, float4* out, int* n_out, hipStream_t s, const float* inten,
+                                 float* inten_out) {
   if (n <= 0) return;
   unsigned int *tot = vb.hist, *cursor = vb.hist + kMaxBuckets, *bucket_start = vb.hist + 2 * kMaxBuckets,
                *group_count = vb.hist + 3 * kMaxBuckets + 2;
   if (n <= 512) {
     hipLaunchKernelGGL(k_vsort_small, dim3(1), dim3(512), 0, s, vb.keys_in, n, vb.keys_out, vb.idx_out, bucket_start, group_count);
-    hipLaunchKernelGGL(k_voxel_centroids<kGroup>, dim3(1), dim3(256), 0, s, pts, vb.keys_out, vb.idx_out, bucket_start, kGroup, n,
-                       group_count, out, n_out, vb.pcl_in, vb.pcl_out, vb.max_run);
+    launch_centroids<kGroup>(1, s, vb, pts, bucket_start, kGroup, n, group_count, out, n_out, inten, inten_out);
     return;
   }
   const VoxelSortPlan p = voxel_sort_plan(n);
@@ -481,13 +500,11 @@ void launch_voxel_sort_centroids(const VoxelSortBuffers& vb, const float4* pts, 
   if (n <= B * 64) {  // buckets of ~<= 64 pairs: four to a workgroup
     hipLaunchKernelGGL(k_vsort_local<kGroup>, dim3(groups), dim3(256), 0, s, vb.comp, bucket_start, B, tot, cursor, vb.keys_out,
                        vb.idx_out, group_count);
-    hipLaunchKernelGGL(k_voxel_centroids<kGroup>, dim3(groups), dim3(256), 0, s, pts, vb.keys_out, vb.idx_out, bucket_start, B, n,
-                       group_count, out, n_out, vb.pcl_in, vb.pcl_out, vb.max_run);
+    launch_centroids<kGroup>(groups, s, vb, pts, bucket_start, B, n, group_count, out, n_out, inten, inten_out);
   } else {  // the bucket count is capped (n > 131 k): larger buckets, one to a workgroup
     hipLaunchKernelGGL(k_vsort_local<1>, dim3(B), dim3(256), 0, s, vb.comp, bucket_start, B, tot, cursor, vb.keys_out, vb.idx_out,
                        group_count);
-    hipLaunchKernelGGL(k_voxel_centroids<1>, dim3(B), dim3(256), 0, s, pts, vb.keys_out, vb.idx_out, bucket_start, B, n, group_count,
-                       out, n_out, vb.pcl_in, vb.pcl_out, vb.max_run);
+    launch_centroids<1>(B, s, vb, pts, bucket_start, B, n, group_count, out, n_out, inten, inten_out);
   }
 }
 
