@@ -132,6 +132,35 @@ int lii_map_size(lii_handle h, int32_t* n_valid);
 int lii_map_download(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n);
 /* Kept for callers of ABI 1: the device map is always current (updates are applied in place); waits for the stream. */
 int lii_map_commit(lii_handle h);
+/* lii_map_nearest <- ikdtree.Nearest_Search(point, k_nearest, Nearest_Points, Point_Distance, max_dist) for arbitrary points, k and
+ *                  max_dist  (include/ikd-Tree/ikd_Tree.cpp:349-379, :825-968; the registration pass searches the handle's own
+ *                  down-sampled cloud with k = 5 and max_match_dist2 and needs none of this).
+ * Query i (float xyz every stride_bytes, as for lii_map_build) receives the min(k, m) nearest of the m map points with
+ * d2 <= max_dist - inclusive, and the SQUARED distance against max_dist itself, as the reference compares (quirk A5) - ascending in
+ * d2, where d2 is the reference's float32 calc_dist (dx*dx + dy*dy + dz*dz, left to right, no FMA): rows i*k .. i*k + count[i] - 1 of
+ * pts (3 floats a row) and d2; the rows from count[i] on are written as zeros.  Among EQUAL d2 the order - and, at the end of a full
+ * list, which of them is kept - is the library's own visiting order: deterministic for a given map state, otherwise unspecified (the
+ * reference keeps whichever its tree visits first).  The distances are never ambiguous.  pts / d2 may be NULL (that output is not
+ * wanted); count is required.
+ * LII_ERR_INVALID, nothing written: k < 1 or k > 64; max_dist NaN, infinite or < 1 (the reference prunes sub-trees at
+ * box_d2 > max_dist^2, which is tighter than its acceptance test below 1: its answer then depends on the shape of its tree, and the
+ * library refuses instead of inventing a rule); sqrt(max_dist) > 32 map_cell_size (the ball would span more cells than a query
+ * should walk - create the handle with a larger lii_config::map_cell_size); a bad stride; NULL queries with n > 0.  No map:
+ * LII_ERR_STATE.  n == 0: LII_OK.  A query with a NaN coordinate gets count 0; one whose ball leaves the addressable grid is
+ * searched over the cells that exist (no map point lies outside them).
+ * The call is an OBSERVER: scan, down-sampled cloud, neighbour lists, IMU carry and publish order of the handle stay as they are, and
+ * a registration behind it behaves as if it had not been made.  It ends a pre-armed launch and joins a map update in flight first
+ * (never a map with a pending update or parked inserts); it works with a communicator attached (the map is replicated, the query
+ * local) and under LII_TEST=host_solve.
+ *   lii_map_nearest      host queries, host results, synchronous.  n is processed in chunks of at most 65 536 queries and 2^20 rows
+ *                        (queries x k) through staging buffers of the handle - created by the first call, grown geometrically, never
+ *                        more than 17 MiB of device and 17 MiB of pinned host memory, released with the handle.
+ *   lii_map_nearest_dev  queries and results in device memory of the caller (lii_dev_alloc, a tensor's data_ptr): enqueued on the
+ *                        handle's stream, returns without waiting - lii_synchronize or any later synchronous call orders it. */
+int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
+                    float* pts_out /* n*k*3 */, float* d2_out /* n*k */, int32_t* count_out /* n */);
+int lii_map_nearest_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
+                        float* pts_dev, float* d2_dev, int32_t* count_dev);
 
 /* ---------------------------------------------------------------- scan in / undistortion / down-sampling
  * lii_scan_upload: host AoS -> device float4 (x,y,z,t_ms).  For pcl::PointXYZINormal use stride 48,

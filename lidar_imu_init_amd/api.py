@@ -125,6 +125,8 @@ _DECLS = {
     "lii_map_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_map_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_commit": (C.c_int, [C.c_void_p]),
+    "lii_map_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_map_nearest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_scan_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_upload_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_advance": (C.c_int, [C.c_void_p]),
@@ -252,6 +254,16 @@ def _ptr(a):
     # the raw address (ctypes converts an int for a c_void_p parameter); ndarray.ctypes.data_as() is two orders of
     # magnitude slower once a large framework is loaded in the process (measured: 60 us per call next to torch)
     return a.__array_interface__["data"][0]
+
+
+def _dev_address(a):
+    """The device address behind `a`: an int, a ctypes pointer, None, or anything with __cuda_array_interface__ (a torch tensor)."""
+    if a is None:
+        return None
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        return int(cai["data"][0])
+    return int(getattr(a, "value", a) or 0) or None
 
 
 def data_sufficiency(omg, data_accum_length):
@@ -407,6 +419,35 @@ class Registrar:
 
     def map_commit(self):
         self._check(self.L.lii_map_commit(self.h))
+
+    def map_nearest(self, q, k=5, max_dist=5.0):
+        """ikdtree.Nearest_Search for the points q (n, >= 3) float: the min(k, m) nearest of the m map points with d2 <= max_dist
+        (the SQUARED distance against max_dist, as the reference compares), ascending.  Returns (pts (n, k, 3), d2 (n, k), count (n,));
+        the rows from count[i] on are zeros.  Leaves the handle's scan, neighbour lists and everything else of a registration alone."""
+        q = np.asarray(q, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n, k = len(q), int(k)
+        pts = np.zeros((n, max(k, 0), 3), np.float32)
+        d2 = np.zeros((n, max(k, 0)), np.float32)
+        cnt = np.zeros(n, np.int32)
+        self._check(self.L.lii_map_nearest(self.h, _ptr(q) if n else None, n, q.strides[0] if n else 12, k, float(max_dist),
+                                           _ptr(pts), _ptr(d2), _ptr(cnt)))
+        return pts, d2, cnt
+
+    def dev_alloc(self, nbytes: int) -> int:
+        """nbytes of device memory of the library's (lii_dev_alloc), released with the Registrar; returns the address."""
+        p = C.c_void_p()
+        self._check(self.L.lii_dev_alloc(self.h, max(int(nbytes), 16), C.byref(p)))
+        self._dev_bufs.append(p)
+        return int(p.value)
+
+    def map_nearest_dev(self, q_dev, n, k, max_dist, pts_dev, d2_dev, count_dev, stride_bytes=12):
+        """map_nearest with queries and results in device memory the caller owns - raw addresses, or objects with
+        __cuda_array_interface__ (torch tensors): float xyz every stride_bytes in, (n, k, 3) float32 / (n, k) float32 / (n,) int32 out
+        (pts_dev / d2_dev may be None).  Enqueued on the handle's stream; synchronize() - or any synchronous call - orders it."""
+        self._check(self.L.lii_map_nearest_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), int(k), float(max_dist),
+                                               _dev_address(pts_dev), _dev_address(d2_dev), _dev_address(count_dev)))
 
     # ------------------------------------------------------------------ scan
     def scan_upload(self, pts):

@@ -573,6 +573,106 @@ int lii_map_commit(lii_handle h) {
   return LII_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ map queries (kernel: lii_query.hip)
+namespace {
+struct NearestPlan {
+  float max_d2;  // the largest float <= max_dist: `float d2 <= double max_dist` (Search, :842) in float
+  int r_max;     // rings of cells that cover the ball of radius sqrt(max_dist)
+};
+// The argument rules both forms share; LII_OK with n == 0 means "nothing to do".  Nothing has been touched when this fails.
+int nearest_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int32_t stride_bytes, int32_t k, double max_dist, const void* count_out,
+                 NearestPlan* plan) {
+  if (!h) return LII_ERR_INVALID;
+  if ((!xyz && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4 || !count_out)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments (queries, n >= 0, stride a multiple of 4 and >= 12, count_out)");
+  if (k < 1 || k > 64) return fail(h, LII_ERR_INVALID, std::string(who) + ": k must be 1 .. 64");
+  // max_dist < 1: the reference prunes sub-trees at box_d2 > max_dist^2 (:828), tighter than it accepts points there - its answer then
+  // depends on the shape of its tree, and there is no rule to reproduce
+  if (!(max_dist >= 1.0) || !std::isfinite(max_dist)) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_dist must be finite and >= 1 (it bounds the SQUARED distance)");
+  const double cells = std::sqrt(max_dist) / double(h->cell_size);
+  if (cells > 32.0) {
+    char msg[256];
+    std::snprintf(msg, sizeof(msg), "%s: a ball of radius sqrt(max_dist) = %.3f m spans more than 32 grid cells of %.3f m; create the handle with a larger map_cell_size",
+                  who, std::sqrt(max_dist), double(h->cell_size));
+    return fail(h, LII_ERR_INVALID, msg);
+  }
+  float md = float(max_dist);
+  if (double(md) > max_dist) md = std::nextafterf(md, 0.f);
+  plan->max_d2 = md;
+  plan->r_max = int(std::ceil(cells)) + 1;
+  return LII_OK;
+}
+// ... and what both need from the handle: no pre-armed launch on the stream, no map update pending or parked, a map
+int nearest_map(lii_handle h, const char* who) {
+  const int rc = commit_map(h);
+  if (rc != LII_OK) return rc;
+  if (h->n_map <= 0 && !h->map_dirty) return fail(h, LII_ERR_STATE, std::string(who) + ": no map");
+  return LII_OK;
+}
+void nearest_launch(lii_handle h, const NearestPlan& plan, const void* q_dev, int n, int stride_bytes, int k, float* pts_dev, float* d2_dev, int* count_dev) {
+  const size_t entries = std::min<size_t>(h->cells_cap_blocks * 512, 0xFFFFFFFFu);
+  launch_map_nearest(grid_view(h), (unsigned int)entries, h->pts_cap, q_dev, n, stride_bytes, k, plan.max_d2, plan.r_max, pts_dev, d2_dev, count_dev, h->stream);
+}
+}  // namespace
+
+int lii_map_nearest_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, int32_t k, double max_dist, float* pts_dev, float* d2_dev,
+                        int32_t* count_dev) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  NearestPlan plan;
+  int rc = nearest_plan(h, "lii_map_nearest_dev", xyz_dev, n, stride_bytes, k, max_dist, count_dev, &plan);
+  if (rc != LII_OK || n == 0) return rc;
+  rc = nearest_map(h, "lii_map_nearest_dev");
+  if (rc != LII_OK) return rc;
+  nearest_launch(h, plan, xyz_dev, n, stride_bytes, k, pts_dev, d2_dev, count_dev);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+
+int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t k, double max_dist, float* pts_out, float* d2_out,
+                    int32_t* count_out) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  NearestPlan plan;
+  int rc = nearest_plan(h, "lii_map_nearest", xyz, n, stride_bytes, k, max_dist, count_out, &plan);
+  if (rc != LII_OK || n == 0) return rc;
+  rc = nearest_map(h, "lii_map_nearest");
+  if (rc != LII_OK) return rc;
+  using MQ = lii_context::MapQuery;
+  // a chunk: at most kQueriesMax queries and kRowsMax rows - the staging stays bounded whatever n is
+  const size_t chunk = std::min<size_t>(std::min<size_t>(size_t(n), MQ::kQueriesMax), MQ::kRowsMax / size_t(k));
+  if (chunk * size_t(k) > h->mq.rows) {
+    // (grown geometrically, so that a host whose batches creep upwards frees - hipFree waits for the device - a handful of times at most)
+    const size_t rows = std::min(std::max(chunk * size_t(k), 2 * h->mq.rows), MQ::kRowsMax);
+    const size_t bytes = 16 * std::min(rows, MQ::kQueriesMax) + 16 * rows;
+    h->mq.rows = 0;
+    h->mq.h_buf.reset();
+    HIPCHK(h, h->mq.d_buf.grow(bytes));
+    HIPCHK(h, h->mq.h_buf.alloc(bytes, hipHostMallocDefault));
+    h->mq.rows = rows;
+  }
+  const size_t q_cap = std::min(h->mq.rows, MQ::kQueriesMax);
+  const size_t off_cnt = 12 * q_cap, off_pts = 16 * q_cap, off_d2 = off_pts + 12 * h->mq.rows;
+  unsigned char *hb = h->mq.h_buf, *db = h->mq.d_buf;
+  hipStream_t s = h->stream;
+  const char* src = static_cast<const char*>(xyz);
+  for (size_t at = 0; at < size_t(n); at += chunk) {
+    const size_t m = std::min(chunk, size_t(n) - at), rows = m * size_t(k);
+    float* hq = reinterpret_cast<float*>(hb);
+    for (size_t i = 0; i < m; i++) std::memcpy(hq + 3 * i, src + (at + i) * size_t(stride_bytes), 12);
+    HIPCHK(h, hipMemcpyAsync(db, hb, 12 * m, hipMemcpyHostToDevice, s));
+    nearest_launch(h, plan, db, int(m), 12, k, pts_out ? reinterpret_cast<float*>(db + off_pts) : nullptr, d2_out ? reinterpret_cast<float*>(db + off_d2) : nullptr,
+                   reinterpret_cast<int*>(db + off_cnt));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hb + off_cnt, db + off_cnt, 4 * m, hipMemcpyDeviceToHost, s));
+    if (pts_out) HIPCHK(h, hipMemcpyAsync(hb + off_pts, db + off_pts, 12 * rows, hipMemcpyDeviceToHost, s));
+    if (d2_out) HIPCHK(h, hipMemcpyAsync(hb + off_d2, db + off_d2, 4 * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    std::memcpy(count_out + at, hb + off_cnt, 4 * m);
+    if (pts_out) std::memcpy(pts_out + 3 * at * size_t(k), hb + off_pts, 12 * rows);
+    if (d2_out) std::memcpy(d2_out + at * size_t(k), hb + off_d2, 4 * rows);
+  }
+  return LII_OK;
+}
+
 
 int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, int32_t* n_no_downsample) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)

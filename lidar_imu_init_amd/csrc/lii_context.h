@@ -101,6 +101,14 @@ struct lii_context {
   PinnedBuf<int> n_map_pinned;  // small pinned scratch for H2D of counters
   float cell_size = 0.3f;
   DevBuf<unsigned char> d_sort_temp;  // temporary storage of the sorts and scans (size(): bytes)
+  // lii_map_nearest (host form): staging for one chunk of queries and its results, device and pinned, laid out alike (queries |
+  // counts | points | d2).  Created by the first call, grown geometrically up to kRowsMax rows (17 MiB each), kept until the handle goes.
+  struct MapQuery {
+    static constexpr size_t kQueriesMax = 65536, kRowsMax = size_t(1) << 20;  // per chunk: queries, and rows (queries x k)
+    DevBuf<unsigned char> d_buf;
+    PinnedBuf<unsigned char> h_buf;
+    size_t rows = 0;  // both hold min(rows, kQueriesMax) queries and `rows` result rows
+  } mq;
 
   // ---- scan
   DevBuf<float4> d_scan;   // raw / undistorted (x,y,z,t_ms)

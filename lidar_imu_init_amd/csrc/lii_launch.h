@@ -44,6 +44,12 @@ void launch_win_bbox(const BlockEntry* blocks, unsigned int cap, unsigned int* b
 void launch_win_fill(const BlockEntry* blocks, unsigned int cap, const uint2* cells, uint2* win, const int org[3], const int dim[3], hipStream_t s);
 void launch_cells_fill(const unsigned long long* keys, const unsigned int* ranks, int n, BlockEntry* blocks,
                        unsigned int block_mask, uint2* cells, unsigned long long* key_of_id, hipStream_t s);
+// map queries (lii_query.hip): Nearest_Search for n points (float xyz every stride_bytes, device memory), one wavefront each.
+// n_entries / pts_cap: the sizes of the cell tables (entries) and of the point array (slots) behind `g`; max_d2: the largest float
+// that is <= max_dist; r_max: rings of cells that cover the ball (ceil(sqrt(max_dist) / cell) + 1).  Row i * k + j of pts_out (3 floats)
+// / d2_out: neighbour j of query i, zeros from count_out[i] on; pts_out / d2_out may be nullptr.
+void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, int k,
+                        float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s);
 // registration: the search launch (lii_knn.hip)
 // (`pose`: device memory on every path - a host-driven pass uploads it first)
 // epoch: the number of this search launch (> 0, RegistrationBuffers::flag_*) and of the fit launch behind it; 0: no list of unfinished queries
