@@ -185,6 +185,8 @@ struct lii_replay {
   std::vector<float> pub_cloud[4];   // the last scan's clouds, by bit of lii_publish_opts::clouds
   std::vector<float> pcl_wait_save;  // what the last flush handed over (the reference writes it to a PCD file)
   int32_t pcd_index = 0;             // flushes so far
+  // lii_replay_set_local_map: lasermap_fov_segment (:914) + the box delete; off by default
+  bool local_map = false, lm_placed = false, lm_in_job = false;
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -252,6 +254,17 @@ int lii_replay_set_publish(lii_replay* r, int32_t clouds, int32_t save_interval)
   r->pub_clouds = clouds;
   r->pub_save_interval = save_interval;
   r->pub_placed = false;
+  return LII_OK;
+}
+// 1: the moving local map (src/laserMapping.cpp:260-305, called at :914, with the Delete_Point_Boxes call upstream never made): cube_side_length
+// and mapping/det_range of the launch file go to lii_local_map_set before the first scan is processed - enabled where the registration goes
+// through the one-call forms of lii_replay_set_device_imu, which then segment by themselves; the scans that take the separate path (the scan
+// that seeds the map, and every scan of the host-propagated path) call lii_local_map_segment with the propagated position.  0 (default):
+// process() makes the calls it made before.
+int lii_replay_set_local_map(lii_replay* r, int32_t on) {
+  if (!r) return LII_ERR_INVALID;
+  r->local_map = on != 0;
+  r->lm_placed = false;
   return LII_OK;
 }
 // cloud: one LII_PUB_* bit, or 0 for what the last flush of the save buffer handed over; the last processed scan's points -> out
@@ -664,6 +677,23 @@ static int process(lii_replay* r) {
     if (rc != LII_OK) return fail(r, rc, std::string("lii_frame_select: ") + lii_last_error(r->h));
   }
   r->have_scan = true;
+  // ---- lasermap_fov_segment (:914): behind the propagation, in front of the voxel filter
+  if (r->local_map) {
+    if (!r->lm_placed) {
+      lii_local_map_opts lo{};
+      int rc = lii_params_local_map(&r->prm, &lo);
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_params_local_map: ") + lii_params_last_error());
+      r->lm_in_job = r->device_imu;
+      lo.enabled = r->lm_in_job ? 1 : 0;
+      rc = lii_local_map_set(r->h, &lo);
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_local_map_set: ") + lii_last_error(r->h));
+      r->lm_placed = true;
+    }
+    if (!r->map_built || !r->lm_in_job) {  // (no registration call that would segment by itself: `st` is the propagated state here)
+      const int rc = lii_local_map_segment(r->h, st.pos_end, nullptr);
+      if (rc != LII_OK) return fail(r, rc, std::string("lii_local_map_segment: ") + lii_last_error(r->h));
+    }
+  }
   // ---- the first scan seeds the map (:921-931): de-skew + voxel grid, pointBodyToWorld on the host, ikdtree.Build
   if (!r->map_built) {
     int rc = LII_OK;

@@ -128,6 +128,57 @@ int lii_map_add_points(lii_handle h, const void* xyz, int32_t n, int32_t stride_
  *                       prepares in lasermap_fov_segment, src/laserMapping.cpp:260-305, and never makes - quirk A6: its map only
  *                       grows).  boxes = n x 6 floats (min xyz, max xyz); a point goes when min <= p < max on every axis. */
 int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int32_t* n_deleted);
+/* ---- the moving local map: lasermap_fov_segment (src/laserMapping.cpp:260-305, called at :914 between p_imu->Process and the voxel
+ * filter) FOLLOWED BY Delete_Point_Boxes(cub_needrm) - the call upstream prepared and never made (quirk A6).  A cube of edge cube_len
+ * follows the sensor; when state.pos_end (the IMU's position, as upstream - not the LiDAR's) comes within 1.5 * det_range of a face the
+ * cube moves by mov_dist along that axis, and the slab it leaves behind - one box per axis, x, y, z, the low side tested before the high
+ * side - is deleted from the map (min <= p < max, the rule of lii_map_delete_boxes).  Without it nothing ever makes room in the map and a
+ * sensor that keeps travelling ends in LII_ERR_CAPACITY.  The arithmetic is the reference's: MOV_THRESHOLD = 1.5f, det_range a float,
+ * cube_len a double, the cube six floats; mov_dist = (float)max((cube_len - 2.0 * 1.5f * det_range) * 0.5 * 0.9, det_range * (1.5f - 1)).
+ *
+ * The setting is durable handle state (like lii_publish_set) and OFF until asked for; lii_scan_job is unchanged.
+ *   lii_local_map_set      installs cube_len / det_range and sets Localmap_Initialized = false (every call of it does: the next segment
+ *                          initialises the cube around its position).  enabled = 1: every lii_scan_register, lii_scan_register_imu and
+ *                          lii_scan_register_cv makes one lii_local_map_segment call itself, on the device, with the PROPAGATED state - the
+ *                          `state` argument of lii_scan_register, what the in-call propagation produced for the other two - behind any
+ *                          map update still in flight and in front of the call's first search: three launches of fixed size, whatever
+ *                          the map holds (lii_set_profiling(h, 3) counts them as LII_KP_VOXEL).  Calls that do not register are not
+ *                          touched (lii_iekf_update, the separate lii_undistort_* path, lii_map_build_from_scan): their hosts call
+ *                          lii_local_map_segment.  enabled = 0: only lii_local_map_segment segments.
+ *   lii_local_map_segment  one such call at pos_end; works without a map (the first scan: the cube is initialised, or moved with nothing
+ *                          to delete).  out == NULL: enqueued only - and, since nobody knows yet whether the cube moved, the neighbour
+ *                          lists and planes of an earlier search are not used again (call it where the reference does: in front of the
+ *                          scan's search); out != NULL: waits and reports (the lists are dropped when points were deleted).
+ *   lii_local_map_get      waits for the stream and reports the state after the last call that ran, in-job calls included.
+ * Refusals (nothing changed, an earlier setting stays in force).  LII_ERR_INVALID: NaN / infinite pos_end, cube_len or det_range;
+ * det_range <= 0; cube_len <= 3 * det_range - a sensor at the centre of a fresh cube is then inside the threshold of BOTH faces of every
+ * axis, the reference's arithmetic would move the cube on every scan and delete around the sensor; this includes the reference's own
+ * parameter defaults (cube_side_length 200, det_range 300: lii_params_defaults), which upstream survives only because it never deletes.
+ * The library refuses instead of inventing a rule.  LII_ERR_STATE: a communicator is attached (single rank for now; a registration call
+ * on a handle with enabled = 1 refuses likewise), lii_local_map_segment / _get before lii_local_map_set, a call from inside
+ * lii_scan_job::while_waiting.  Under LII_TEST=host_solve a registration call with enabled = 1 returns LII_ERR_STATE (the decision reads
+ * the device-resident control block the host-driven loop does not have); lii_local_map_segment works there.  A job on a handle with
+ * enabled = 1 neither uses nor arms the pre-armed prologue: next_scan_dev is ignored. */
+typedef struct lii_local_map_opts {
+  uint32_t struct_size; /* sizeof(lii_local_map_opts) */
+  int32_t enabled;      /* 1: the registration calls segment by themselves */
+  double cube_len;      /* cube_side_length */
+  float det_range;      /* mapping/det_range */
+  int32_t reserved;
+} lii_local_map_opts;
+typedef struct lii_local_map_info {
+  uint32_t struct_size; /* sizeof(lii_local_map_info); set by the call */
+  int32_t initialized;  /* Localmap_Initialized */
+  float cube[6];        /* LocalMap_Points: min xyz, max xyz */
+  int32_t last_n_boxes; /* cub_needrm of the last call that ran: 0 .. 3 boxes of 6 floats */
+  float last_boxes[18];
+  int32_t last_n_deleted; /* points those boxes removed */
+  int32_t moves;          /* calls that moved the cube since lii_local_map_set */
+  int64_t deleted_total;
+} lii_local_map_info;
+int lii_local_map_set(lii_handle h, const lii_local_map_opts* opts);
+int lii_local_map_get(lii_handle h, lii_local_map_info* out);
+int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_info* out /* may be NULL */);
 int lii_map_size(lii_handle h, int32_t* n_valid);
 int lii_map_download(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n);
 /* Kept for callers of ABI 1: the device map is always current (updates are applied in place); waits for the stream. */
@@ -726,6 +777,8 @@ int lii_params_load_launch(const char* launch_path, const char* config_dir /* ma
 int lii_params_set(lii_params* inout, const char* name, const char* value);
 int lii_params_apply(const lii_params* p, int32_t device, int32_t max_scan_points, int32_t max_map_points, lii_config* cfg /* may be NULL */,
                      lii_ingest_opts* ingest /* may be NULL */, lii_iekf_opts* opts /* may be NULL */, float* leaf /* may be NULL */);
+/* cube_side_length, mapping/det_range -> lii_local_map_opts with enabled = 1 (lii_local_map_set judges the values) */
+int lii_params_local_map(const lii_params* p, lii_local_map_opts* out);
 const char* lii_params_last_error(void);
 
 /* ---------------------------------------------------------------- utilities for harnesses */
@@ -744,7 +797,8 @@ int lii_last_timings(lii_handle h, double out_ms[8]);
  * Accumulators start at lii_set_profiling(h, 1), like the others. */
 enum lii_kernel_kind {
   LII_KP_DESKEW = 0,     /* adoption + de-skew (+ the voxel filter's insert, + the time-extent launch of an unsorted scan) */
-  LII_KP_VOXEL = 1,      /* the rest of the voxel filter */
+  LII_KP_VOXEL = 1,      /* the rest of the voxel filter - AND, on a handle with lii_local_map_set(enabled = 1), the three launches of the
+                            local map (this struct has no kind to spare in ABI 9): + 3 launches per scan and their time */
   LII_KP_KNN = 2,        /* k-NN pass */
   LII_KP_FIT_SEARCH = 3, /* plane fit + residual + reduction behind a k-NN pass */
   LII_KP_FIT = 4,        /* residual + reduction on cached planes */

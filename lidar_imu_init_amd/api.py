@@ -66,6 +66,16 @@ class lii_publish_opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("clouds", C.c_int32), ("to_host", C.c_int32), ("save_capacity", C.c_int32)]
 
 
+class lii_local_map_opts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_int32), ("cube_len", C.c_double), ("det_range", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class lii_local_map_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("initialized", C.c_int32), ("cube", C.c_float * 6), ("last_n_boxes", C.c_int32),
+                ("last_boxes", C.c_float * 18), ("last_n_deleted", C.c_int32), ("moves", C.c_int32), ("deleted_total", C.c_int64)]
+
+
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
@@ -164,6 +174,10 @@ _DECLS = {
     "lii_scan_register_cv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(lii_iekf_report)]),
     "lii_map_build_from_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "lii_local_map_set": (C.c_int, [C.c_void_p, C.POINTER(lii_local_map_opts)]),
+    "lii_local_map_get": (C.c_int, [C.c_void_p, C.POINTER(lii_local_map_info)]),
+    "lii_local_map_segment": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(lii_local_map_info)]),
+    "lii_params_local_map": (C.c_int, [C.c_void_p, C.POINTER(lii_local_map_opts)]),
     "lii_publish_set": (C.c_int, [C.c_void_p, C.POINTER(lii_publish_opts)]),
     "lii_publish_now": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lii_publish_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
@@ -404,6 +418,36 @@ class Registrar:
         n = C.c_int32(0)
         self._check(self.L.lii_map_delete_boxes(self.h, _ptr(b) if len(b) else None, len(b), C.byref(n)))
         return n.value
+
+    # ---- the moving local map (lasermap_fov_segment + the box delete upstream never made)
+    @staticmethod
+    def _local_map_info(info) -> dict:
+        nb = int(info.last_n_boxes)
+        return {"initialized": bool(info.initialized), "cube": np.array(info.cube, np.float32), "n_boxes": nb,
+                "boxes": np.array(info.last_boxes, np.float32).reshape(3, 6)[:nb].copy(), "n_deleted": int(info.last_n_deleted),
+                "moves": int(info.moves), "deleted_total": int(info.deleted_total)}
+
+    def local_map_set(self, cube_len, det_range, enabled=True):
+        """lii_local_map_set: the cube's edge and the detection range; enabled: every scan_register* call segments by itself.
+        Every call starts the cube over (Localmap_Initialized = false)."""
+        o = lii_local_map_opts(C.sizeof(lii_local_map_opts), int(bool(enabled)), float(cube_len), float(det_range), 0)
+        self._check(self.L.lii_local_map_set(self.h, C.byref(o)))
+
+    def local_map_get(self) -> dict:
+        """The cube and what the last call that ran did (waits for the stream)."""
+        info = lii_local_map_info()
+        self._check(self.L.lii_local_map_get(self.h, C.byref(info)))
+        return self._local_map_info(info)
+
+    def local_map_segment(self, pos_end, report=True):
+        """One lasermap_fov_segment at pos_end (state.pos_end) + the delete of its boxes; report=False only enqueues."""
+        p = (C.c_double * 3)(*[float(x) for x in np.asarray(pos_end, np.float64).reshape(3)])
+        if not report:
+            self._check(self.L.lii_local_map_segment(self.h, p, None))
+            return None
+        info = lii_local_map_info()
+        self._check(self.L.lii_local_map_segment(self.h, p, C.byref(info)))
+        return self._local_map_info(info)
 
     def map_size(self) -> int:
         n = C.c_int32(0)

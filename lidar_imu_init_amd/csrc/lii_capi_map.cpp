@@ -190,6 +190,7 @@ int commit_map(lii_handle h) {
     h->n_map = h->h_mapflag[kMapCtrValid];
     h->n_blocks = int(std::min<size_t>(size_t(std::max(h->h_mapflag[kMapCtrBlocks], 0)), h->cells_cap_blocks));
     h->map_dirty = false;
+    h->lm.counts_pending = false;  // (the update ran behind every local-map call enqueued so far: its counters hold their deletes)
   }
   return LII_OK;
 }
@@ -204,7 +205,8 @@ int map_counters(lii_handle h, bool already_synced) {
     if (rc != LII_OK) return rc;
   }
   h->map_flag_pending = false;
-  if (!h->map_dirty) return LII_OK;
+  if (!h->map_dirty && !h->lm.counts_pending) return LII_OK;  // (counts_pending: a local-map call deleted on the device since the last read)
+  h->lm.counts_pending = false;
   if (!already_synced) {
     HIPCHK(h, hipMemcpyAsync(h->h_small + 3072, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -387,6 +389,7 @@ int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, con
 int map_update_early(lii_handle h) {
   const int nb = h->n_body;
   if (nb <= 0 || nb > h->cfg.max_map_points || h->net.n_ranks > 1 || h->pred_add < 0 || h->map_dirty || h->map_async || h->lists_predicted) return 0;
+  if (h->lm.counts_pending) return 0;  // (a local-map call nobody has settled: the counters are read when the update has ended, not in the middle of it)
   if ((long long)h->n_map + std::min(nb, h->pred_add) + std::min(nb, h->pred_nodown) > (long long)h->cfg.max_map_points) return 0;
   RegistrationBuffers rb = reg_buffers(h);
   int ba = std::min(nb, h->pred_add), bn = std::min(nb, h->pred_nodown);
@@ -408,6 +411,65 @@ int map_update_early(lii_handle h) {
   return rc == LII_OK ? 1 : rc;
 }
 
+
+// ------------------------------------------------------------------------------------------------ the moving local-map cube
+int local_map_enqueue(lii_handle h, const double* pos_dev, const double* pos, bool mark) {
+  lii_context::LocalMap& L = h->lm;
+  hipStream_t s = h->stream;
+  if (h->map_dirty) {  // (cannot happen behind commit_map / map_counters; the launches below take the number of blocks from the host)
+    const int rc = map_counters(h);
+    if (rc != LII_OK) return rc;
+  }
+  // the work list holds every cell entry of the map if it must: made here, on the host, in front of the launches (a rebuild may have
+  // changed the number of blocks since the setting was made; nothing is in flight that uses the list)
+  const size_t ne = size_t(std::max(h->n_blocks, 0)) * 512;
+  if (ne > size_t(h->work_cap)) {
+    h->work_cap = 0;
+    HIPCHK(h, h->d_work.grow(ne + ne / 2 + 4096));
+    h->work_cap = (unsigned int)h->d_work.size();
+  }
+  L.seq = L.seq == 0x7FFFFFFF ? 1 : L.seq + 1;
+  if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
+  launch_local_map_tomb(L.d_state + L.cur, L.d_state + (L.cur ^ 1), L.P, pos_dev, pos, h->d_pts, h->d_cells, h->d_block_key, std::max(h->n_blocks, 0), h->cell_size,
+                        h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
+  const lii::WinKeep wk = win_keep_view(h);
+  if (!wk.win && h->win_valid) { h->win_valid = false; h->win_dropped++; }  // (cell entries may change: a window that is not kept current goes)
+  if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
+  launch_cell_apply_listed(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, h->work_cap, wk, s);
+  if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
+  launch_local_map_finish(L.d_state + (L.cur ^ 1), h->d_mapctr, L.h_state, L.seq, s);
+  HIPCHK(h, hipGetLastError());
+  L.cur ^= 1;
+  return LII_OK;
+}
+void local_map_settle(lii_handle h) {
+  lii_context::LocalMap& L = h->lm;
+  if (L.h_state->seq != L.seq) { L.counts_pending = true; return; }  // (the report is not the last call's: the count waits for a read of the device's counters)
+  if (h->map_dirty) return;  // (a map update was enqueued behind the call: its counters bring the count, commit_map)
+  h->n_map = L.h_state->n_valid;
+  L.counts_pending = false;
+}
+namespace {
+const char* local_map_refusal(double cube_len, float det_range) {
+  if (!std::isfinite(cube_len) || !std::isfinite(det_range)) return "cube_len and det_range must be finite";
+  if (!(det_range > 0.f)) return "det_range must be positive";
+  // a sensor at the centre of a fresh cube is cube_len / 2 from both faces of an axis: with cube_len <= 3 det_range both are inside the
+  // threshold 1.5 det_range at once, every scan moves the cube and the boxes close in on the sensor
+  if (!(cube_len > 3.0 * double(det_range))) return "cube_len must exceed 3 * det_range (MOV_THRESHOLD = 1.5 on both faces of an axis)";
+  return nullptr;
+}
+void local_map_info_out(const lii::LocalMapState& st, lii_local_map_info* out) {
+  static_assert(sizeof(lii_local_map_opts) == 24 && sizeof(lii_local_map_info) == 128, "lii_local_map_opts / lii_local_map_info layout");
+  out->struct_size = sizeof(lii_local_map_info);
+  out->initialized = st.initialized;
+  std::memcpy(out->cube, st.cube, sizeof(out->cube));
+  out->last_n_boxes = st.n_boxes;
+  std::memcpy(out->last_boxes, st.boxes, sizeof(out->last_boxes));
+  out->last_n_deleted = st.n_deleted;
+  out->moves = st.moves;
+  out->deleted_total = st.deleted_total;
+}
+}  // namespace
 }  // namespace lii_impl
 
 extern "C" {
@@ -531,6 +593,70 @@ int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int3
   if (rc != LII_OK) return rc;
   if (n_deleted) *n_deleted = n_old - h->n_map;
   if (h->n_map != n_old) h->have_search = false;
+  return LII_OK;
+}
+int lii_local_map_set(lii_handle h, const lii_local_map_opts* opts) {
+  if (!h) return LII_ERR_INVALID;
+  if (!opts || opts->struct_size != sizeof(lii_local_map_opts) || (opts->enabled != 0 && opts->enabled != 1))
+    return fail(h, LII_ERR_INVALID, "lii_local_map_set: bad lii_local_map_opts (struct_size, enabled 0 / 1)");
+  if (const char* why = local_map_refusal(opts->cube_len, opts->det_range)) return fail(h, LII_ERR_INVALID, std::string("lii_local_map_set: ") + why);
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_local_map_set: single rank only for now (a communicator is attached)");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_local_map_set: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  lii_context::LocalMap& L = h->lm;
+  if (!L.d_state) {
+    HIPCHK(h, L.d_state.alloc(2));
+    HIPCHK(h, L.h_state.alloc(1, hipHostMallocMapped));
+  }
+  // Localmap_Initialized = false: both copies and the report start from nothing, behind whatever call is still on the stream
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemset(L.d_state, 0, 2 * sizeof(lii::LocalMapState)));
+  std::memset(L.h_state.get(), 0, sizeof(lii::LocalMapState));
+  L.cur = 0;
+  L.seq = 0;
+  // the two constants of the configuration, formed here (this unit is compiled without contraction: the products and the difference round
+  // one by one, as the reference's do)
+  const float det = opts->det_range;
+  L.det_range = det;
+  L.P.cube_len = opts->cube_len;
+  L.P.thr = 1.5f * det;
+  const double a = (opts->cube_len - 2.0 * 1.5f * det) * 0.5 * 0.9, b = double(det * (1.5f - 1));
+  L.P.mov_dist = float(std::max(a, b));
+  L.enabled = opts->enabled == 1;
+  L.set = true;
+  return LII_OK;
+}
+int lii_local_map_get(lii_handle h, lii_local_map_info* out) {
+  if (!h) return LII_ERR_INVALID;
+  if (!out) return fail(h, LII_ERR_INVALID, "lii_local_map_get: bad arguments");
+  if (!h->lm.set) return fail(h, LII_ERR_STATE, "lii_local_map_get: no local map (lii_local_map_set)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  local_map_settle(h);
+  local_map_info_out(*h->lm.h_state, out);
+  return LII_OK;
+}
+int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_info* out) {
+  if (!h) return LII_ERR_INVALID;
+  if (!pos_end || !std::isfinite(pos_end[0]) || !std::isfinite(pos_end[1]) || !std::isfinite(pos_end[2]))
+    return fail(h, LII_ERR_INVALID, "lii_local_map_segment: pos_end must be three finite numbers");
+  if (!h->lm.set) return fail(h, LII_ERR_STATE, "lii_local_map_segment: no local map (lii_local_map_set)");
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_local_map_segment: single rank only for now (a communicator is attached)");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_local_map_segment: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  int rc = map_counters(h);  // (joins a map update in flight; the host's counters are current from here)
+  if (rc != LII_OK) return rc;
+  rc = local_map_enqueue(h, nullptr, pos_end, false);
+  if (rc != LII_OK) return rc;
+  h->lm.counts_pending = true;  // (until somebody has seen the call's report, or read the device's counters)
+  if (!out) {
+    h->have_search = false;  // (whether the cube moved is not known here: lists and planes of an earlier search are not used again)
+    return LII_OK;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  local_map_settle(h);
+  if (h->lm.h_state->n_deleted != 0) h->have_search = false;
+  local_map_info_out(*h->lm.h_state, out);
   return LII_OK;
 }
 int lii_map_size(lii_handle h, int32_t* n_valid) {

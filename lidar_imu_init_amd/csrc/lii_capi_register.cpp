@@ -122,6 +122,13 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   h->ctrl_preloaded = false;
   h->h_res->singular = 0;
   h->h_res->it = -1;  // overwritten by the stopping iteration
+  // lii_local_map_set(enabled): lasermap_fov_segment + the box delete at the reference's place - behind the propagation (state.pos_end of
+  // the control block, which every prologue has put on the stream by now) and the map update that commit_map joined, in front of the
+  // first search.  Three launches of fixed size.
+  if (h->lm.in_job) {
+    rc = local_map_enqueue(h, h->d_ctrl->st + 9, nullptr, h->prof.kp_active);
+    if (rc != LII_OK) return rc;
+  }
   GridView g = grid_view(h);
   RegistrationBuffers rb = reg_buffers(h);
   const PoseArg* pose = reinterpret_cast<const PoseArg*>(h->d_ctrl);  // first 24 doubles of IekfCtrl::st
@@ -521,6 +528,11 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   const bool sort_first = job->struct_size >= 56u && job->scan_sorted == 2;
   if (sort_first && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": scan_sorted = 2 is single rank only for now (a communicator is attached)");
   const bool sorted = job->struct_size >= 56u && (job->scan_sorted == 1 || sort_first);
+  // lii_local_map_set(enabled): this call segments by itself (update_on_device).  Single rank, and not under LII_TEST=host_solve: the
+  // decision reads the device-resident control block, which the host-driven loop does not have.
+  const bool local_map = h->lm.enabled;
+  if (local_map && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is single rank only for now (a communicator is attached)");
+  if (local_map && h->host_solve) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is not available under LII_TEST=host_solve; call lii_local_map_segment");
   h->scan_buf_idle = false;
   int rc = LII_OK;
   const auto t_entry = std::chrono::steady_clock::now();
@@ -543,14 +555,14 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   bool use_pre = h->pre.armed && sorted && job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= lii::kGateMaxPoses &&
                  cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && leaf_now == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
                  h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, leaf_now) == h->pre.fuse;
-  if (feed || cv || sort_first) use_pre = false;  // (lii_scan_register_imu / _cv, a job that sorts: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
+  if (feed || cv || sort_first || local_map) use_pre = false;  // (lii_scan_register_imu / _cv, a job that sorts, a handle with the local map enabled: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
   if (!use_pre) prearm_cancel(h);
   // ... and what this job announces for the next call (update_on_device arms it behind the passes)
   h->pre.want_dev = nullptr;
-  if (!feed && !cv && !sort_first && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
+  if (!feed && !cv && !sort_first && !local_map && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
       sorted && job->undistort == 1) {
     h->pre.want_dev = job->next_scan_dev; h->pre.want_n = job->next_n_scan; h->pre.want_leaf = leaf_now; h->pre.want_late = false;
-  } else if (!feed && !cv && !sort_first && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
+  } else if (!feed && !cv && !sort_first && !local_map && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
     // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
     h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = leaf_now; h->pre.want_late = true;
   }
@@ -711,7 +723,15 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   // arrangement without that wait (LII_TEST=host_solve) calls it behind the update - once per call that got this far, never otherwise
   h->wait_hook = (rc == LII_OK && job->struct_size >= 88u) ? job->while_waiting : nullptr;
   h->wait_hook_arg = job->struct_size >= 88u ? job->while_waiting_arg : nullptr;
+  h->lm.in_job = local_map && rc == LII_OK;
   if (rc == LII_OK) rc = lii_iekf_update(h, state, state_prop ? state_prop : state, &job->opts, report);
+  if (h->lm.in_job) {
+    // (the update's result came back behind the local-map call: its report is in pinned memory, and the host's live-point count takes
+    // it - a call that failed on the way leaves the count to the next read of the device's counters)
+    if (rc == LII_OK) local_map_settle(h);
+    else h->lm.counts_pending = true;
+    h->lm.in_job = false;
+  }
   if (h->wait_hook) {
     void (*hook)(void*) = h->wait_hook;
     h->wait_hook = nullptr;

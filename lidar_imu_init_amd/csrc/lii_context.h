@@ -320,6 +320,20 @@ struct lii_context {
     int clouds_at[2] = {0, 0};              // the clouds the slot holds
     int kp_idx = -1;                        // lii_set_profiling(h, 3): the mark of the launch enqueued behind the planned passes
   } pub;
+  // ---- the moving local-map cube (lii_local_map_*, lii_capi_map.cpp; kernels: lii_map.hip, arithmetic: lii_fov.h): durable handle state,
+  // off until lii_local_map_set asks for it.  Nothing here exists before the first lii_local_map_set.
+  struct LocalMap {
+    bool set = false;        // lii_local_map_set has been accepted once (lii_local_map_segment works from then on)
+    bool enabled = false;    // every registration call segments by itself
+    float det_range = 0.f;
+    lii::LocalMapParams P{};
+    DevBuf<lii::LocalMapState> d_state;    // two copies: call k reads [cur], writes [cur ^ 1]
+    PinnedBuf<lii::LocalMapState> h_state; // the copy the last call's last launch leaves for the host
+    int cur = 0;
+    int seq = 0;                 // number of the last enqueued call
+    bool in_job = false;         // scan_register_job -> update_on_device: this update segments behind commit_map, in front of its first search
+    bool counts_pending = false; // a call has been enqueued whose deletes the host's copy of the live-point count does not hold yet
+  } lm;
   void* ingest = nullptr;  // lii_ingest.hip state (frames of the last driver message)
   bool ingest_sort_always = false;  // LII_INGEST_SORT=always: the ingest never leaves the time sort out (IngestRing::never_predict)
 
@@ -402,6 +416,10 @@ int map_update_early(lii_handle h);  // 1: enqueued behind the passes of the upd
 int commit_map(lii_handle h);
 int map_counters(lii_handle h, bool already_synced = false);
 lii::WinKeep win_keep_view(lii_handle h);  // the window as the update's launches keep it current (win == nullptr: nothing to keep)
+// one lasermap_fov_segment + Delete_Point_Boxes on the handle's stream (three launches); pos_dev: state.pos_end in device memory, else pos by
+// value.  The caller has joined the map update in flight.  mark: lii_set_profiling(h, 3) brackets the launches (LII_KP_VOXEL)
+int local_map_enqueue(lii_handle h, const double* pos_dev, const double* pos, bool mark);
+void local_map_settle(lii_handle h);  // the stream has passed the last enqueued call: the host's live-point count takes its result
 int map_gather(lii_handle h, int* n_out);
 int map_rebuild(lii_handle h, int extra_blocks);
 int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, const float4* extra, int n_extra, bool beside = false,

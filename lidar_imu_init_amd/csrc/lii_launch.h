@@ -6,6 +6,7 @@
 #include <string>
 
 #include "lii_device.h"
+#include "lii_fov.h"
 
 struct lii_context;
 // internal hooks of the handle for the translation units that live beside lii_capi.cpp (not exported in the C-ABI header)
@@ -279,6 +280,16 @@ void launch_cell_counts(const uint2* cells, int n_entries, unsigned int* cnt, hi
 void launch_gather_live(const float4* pts, const uint2* cells, const unsigned int* cntsum, int n_entries, float4* dst, int dst_cap, hipStream_t s);
 void launch_box_tomb_cells(const float4* pts, const uint2* cells, int n_entries, const float* boxes, int n_boxes, unsigned char* tomb, unsigned int* tp,
                            unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s);
+// the moving local-map cube (lii_map.hip: k_local_map_tomb -> k_cell_apply_listed -> k_local_map_finish; the arithmetic: lii_fov.h).  `in` / `out`:
+// the two copies of the state in device memory; pos_dev != nullptr: state.pos_end is read there, else `pos` travels by value; `host`: the
+// pinned copy of the state the last launch leaves.  All three launches have a fixed size.
+constexpr int kLocalMapGrid = 512;
+void launch_local_map_tomb(const LocalMapState* in, LocalMapState* out, const LocalMapParams& P, const double* pos_dev, const double* pos, const float4* pts,
+                           const uint2* cells, const unsigned long long* key_of_id, int n_blocks, float cs, unsigned char* tomb, unsigned int* tp,
+                           unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s);
+void launch_cell_apply_listed(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
+                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s);
+void launch_local_map_finish(LocalMapState* st, int* ctr, LocalMapState* host, int seq, hipStream_t s);
 
 // the registered clouds of a scan (lii_publish.hip: k_publish_world)
 struct PublishArgs {

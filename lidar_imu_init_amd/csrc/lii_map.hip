@@ -21,6 +21,7 @@
 #include <cstring>
 #include <math.h>
 
+#include "lii_fov.h"
 #include "lii_grid.h"
 #include "lii_launch.h"
 
@@ -663,16 +664,10 @@ __global__ void k_ins_cells(const float4* __restrict__ list, const unsigned int*
   ins_cell_one(list[i], &ins_e[i], a);
 }
 
-__global__ void k_cell_apply(const unsigned int* __restrict__ work, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap,
-                             float4* __restrict__ pts, unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr,
-                             unsigned int pts_cap, int launch_bound, WinKeep wk) {
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n_work = ctr[kMapCtrWork];
-  const bool valid = w < n_work && w < launch_bound;
-  if (!__any(valid)) return;  // (uniform per wavefront)
-  int gone = 0;
-  if (valid) {
-  const unsigned int e = work[w];
+// one listed cell: its tombstones squeezed out, the cell moved to the tail when survivors + pending inserts outgrow it; returns the points gone
+__device__ __forceinline__ int cell_apply_one(const unsigned int e, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap, float4* __restrict__ pts,
+                                              unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr, unsigned int pts_cap,
+                                              const WinKeep& wk) {
   const uint2 c = cells[e];
   const unsigned int tpv = tp[e], capv = cell_cap[e];  // (loaded beside the cell entry, not behind the squeeze)
   unsigned int first = c.x, end = c.y, wpos = c.x;
@@ -727,8 +722,17 @@ __global__ void k_cell_apply(const unsigned int* __restrict__ work, uint2* __res
     if (wi >= 0) wk.win[wi] = make_uint2(first, first + alive);
     else __hip_atomic_store(&ctr[kMapCtrWinStale], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  gone = (int)deleted;
-  }
+  return (int)deleted;
+}
+__global__ void k_cell_apply(const unsigned int* __restrict__ work, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap,
+                             float4* __restrict__ pts, unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr,
+                             unsigned int pts_cap, int launch_bound, WinKeep wk) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n_work = ctr[kMapCtrWork];
+  const bool valid = w < n_work && w < launch_bound;
+  if (!__any(valid)) return;  // (uniform per wavefront)
+  int gone = 0;
+  if (valid) gone = cell_apply_one(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
   wave_atomic_add_all(&ctr[kMapCtrValid], -gone);
 }
 
@@ -851,6 +855,133 @@ __global__ void k_box_tomb_cells(const float4* __restrict__ pts, const uint2* __
   if (any) touch_cell(tp, work, ctr, work_cap, (unsigned int)e);
 }
 
+
+// ------------------------------------------------------------------------------------------------ the moving local-map cube
+// lasermap_fov_segment + Delete_Point_Boxes(cub_needrm), src/laserMapping.cpp:260-305 (the delete is the call upstream prepared and never
+// made), in three launches of FIXED size - a scan that does not move the cube, which is nearly every scan, costs the same whatever the
+// map holds:
+//   k_local_map_tomb    every wavefront forms the decision (fov_segment_dev, lii_fov.h: a few dozen flops on the cube the launch finds and
+//                       the position - the update's control block, or by value); lane 0 of the launch leaves it in the OTHER copy of the
+//                       state.  No box: the launch ends there.  Else one wavefront per 8 x 8 x 8 block, striding over the block ids: the
+//                       block's extent against the boxes - disjoint from all: skipped untouched; inside one: every live point goes
+//                       without a compare; else the 64 lanes take 8 cells each and compare.  Tombstones and the work list as
+//                       k_box_tomb_cells leaves them.
+//   k_cell_apply_listed k_cell_apply's squeeze over the listed cells, striding: its size does not follow the map either
+//   k_local_map_finish  one wavefront: the work list is re-armed, the counts of the call go into the state and the state into pinned memory
+// The extent of a block is taken a little wide (the cell of a point is floorf(p * inv_cs): not exactly a multiple of the cell size): a
+// block is "inside" only when that closed extent satisfies min <= x < max, and "disjoint" only when no point of it can; in doubt it
+// is compared point by point, which is the rule itself.
+struct LocalMapCall {
+  const LocalMapState* in;
+  LocalMapState* out;
+  LocalMapParams P;
+  const double* pos_dev;  // != nullptr: state.pos_end is read here (IekfCtrl::st + 9); else pos
+  double pos[3];
+};
+__global__ __launch_bounds__(256) void k_local_map_tomb(LocalMapCall a, const float4* __restrict__ pts, const uint2* __restrict__ cells,
+                                                        const unsigned long long* __restrict__ key_of_id, int n_blocks, float cs,
+                                                        unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, unsigned int* __restrict__ work,
+                                                        int* __restrict__ ctr, unsigned int work_cap) {
+  LocalMapState st;
+  {
+    const LocalMapState in = *a.in;
+    double pos[3] = {a.pos[0], a.pos[1], a.pos[2]};
+    if (a.pos_dev) { pos[0] = a.pos_dev[0]; pos[1] = a.pos_dev[1]; pos[2] = a.pos_dev[2]; }  // (uniform)
+    // (a scan that moves nothing - nearly every scan - ends here for all but the one lane that keeps the state: six distances, no more)
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    float d0[3], d1[3];
+    const bool moves = in.initialized && fov_need_move(in.cube, pos, a.P.thr, d0, d1);  // (uniform over the launch)
+    if (!moves && !first) return;
+    fov_segment_dev(in, pos, a.P, st);
+    if (first) {
+      st.n_deleted = 0;
+      st.n_valid = ctr[kMapCtrValid];  // (as the call finds it: k_local_map_finish turns it into the count of the call)
+      st.seq = in.seq;
+      st.deleted_total = in.deleted_total;
+      *a.out = st;
+    }
+  }
+  const int nb = st.n_boxes;
+  if (nb == 0) return;
+  // the (at most three) boxes in registers, indexed by constants from here on; a box that is not there is an empty one (min = +inf,
+  // max = -inf: disjoint from every block, no point inside)
+  float bx[3][6];
+#pragma unroll
+  for (int b = 0; b < 3; b++)
+#pragma unroll
+    for (int k = 0; k < 6; k++) bx[b][k] = b < nb ? st.boxes[6 * b + k] : (k < 3 ? __builtin_inff() : -__builtin_inff());
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), n_waves = (int)((gridDim.x * blockDim.x) >> 6);
+  const int bb = kCellBias >> kCoarseShift;
+  for (int bid = wave; bid < n_blocks; bid += n_waves) {
+    unsigned int kx, ky, kz;
+    unpack_block(key_of_id[bid], kx, ky, kz);
+    const int c0[3] = {((int)kx - bb) * 8, ((int)ky - bb) * 8, ((int)kz - bb) * 8};
+    float lo[3], hi[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const float l = (float)c0[i] * cs, h = (float)(c0[i] + 8) * cs;
+      const float m = 1e-5f * (fabsf(l) + fabsf(h)) + 1e-3f * cs;
+      lo[i] = l - m; hi[i] = h + m;
+    }
+    bool inside = false, touches = false;
+#pragma unroll
+    for (int b = 0; b < 3; b++) {
+      const float* q = bx[b];
+      bool in_b = true, dis_b = false;
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        in_b = in_b && q[i] <= lo[i] && hi[i] < q[3 + i];
+        dis_b = dis_b || hi[i] < q[i] || lo[i] >= q[3 + i];
+      }
+      inside = inside || in_b;
+      touches = touches || !dis_b;
+    }
+    if (!touches) continue;  // (uniform per wavefront) nothing of this block is read
+    for (int u = 0; u < 8; u++) {
+      const unsigned int e = (unsigned int)bid * kBlockCells + (unsigned int)(lane * 8 + u);
+      const uint2 c = cells[e];
+      bool any = false;
+      for (unsigned int j = c.x; j < c.y; j++) {
+        bool dead = inside;
+        if (!inside) {
+          const float4 p = pts[j];
+#pragma unroll
+          for (int b = 0; b < 3; b++) {
+            const float* q = bx[b];
+            dead = dead || (q[0] <= p.x && q[3] > p.x && q[1] <= p.y && q[4] > p.y && q[2] <= p.z && q[5] > p.z);
+          }
+        }
+        if (dead) { tomb[j] = 1; any = true; }
+      }
+      if (any) touch_cell(tp, work, ctr, work_cap, e);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_cell_apply_listed(const unsigned int* __restrict__ work, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap,
+                                                           float4* __restrict__ pts, unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp,
+                                                           int* __restrict__ ctr, unsigned int pts_cap, unsigned int work_cap, WinKeep wk) {
+  const int n_work = min(ctr[kMapCtrWork], (int)work_cap);
+  if (n_work <= 0) return;  // (uniform)
+  const int total = (int)(gridDim.x * blockDim.x);
+  int gone = 0;
+  for (int w = (int)(blockIdx.x * blockDim.x + threadIdx.x); w < n_work; w += total)
+    gone += cell_apply_one(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
+  wave_atomic_add_all(&ctr[kMapCtrValid], -gone);  // (every lane of the wavefront arrives here)
+}
+__global__ __launch_bounds__(64) void k_local_map_finish(LocalMapState* __restrict__ st, int* __restrict__ ctr, LocalMapState* __restrict__ host, int seq) {
+  if (threadIdx.x != 0) return;
+  ctr[kMapCtrWork] = 0;  // the work list has been consumed
+  LocalMapState s = *st;
+  const int valid = ctr[kMapCtrValid];
+  s.n_deleted = s.n_valid - valid;
+  s.n_valid = valid;
+  s.deleted_total += (long long)s.n_deleted;
+  s.seq = seq;
+  *st = s;
+  *host = s;
+}
+
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 void launch_ins_cells(const float4* list, const unsigned int* flags, int n, const int* n_dev, const float4* list2, int n2, const int* n2_dev, unsigned int* ins_e2,
                       BlockEntry* blocks, unsigned int mask, float inv_cs, unsigned int tables_cap, unsigned int* ins_e, unsigned int* tp,
@@ -891,6 +1022,23 @@ void launch_gather_live(const float4* pts, const uint2* cells, const unsigned in
 void launch_box_tomb_cells(const float4* pts, const uint2* cells, int n_entries, const float* boxes, int n_boxes, unsigned char* tomb, unsigned int* tp,
                            unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s) {
   if (n_entries > 0) hipLaunchKernelGGL(k_box_tomb_cells, dim3(nblk(n_entries, 256)), dim3(256), 0, s, pts, cells, n_entries, boxes, n_boxes, tomb, tp, work, ctr, work_cap);
+}
+
+// 512 workgroups of four wavefronts - two per compute unit of an MI355X - for the two launches that stride (kLocalMapGrid)
+void launch_local_map_tomb(const LocalMapState* in, LocalMapState* out, const LocalMapParams& P, const double* pos_dev, const double* pos, const float4* pts,
+                           const uint2* cells, const unsigned long long* key_of_id, int n_blocks, float cs, unsigned char* tomb, unsigned int* tp,
+                           unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s) {
+  LocalMapCall a;
+  a.in = in; a.out = out; a.P = P; a.pos_dev = pos_dev;
+  for (int i = 0; i < 3; i++) a.pos[i] = pos ? pos[i] : 0.0;
+  hipLaunchKernelGGL(k_local_map_tomb, dim3(kLocalMapGrid), dim3(256), 0, s, a, pts, cells, key_of_id, n_blocks, cs, tomb, tp, work, ctr, work_cap);
+}
+void launch_cell_apply_listed(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
+                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s) {
+  hipLaunchKernelGGL(k_cell_apply_listed, dim3(kLocalMapGrid), dim3(256), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, work_cap, wk);
+}
+void launch_local_map_finish(LocalMapState* st, int* ctr, LocalMapState* host, int seq, hipStream_t s) {
+  hipLaunchKernelGGL(k_local_map_finish, dim3(1), dim3(64), 0, s, st, ctr, host, seq);
 }
 
 // The last launch of an in-place update: the map's counters (and the list sizes behind them) go to the caller's pinned, mapped buffer

@@ -348,4 +348,15 @@ int lii_params_apply(const lii_params* p, int32_t device, int32_t max_scan_point
   return LII_OK;
 }
 
+// cube_len = cube_side_length (a double), DET_RANGE = mapping/det_range (nh.param<float>: a float), laserMapping.cpp:776-777
+int lii_params_local_map(const lii_params* p, lii_local_map_opts* out) {
+  if (!p || p->struct_size != sizeof(lii_params) || !out) return pfail(LII_ERR_INVALID, "lii_params_local_map: bad arguments");
+  std::memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(lii_local_map_opts);
+  out->enabled = 1;
+  out->cube_len = p->cube_side_length;
+  out->det_range = (float)p->det_range;
+  return LII_OK;
+}
+
 }  // extern "C"

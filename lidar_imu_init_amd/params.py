@@ -75,3 +75,9 @@ class Params:
         _check(_lib().lii_params_apply(C.byref(self.pod), device, max_scan_points, max_map_points, C.byref(cfg), C.byref(ing),
                                        C.byref(opts), C.byref(leaf)))
         return cfg, ing, opts, leaf.value
+
+    def local_map(self):
+        """-> api.lii_local_map_opts from cube_side_length / mapping/det_range, enabled = 1 (lii_params_local_map)."""
+        o = api.lii_local_map_opts()
+        _check(_lib().lii_params_local_map(C.byref(self.pod), C.byref(o)))
+        return o
