@@ -42,7 +42,7 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {  // lane is
 // its column and only otherwise the largest entry is searched and the rows exchanged (partial pivoting's choice).  Stable like
 // partial pivoting (element growth per step bounded by 1 + 1/tau = 5 instead of 2).
 // Round 5: this routine - twelve unrolled steps with the exchange code behind every one of them, ~30 KB of straight-line code that
-// a launch executes once, every line of it an instruction-cache miss - is now the FALLBACK of gj12_loop below.
+// a launch executes once, every line of it an instruction-cache miss - is now the FALLBACK of gj12_dpp below.
 __device__ __forceinline__ bool gj12_pivoting(double (&col)[H]) {
 #pragma unroll
   for (int k = 0; k < H; k++) {
@@ -92,17 +92,13 @@ __device__ __forceinline__ bool gj12_pivoting(double (&col)[H]) {
   return true;
 }
 
-// The same elimination as a LOOP of twelve identical steps (round 5).  What made the unrolled form necessary were the register
-// indices: step k reads row k as the pivot row.  Here the rows ROTATE instead: position 0 always holds the pivot row, the update of
-// row p lands in position p - 1 (the fused multiply-add writes its result one register pair down: the rotation costs no move) and
-// the finished pivot row enters at position 11 - after twelve steps every row is back where it started.  Only the lane that
-// holds the pivot column changes from step to step, and v_readlane takes the lane from a scalar register.  The body is ~60
-// instructions (~0.5 KB): fetched once, it runs out of the instruction cache, where the unrolled form paid a memory round trip for
-// every eight instructions (phase stamps: 3.0 us for ~700 instructions - ten cycles per instruction on a wavefront that can
-// issue one every four or five).
-// Pivoting: none inside the loop - a data-dependent row exchange is what cannot be expressed with static register indices - but
+// The elimination the launches run: gj12_dpp, twelve steps WITHOUT row exchanges.  Position 0 always holds the pivot row, the update
+// of row p lands in position p - 1 and the finished pivot row enters at position 11 - after twelve steps every row is back where it
+// started (round 5 ran these steps as a loop of ~0.5 KB, gj12_loop, with the pivot column by v_readlane from a lane held in a scalar register;
+// unrolled, the rotation is register naming).
+// Pivoting: none inside the steps - a data-dependent row exchange is what cannot be expressed with static register indices - but
 // the elimination WATCHES ITS OWN GROWTH: every lane keeps the largest magnitude its column takes on the way (twelve maxima per
-// step, off the critical chain readlane -> reciprocal -> multiply-add), and the result stands only if the columns of A never
+// step, off the critical chain broadcast -> reciprocal -> multiply-add), and the result stands only if the columns of A never
 // outgrew 2^8 x max(1, max |A|) - the quantity the backward error of an elimination is proportional to (Wilkinson) - and
 // every pivot was a number.  Otherwise the saved input goes through gj12_pivoting.  I + P11 G with P11, G positive semi-definite
 // has its spectrum in [1, inf): measured on LIO sequences (hall, corridor: tools/gj_growth.py) the pivot-free growth stays
@@ -114,7 +110,7 @@ __device__ __forceinline__ bool gj12_pivoting(double (&col)[H]) {
 // occupies the pipe for 7 - 10 cycles, a 32-bit operation for 4), and "x 2^8" is an addition to the double's exponent field.  A word
 // whose upper exponent bits are all ones - a double beyond 2^1016, infinity, not-a-number - reads as a single-precision NaN, which the
 // maximum SKIPS: such a value cannot pass the elimination unnoticed all the same, a pivot that was zero or not a number turns its
-// whole row - every lane's last entry - into not-a-number for good, and gj12_loop looks at that entry once at the end.
+// whole row - every lane's last entry - into not-a-number for good, and gj12_dpp looks at that entry once at the end.
 __device__ __forceinline__ float max3_abs(float a, float b, float c) {
   float r;
   asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -137,24 +133,47 @@ __device__ __forceinline__ float col_absmax_hi(const double (&col)[H], float g) 
 // factor of the whole matrix (a column's scale is at most the matrix's) and needs no reduction over the lanes - the verdict is one
 // ballot at the end.  (The columns of the right-hand side are watched as well: they only ride along, but a column that outgrows
 // its start by 2^8 says the multipliers were large.)
-__device__ __forceinline__ bool gj12_loop(double (&col)[H]) {
+//
+// The pivot column travels by DPP ROW BROADCAST.  The loop form paid 24 v_readlane for a step's twelve multipliers - a scalar-register
+// round trip each, most of the step (tools/ubench/solve_ubench.hip, profiles/solve_dpp.md).
+// A DPP move with row_newbcast:k copies lane k of every 16-lane row to the whole row in one vector instruction.  Its
+// conditions shape the layout: k is an immediate - the twelve steps are unrolled, and the row rotation of the loop form becomes
+// register naming - and a lane reads from its own row - EVERY row holds the twelve columns of A in its lanes 0 - 11 (replicated:
+// the same instructions on the same numbers give the same bits in every row) and four right-hand columns in lanes 12 - 15.  24
+// right-hand columns are six rows: two wavefronts.  A DPP read from a lane whose EXEC bit is off does not deliver that lane's value:
+// all 64 lanes of a wavefront stay active from the first step to the last.
+// Per column the arithmetic is the loop form's to the letter - the same reciprocal, the same multiply-adds in the same order, the same
+// growth watch - so every column comes out with the same bits (tests/test_gpu_solve_bits.py).
+// One v_mov_b64_dpp per double (row_newbcast is the one control the 64-bit form takes) with bound_ctrl:1: every lane is written, so
+// the destination needs no preset.  Priced in tools/ubench/solve_ubench.hip: two 32-bit moves into a register preset to 0 - what
+// bound_ctrl off costs, a v_mov_b32 0 in front of every move - make a step of 329 clk, with bound_ctrl:1 229, this form 173
+// (v_readlane, the loop: 366).
+template <int K>
+__device__ __forceinline__ double rowbcast_f64(double v) {
+  return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + K, 0xF, 0xF, true);  // row_newbcast:K
+}
+template <int K>
+__device__ __forceinline__ void gj12_dpp_step(double (&col)[H], float& g) {
+  double m[H];
+#pragma unroll
+  for (int r = 0; r < H; r++) m[r] = rowbcast_f64<K>(col[r]);  // the pivot column (lane K of this row), pivot row first
+  double inv = __builtin_amdgcn_rcp(m[0]);
+  inv = fma(fma(-m[0], inv, 1.0), inv, inv);
+  inv = fma(fma(-m[0], inv, 1.0), inv, inv);
+  const double rowk = col[0] * inv;
+#pragma unroll
+  for (int r = 1; r < H; r++) col[r - 1] = fma(-m[r], rowk, col[r]);
+  col[H - 1] = rowk;
+  g = col_absmax_hi(col, g);
+}
+// This wavefront's verdict (uniform) over the columns its lanes hold; the caller repeats the elimination with gj12_pivoting on the
+// saved input when either wavefront objects.  Must be called by all 64 lanes.
+__device__ __forceinline__ bool gj12_dpp(double (&col)[H]) {
   float g = col_absmax_hi(col, 0.f);
   const unsigned int bound = max(__float_as_uint(g), 0x3FF00000u /* 1.0 */) + (8u << 20);  // kGrowthMax = 2^8
-#pragma nounroll
-  for (int k = 0; k < H; k++) {
-    double m[H];
-#pragma unroll
-    for (int r = 0; r < H; r++) m[r] = readlane_f64(col[r], k);  // the pivot column (lane k), pivot row first
-    // 1 / pivot: hardware reciprocal seed + two Newton steps (full double precision, a third of the divide's latency)
-    double inv = __builtin_amdgcn_rcp(m[0]);
-    inv = fma(fma(-m[0], inv, 1.0), inv, inv);
-    inv = fma(fma(-m[0], inv, 1.0), inv, inv);
-    const double rowk = col[0] * inv;
-#pragma unroll
-    for (int r = 1; r < H; r++) col[r - 1] = fma(-m[r], rowk, col[r]);
-    col[H - 1] = rowk;
-    g = col_absmax_hi(col, g);
-  }
+  gj12_dpp_step<0>(col, g); gj12_dpp_step<1>(col, g); gj12_dpp_step<2>(col, g); gj12_dpp_step<3>(col, g);
+  gj12_dpp_step<4>(col, g); gj12_dpp_step<5>(col, g); gj12_dpp_step<6>(col, g); gj12_dpp_step<7>(col, g);
+  gj12_dpp_step<8>(col, g); gj12_dpp_step<9>(col, g); gj12_dpp_step<10>(col, g); gj12_dpp_step<11>(col, g);
   // (g >= 0: its bits order like its value.  The last pivot row: not-a-number if any pivot was zero or not a number; idle lanes hold zeros)
   // The growth watch reads the doubles' high words as floats, and v_max3_f32 skips an operand that reads as a float NaN - which is what
   // the high word of a double beyond 2^1016, of an infinity or of a NaN looks like.  One INTEGER look at the end closes that hole
@@ -163,18 +182,6 @@ __device__ __forceinline__ bool gj12_loop(double (&col)[H]) {
 #pragma unroll
   for (int r = 0; r < H; r++) top = max(top, (unsigned int)__double2hiint(col[r]) & 0x7FFFFFFFu);
   return __all(__float_as_uint(g) <= bound && top < 0x7FF00000u);
-}
-// pivoted: the elimination went through gj12_pivoting (wave-uniform)
-__device__ __forceinline__ bool gj12(double (&col)[H], bool& pivoted) {
-  pivoted = false;
-  double keep[H];
-#pragma unroll
-  for (int r = 0; r < H; r++) keep[r] = col[r];
-  if (__builtin_expect(gj12_loop(col), 1)) return true;  // (wave-uniform)
-#pragma unroll
-  for (int r = 0; r < H; r++) col[r] = keep[r];
-  pivoted = true;
-  return gj12_pivoting(col);
 }
 
 __device__ void d_m3_mul(const double* A, const double* B, double* C) {
@@ -215,13 +222,47 @@ __device__ void d_so3_log(const double* R, double* out) {
   out[0] = f * K[0]; out[1] = f * K[1]; out[2] = f * K[2];
 }
 
+// R (+) v = R Exp(v), ONE ENTRY of the product per lane: lane e = 3 r + c of nine takes entry (r, c) of every matrix on the way.
+// d_so3_exp + d_m3_mul on one lane are ~300 double-precision instructions one behind the other; here the wavefront issues the
+// square root, sin, cos and ONE quotient (a lane divides the component its own entry of K holds: no exchange for K), then an entry's
+// five operations of (c1 K) K, of (I + s K) + K K and of R E - two exchanges through LDS (xk, xck, xe: nine doubles each, this
+// rotation's own) inside the wavefront.  Every expression is associated as d_so3_exp / d_m3_mul write it (sums left to right,
+// the identity below 1e-5): the same bits.
+__device__ __forceinline__ double boxplus_rot_entry(const double* v, const double* R, double* xk, double* xck, double* xe, int e) {
+#pragma clang fp contract(off)  // this unit is built with -ffp-contract=fast; the SO(3) helpers keep the reference's rounding (so3_math.h)
+  const int r = e / 3, cc = e % 3;
+  const double v1 = v[0], v2 = v[1], v3 = v[2];
+  const double n = sqrt(v1 * v1 + v2 * v2 + v3 * v3);
+  const double id = (r == cc) ? 1.0 : 0.0;
+  double E = id;
+  if (n > 0.00001) {  // (the nine lanes of a rotation agree)
+    // K = [0 -a2 a1; a2 0 -a0; -a1 a0 0], a = v / n: entry (r, c) off the diagonal holds component 3 - r - c, negated where c = r + 1 (mod 3)
+    const double a = v[r == cc ? 0 : 3 - r - cc] / n;
+    const double k = (r == cc) ? 0.0 : ((cc == (r + 1) % 3) ? -a : a);
+    const double s = sin(n), c1 = 1.0 - cos(n);
+    xk[e] = k;
+    xck[e] = c1 * k;  // `(1.0 - cos) * K * K` = ((1 - cos) K) K, so3_math.h:73
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const double kk = xck[3 * r] * xk[cc] + xck[3 * r + 1] * xk[3 + cc] + xck[3 * r + 2] * xk[6 + cc];
+    E = (id + s * k) + kk;
+  }
+  xe[e] = E;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return R[3 * r] * xe[cc] + R[3 * r + 1] * xe[3 + cc] + R[3 * r + 2] * xe[6 + cc];
+}
+
 // One iteration's solve + state update + schedule.  ne = the 91 reduced normal-equation scalars of this pass.
 // ONE workgroup of kSolveThreads = 256 lanes (round 1: a single wavefront, ~11 us of serial algebra per iteration).  Every
 // global input is fetched in ONE parallel batch into LDS (the control block and `ne` were just written by other kernels, so
 // each dependent global read would cost a full memory round trip); then
-//   phase A  G (78 lanes) | boxminus: the two rotation logarithms + the vector blocks (second wavefront) - side by side
+//   phase A  G (78 lanes) | boxminus: the vector blocks (last wavefront) - side by side
 //   phase A2 A = I + P11 G (144 lanes)
-//   phase B  the 12-step register-resident Gauss-Jordan (first wavefront - inherently serial) | u = H^T z - G vec (second)
+//   phase B  the 12-step register-resident Gauss-Jordan (first and second wavefront - inherently serial) | the two rotation
+//            logarithms, u = H^T z - G vec (third)
 //   phase C  solution (24 lanes), schedule, boxplus, and on the stopping iteration K H (288 entries) and the covariance
 //            (576 entries, 12 MACs each) over all 256 lanes.
 #ifdef LII_SOLVE_TRACE
@@ -266,6 +307,7 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   __shared__ double s_ne[96], s_st[36], s_prop[36];
   __shared__ int s_int[12];
   __shared__ int s_ok;
+  __shared__ double s_rx[2][3][9];  // boxplus: K, c1 K and Exp of the two rotations on their way between lanes
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   {
     const int* ci = &c->max_it;  // max_it, imu_en, it, search_next, stop, rematch_num, converged, searches, effect_num, singular, seq, plan_mask
@@ -288,7 +330,7 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   static const unsigned char kTri[78] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 51, 52, 53, 54, 55, 56, 57, 58, 59, 68, 69, 70, 71, 72, 73, 74, 75, 85, 86, 87, 88, 89, 90, 91, 102, 103, 104, 105, 106, 107, 119, 120, 121, 122, 123, 136, 137, 138, 139, 153, 154, 155, 170, 171, 187};
   // ---- phase A: A = I + P11 G on the first 144 lanes, straight from the 78 sums (G[k][j] = sum number tri(k, j)); meanwhile the
   // last wavefront spreads G out for the later phases and takes the vector blocks of vec = state_propagat (-) state.  (The two
-  // rotation logarithms of vec - 1.2 us of serial fp64 on two lanes - run beside the elimination, on the second wavefront.)
+  // rotation logarithms of vec - 1.2 us of serial fp64 on two lanes - run beside the elimination, on the third wavefront.)
   if (tid < H * H) {
     const int i = tid / H, j = tid % H;
     double s = (i == j) ? 1.0 : 0.0;
@@ -316,24 +358,26 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   LII_TS(2);
   LII_TS(3);
   // ---- phase B: K_1[:, :12]^T = A^-1 P[:12, :]  (A = I + P11 G;  K_1[:, :12] = P[:, :12] (I + G P11)^-1 and G, P symmetric).
-  // Gauss-Jordan on [A | P[:12, :]]: lanes 0..11 of the first wavefront hold the columns of A, lanes 12..35 the 24 columns of
-  // P[:12, :]; afterwards lane 12 + j holds row j of K_1[:, :12].  One elimination gives the gain directly - no inverse to
+  // Gauss-Jordan on [A | P[:12, :]]: every 16-lane row of the first two wavefronts holds the columns of A in its lanes 0..11 and four of
+  // the 24 columns of P[:12, :] in lanes 12..15 (gj12_dpp: wavefront 0 columns 0..15, wavefront 1 columns 16..23 in its rows 0 - 1);
+  // afterwards the lane of column j holds row j of K_1[:, :12].  One elimination gives the gain directly - no inverse to
   // store, no product - and no subtraction of nearly equal terms: the algebraically equal form [M P11 ; P21 - P21 G M P11]
   // cancels catastrophically once the pose block of P has collapsed (1e-8) next to velocity / bias blocks of order 1, the
-  // regime of the LIO phase.  Meanwhile the second wavefront forms u = H^T R^-1 z - G vec[:12] (then solution = K_1[:, :12] u
+  // regime of the LIO phase.  Meanwhile the third wavefront forms u = H^T R^-1 z - G vec[:12] (then solution = K_1[:, :12] u
   // + vec, the reference's K z + vec - K H vec[:12] regrouped).
-  if (wave == 0) {
+  if (wave < 2) {  // (all 64 lanes of both wavefronts go through the elimination: gj12_dpp)
+    const int p = lane & 15, j = 16 * wave + 4 * (lane >> 4) + (p - H);  // p >= 12: right-hand column j (wavefront 1, rows 2 - 3: none)
     double col[H];
 #pragma unroll
-    for (int r = 0; r < H; r++) col[r] = lane < H ? A[r * LDH + lane] : (lane < H + N ? s_cov[r * N + (lane - H)] : 0.0);
-    bool pivoted;
-    const bool ok = gj12(col, pivoted);
-    if (lane == 0) s_ok = ok ? (pivoted ? 2 : 1) : 0;
-    if (lane >= H && lane < H + N) {
+    for (int r = 0; r < H; r++) col[r] = p < H ? A[r * LDH + p] : (j < N ? s_cov[r * N + j] : 0.0);
+    if (!gj12_dpp(col)) {
+      if (lane == 0) s_ok = 3;  // (either wavefront: the elimination is repeated with row exchanges below)
+    } else if (p >= H && j < N) {
 #pragma unroll
-      for (int r = 0; r < H; r++) K1c[(lane - H) * LDH + r] = col[r];
+      for (int r = 0; r < H; r++) K1c[j * LDH + r] = col[r];
     }
-  } else if (wave == 1) {
+    LII_TS(5);  // (the elimination itself; stamp 4 includes the wait for the third wavefront at the barrier)
+  } else if (wave == 2) {
     if (lane < 2) {
       const int o = lane * 12, so = lane * 6;  // rot_end / offset_R_L_I
       double R[9];
@@ -349,6 +393,23 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
     }
   }
   __syncthreads();
+  // (uniform, rare) the growth watch of either wavefront objected: the saved input - A and s_cov are untouched - goes through
+  // gj12_pivoting in the single-wavefront layout (lanes 0..11: A, 12..35: P[:12, :]); every lane has read s_ok before it is rewritten
+  if (__builtin_expect(s_ok == 3, 0)) {
+    __syncthreads();
+    if (wave == 0) {
+      double col[H];
+#pragma unroll
+      for (int r = 0; r < H; r++) col[r] = lane < H ? A[r * LDH + lane] : (lane < H + N ? s_cov[r * N + (lane - H)] : 0.0);
+      const bool ok = gj12_pivoting(col);
+      if (lane == 0) s_ok = ok ? 2 : 0;
+      if (lane >= H && lane < H + N) {
+#pragma unroll
+        for (int r = 0; r < H; r++) K1c[(lane - H) * LDH + r] = col[r];
+      }
+    }
+    __syncthreads();
+  }
   if (!s_ok) {  // uniform
     if (tid == 0) { c->stop = 1; c->singular = 1; res_store(&res->singular, 1); }
     publish_done(res, s_int[10]);
@@ -376,19 +437,11 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   const unsigned int pm = (unsigned int)s_int[11];
   const bool pass_there = it + 1 >= 16 || ((pm >> (16 + it + 1)) & 1u), knn_there = it + 1 >= 16 || ((pm >> (it + 1)) & 1u);
   const int parked = !do_cov && (!pass_there || (search && !knn_there));
-  // state += solution : the two rotations on two lanes of the first wavefront, the vector blocks on 18 more; on the stopping
+  // state += solution : the two rotations on 2 x 9 lanes of the first wavefront (an entry each), the vector blocks on 18; on the stopping
   // iteration the other three wavefronts start on K H = K_1[:, :12] G (needed for the covariance only) right away
+  LII_TS(6);
   if (wave == 0) {
-    if (lane < 2) {
-      double E[9], Rn[9];
-      const int o = lane == 0 ? 0 : 12;  // rot_end / offset_R_L_I
-      const int so = lane == 0 ? 0 : 6;
-      d_so3_exp(sol[so], sol[so + 1], sol[so + 2], E);
-      d_m3_mul(s_st + o, E, Rn);
-      for (int e = 0; e < 9; e++) c->st[o + e] = Rn[e];
-      if (do_cov)
-        for (int e = 0; e < 9; e++) res_store(&res->st[o + e], Rn[e]);
-    } else if (lane >= 8 && lane < 26) {
+    if (lane >= 8 && lane < 26) {
       const int q = lane - 8;  // 0..17 : six 3-vectors
       const int blk = q / 3, i = q % 3;
       const int sto = blk == 0 ? 9 : (blk == 1 ? 21 : (blk == 2 ? 24 : (blk == 3 ? 27 : (blk == 4 ? 30 : 33))));
@@ -398,6 +451,13 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
       if (do_cov) res_store(&res->st[sto + i], v);
     } else if (lane >= 32 && lane < 32 + N) {
       c->solution[lane - 32] = sol[lane - 32];
+    }
+    if (lane < 32 && (lane & 15) < 9) {  // lanes 0..8: rot_end, 16..24: offset_R_L_I - one entry each (boxplus_rot_entry)
+      const int rho = lane >> 4, e = lane & 15, o = 12 * rho;
+      const double v = boxplus_rot_entry(sol + 6 * rho, s_st + o, s_rx[rho][0], s_rx[rho][1], s_rx[rho][2], e);
+      LII_TS(7);
+      c->st[o + e] = v;
+      if (do_cov) res_store(&res->st[o + e], v);
     }
     if (lane == 63) {
       c->converged = converged;

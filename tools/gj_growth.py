@@ -1,4 +1,4 @@
-"""Offline check of the growth-watched, pivot-free Gauss-Jordan of lii_iekf.hip (gj12_loop) on matrices A = I + P11 G, B = P[:12, :]
+"""Offline check of the growth-watched, pivot-free Gauss-Jordan of lii_iekf.hip (gj12_dpp; gj12_loop before it, the same arithmetic) on matrices A = I + P11 G, B = P[:12, :]
 taken from simulated LIO / LO sequences through the oracle: how often does the per-column growth test send an elimination to the
 pivoting fallback, how large is the growth, and how far is the pivot-free gain from the exactly (mpmath) computed one, next to
 the threshold-pivoted gain's distance."""
