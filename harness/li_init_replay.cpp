@@ -187,6 +187,9 @@ struct lii_replay {
   int32_t pcd_index = 0;             // flushes so far
   // lii_replay_set_local_map: lasermap_fov_segment (:914) + the box delete; off by default
   bool local_map = false, lm_placed = false, lm_in_job = false;
+  // lii_replay_set_map_history: points_cache_collect (:249-254, :304) - what the box delete removes is kept on the device; off by default
+  int32_t history_capacity = 0;
+  bool history_placed = false;
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -265,6 +268,45 @@ int lii_replay_set_local_map(lii_replay* r, int32_t on) {
   if (!r) return LII_ERR_INVALID;
   r->local_map = on != 0;
   r->lm_placed = false;
+  return LII_OK;
+}
+// capacity > 0: points_cache_collect (src/laserMapping.cpp:249-254, the last statement of lasermap_fov_segment, :304) - lii_map_removed_set(capacity)
+// is placed before the first scan is processed, beside lii_local_map_set: every point the box delete removes from then on is kept on the
+// device, and lii_replay_global_map hands the run's map at map resolution over.  0 (default): process() makes the calls it made before.
+int lii_replay_set_map_history(lii_replay* r, int32_t capacity) {
+  if (!r || capacity < 0) return LII_ERR_INVALID;
+  r->history_capacity = capacity;
+  r->history_placed = false;
+  return LII_OK;
+}
+// Everything the run has mapped: the history (acquired, not cleared) followed by the live map, packed xyz -> out (capacity points of
+// 3 floats; out may be NULL: *n only).  LII_ERR_STATE without lii_replay_set_map_history; LII_ERR_CAPACITY from the library when the
+// history buffer overflowed (what it holds is delivered all the same).
+int lii_replay_global_map(lii_replay* r, float* out, int32_t capacity, int32_t* n) {
+  if (!r || !n) return LII_ERR_INVALID;
+  *n = 0;
+  if (r->history_capacity <= 0) return fail(r, LII_ERR_STATE, "lii_replay_global_map: no history (lii_replay_set_map_history)");
+  int32_t n_hist = 0, n_map = 0;
+  int rc_hist = LII_OK;
+  if (r->history_placed) {  // (else: no scan has been processed yet)
+    rc_hist = lii_map_removed_acquire(r->h, nullptr, 0, &n_hist, 0);
+    if (rc_hist != LII_OK && rc_hist != LII_ERR_CAPACITY) return fail(r, rc_hist, std::string("lii_map_removed_acquire: ") + lii_last_error(r->h));
+  }
+  int rc = lii_map_download(r->h, nullptr, 0, &n_map);
+  if (rc != LII_OK) return fail(r, rc, std::string("lii_map_download: ") + lii_last_error(r->h));
+  *n = n_hist + n_map;
+  if (!out) return rc_hist;
+  if (capacity < *n) return fail(r, LII_ERR_CAPACITY, "lii_replay_global_map: capacity too small");
+  if (n_hist > 0) {
+    rc_hist = lii_map_removed_acquire(r->h, out, n_hist, &n_hist, 0);
+    if (rc_hist != LII_OK && rc_hist != LII_ERR_CAPACITY) return fail(r, rc_hist, std::string("lii_map_removed_acquire: ") + lii_last_error(r->h));
+  }
+  if (n_map > 0) {
+    rc = lii_map_download(r->h, out + 3 * size_t(n_hist), n_map, &n_map);
+    if (rc != LII_OK) return fail(r, rc, std::string("lii_map_download: ") + lii_last_error(r->h));
+  }
+  *n = n_hist + n_map;
+  if (rc_hist != LII_OK) return fail(r, rc_hist, std::string("lii_map_removed_acquire: ") + lii_last_error(r->h));
   return LII_OK;
 }
 // cloud: one LII_PUB_* bit, or 0 for what the last flush of the save buffer handed over; the last processed scan's points -> out
@@ -677,6 +719,12 @@ static int process(lii_replay* r) {
     if (rc != LII_OK) return fail(r, rc, std::string("lii_frame_select: ") + lii_last_error(r->h));
   }
   r->have_scan = true;
+  // ---- points_cache_collect (:304): the order stands before the first delete can run
+  if (r->history_capacity > 0 && !r->history_placed) {
+    const int rc = lii_map_removed_set(r->h, r->history_capacity);
+    if (rc != LII_OK) return fail(r, rc, std::string("lii_map_removed_set: ") + lii_last_error(r->h));
+    r->history_placed = true;
+  }
   // ---- lasermap_fov_segment (:914): behind the propagation, in front of the voxel filter
   if (r->local_map) {
     if (!r->lm_placed) {

@@ -179,6 +179,50 @@ typedef struct lii_local_map_info {
 int lii_local_map_set(lii_handle h, const lii_local_map_opts* opts);
 int lii_local_map_get(lii_handle h, lii_local_map_info* out);
 int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_info* out /* may be NULL */);
+/* ---- the history of what leaves the local map: points_cache_collect() (src/laserMapping.cpp:249-254, the last statement of
+ * lasermap_fov_segment, :304), which drains KD_TREE::acquire_removed_points (include/ikd-Tree/ikd_Tree.cpp:522-534) into _featsArray - the
+ * reference's store for everything that has left the map.  Upstream never deletes, so it loses nothing; the library does delete (quirk A6),
+ * and without this order what it deletes is gone: lii_local_map_info only counts it.  A buffer on the device, OFF until asked for: while the
+ * order is in force every point a BOX DELETE removes - lii_map_delete_boxes, lii_local_map_segment, the segment call a registration makes
+ * itself - is appended to it, by the launch that squeezes the point out of its cell (no launch is added: the moving local map stays at three
+ * launches of fixed size, lii_set_profiling(h, 3) counts the same with and without the order).
+ *   What is collected: exactly what the box delete removes - the reference's `point_deleted && !point_downsample_deleted`
+ *   (ikd_Tree.cpp:1242-1249); a point inside several boxes of one call once.  NOT collected: the points Add_Points replaces while it
+ *   down-samples (lii_map_add_points, lii_map_incremental, a registration's own map update); lii_map_reset / lii_map_build /
+ *   lii_map_build_from_scan and a rebuild of the index neither collect nor touch the buffer.
+ *   When: as the delete runs.  The reference hands the same points over LATER - when a rebuild happens to flatten the sub-tree that holds
+ *   them (ikd_Tree.cpp:1242-1249 sits in flatten) - so its timing depends on the shape of its tree; the multiset over a run is the same.
+ *   Order: unspecified - the buffer is a multiset of the map's stored float bits of x, y, z (16-byte records on the device, the fourth
+ *   float unspecified).
+ *   Overflow: the delete always completes, the map never depends on the buffer.  Points that find no room are not stored and are counted in
+ *   lost_total; nothing already held is overwritten.  From then on lii_map_removed_acquire / _view deliver what the buffer holds AND return
+ *   LII_ERR_CAPACITY, until an acquire with clear != 0 has emptied it (the rule of lii_publish_saved).
+ *   lii_map_removed_set      capacity in points.  0: collecting off, the contents stay readable.  The capacity the buffer already has: on
+ *                            (again), the contents and totals stay.  Any other: a new, empty buffer, totals zero.  The first order that asks
+ *                            for a buffer creates it (16 bytes a point).
+ *   lii_map_removed_get      waits for the stream and reports (as lii_local_map_get does).
+ *   lii_map_removed_acquire  packed xyz as lii_map_download delivers it; xyz_out == NULL: *n only (nothing is cleared then; LII_ERR_CAPACITY
+ *                            all the same behind an overflow).  clear != 0:
+ *                            the buffer is empty behind the call - acquire returns and clears; the totals go on counting.
+ *   lii_map_removed_view     the records where they lie: *dev_float4 is valid until the next call that deletes or clears.
+ * Refusals.  LII_ERR_INVALID: negative capacity, NULL arguments (xyz_out excepted), a bad struct_size.  LII_ERR_CAPACITY with nothing
+ * cleared: capacity < *n.  LII_ERR_STATE: _get / _acquire / _view before any lii_map_removed_set; a call from inside
+ * lii_scan_job::while_waiting (these calls use the handle's stream; like every entry point they end a pre-armed launch first).  Of
+ * everything else the calls are observers: neighbour lists, IMU carry and publish order stay as they are.  With a communicator attached the
+ * order works wherever lii_map_delete_boxes does: the maps are replicated, every rank collects the same multiset (lii_local_map_* stays
+ * single rank). */
+typedef struct lii_map_removed_info {
+  uint32_t struct_size; /* sizeof(lii_map_removed_info): set by the caller, checked */
+  int32_t capacity;     /* points; 0: off */
+  int32_t held;         /* points in the buffer */
+  int32_t reserved;
+  int64_t collected_total; /* stored since the lii_map_removed_set that made the buffer */
+  int64_t lost_total;      /* not stored for lack of room since then */
+} lii_map_removed_info;
+int lii_map_removed_set(lii_handle h, int32_t capacity);
+int lii_map_removed_get(lii_handle h, lii_map_removed_info* out);
+int lii_map_removed_acquire(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n, int32_t clear);
+int lii_map_removed_view(lii_handle h, const void** dev_float4, int32_t* n);
 int lii_map_size(lii_handle h, int32_t* n_valid);
 int lii_map_download(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n);
 /* Kept for callers of ABI 1: the device map is always current (updates are applied in place); waits for the stream. */

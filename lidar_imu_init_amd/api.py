@@ -76,6 +76,11 @@ class lii_local_map_info(C.Structure):
                 ("last_boxes", C.c_float * 18), ("last_n_deleted", C.c_int32), ("moves", C.c_int32), ("deleted_total", C.c_int64)]
 
 
+class lii_map_removed_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_int32), ("held", C.c_int32), ("reserved", C.c_int32),
+                ("collected_total", C.c_int64), ("lost_total", C.c_int64)]
+
+
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
@@ -178,6 +183,10 @@ _DECLS = {
     "lii_local_map_get": (C.c_int, [C.c_void_p, C.POINTER(lii_local_map_info)]),
     "lii_local_map_segment": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(lii_local_map_info)]),
     "lii_params_local_map": (C.c_int, [C.c_void_p, C.POINTER(lii_local_map_opts)]),
+    "lii_map_removed_set": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_map_removed_get": (C.c_int, [C.c_void_p, C.POINTER(lii_map_removed_info)]),
+    "lii_map_removed_acquire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "lii_map_removed_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "lii_publish_set": (C.c_int, [C.c_void_p, C.POINTER(lii_publish_opts)]),
     "lii_publish_now": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lii_publish_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
@@ -448,6 +457,45 @@ class Registrar:
         info = lii_local_map_info()
         self._check(self.L.lii_local_map_segment(self.h, p, C.byref(info)))
         return self._local_map_info(info)
+
+    # ---- the history of what box deletes remove (points_cache_collect / acquire_removed_points)
+    def map_removed_set(self, capacity):
+        """lii_map_removed_set: a device buffer of `capacity` points that every box delete appends its points to; 0: off (the contents stay
+        readable), the same capacity again: contents kept, another: a new, empty buffer."""
+        self._check(self.L.lii_map_removed_set(self.h, int(capacity)))
+
+    def map_removed_get(self) -> dict:
+        """capacity (0: off), held, collected_total, lost_total (waits for the stream)."""
+        info = lii_map_removed_info(C.sizeof(lii_map_removed_info))
+        self._check(self.L.lii_map_removed_get(self.h, C.byref(info)))
+        return {"capacity": int(info.capacity), "held": int(info.held), "collected_total": int(info.collected_total),
+                "lost_total": int(info.lost_total)}
+
+    def map_removed_acquire(self, clear=False, strict=True):
+        """The history buffer as (n, 3) float32, in no particular order; clear: the buffer is empty afterwards.  A buffer that overflowed
+        raises LIIError(-4) BEFORE anything is delivered or cleared; strict=False delivers what it holds instead."""
+        n = C.c_int32(0)
+        rc = self.L.lii_map_removed_acquire(self.h, None, 0, C.byref(n), 0)  # (the count; -4: overflowed - nothing is cleared by this form)
+        if rc != 0 and (strict or rc != -4):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        rc = self.L.lii_map_removed_acquire(self.h, _ptr(out), len(out), C.byref(n), int(bool(clear)))
+        if rc != 0 and (strict or rc != -4):
+            self._check(rc)
+        return out[:n.value]
+
+    def map_removed_view(self):
+        """(device float4 records as an object with __cuda_array_interface__ - torch.as_tensor(v, device="cuda") -, n); valid until the next
+        call that deletes or clears.  n == 0: (None, 0)."""
+        p, n = C.c_void_p(), C.c_int32(0)
+        self._check(self.L.lii_map_removed_view(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0 or not p.value:
+            return None, 0
+        return _DeviceFloat4(p.value, n.value), n.value
+
+    def global_map(self):
+        """Everything the run has mapped, at map resolution: the history (acquired, not cleared) followed by map_download()."""
+        return np.concatenate([self.map_removed_acquire(clear=False), self.map_download()])
 
     def map_size(self) -> int:
         n = C.c_int32(0)

@@ -290,6 +290,13 @@ lii::WinKeep win_keep_view(lii_handle h) {
   }
   return wk;
 }
+lii::RemovedSink removed_sink(lii_handle h) {
+  lii::RemovedSink rs = {};
+  if (h->rm.on && h->rm.d_buf && h->rm.d_ctr && h->rm.cap > 0) {
+    rs.buf = h->rm.d_buf; rs.reserved = h->rm.d_ctr; rs.cap = (unsigned int)h->rm.cap;
+  }
+  return rs;
+}
 int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, const float4* extra, int n_extra, bool beside,
               const int* n_list_dev, const int* n_extra_dev, bool count_events, bool prefilled) {
   hipStream_t s = h->stream;
@@ -435,7 +442,8 @@ int local_map_enqueue(lii_handle h, const double* pos_dev, const double* pos, bo
   const lii::WinKeep wk = win_keep_view(h);
   if (!wk.win && h->win_valid) { h->win_valid = false; h->win_dropped++; }  // (cell entries may change: a window that is not kept current goes)
   if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
-  launch_cell_apply_listed(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, h->work_cap, wk, s);
+  const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
+  launch_cell_apply_listed(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, h->work_cap, wk, s, &rs);
   if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
   launch_local_map_finish(L.d_state + (L.cur ^ 1), h->d_mapctr, L.h_state, L.seq, s);
   HIPCHK(h, hipGetLastError());
@@ -586,7 +594,8 @@ int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int3
   launch_box_tomb_cells(h->d_pts, h->d_cells, ne, d_boxes, n_boxes, h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
   const lii::WinKeep wk = win_keep_view(h);
   if (!wk.win) h->win_valid = false;
-  launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, ne, wk, s);
+  const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
+  launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, ne, wk, s, &rs);
   launch_ins_write(h->d_pts, h->d_ins_e, 0, nullptr, nullptr, nullptr, 0, nullptr, h->d_cells, h->d_cell_cap, h->d_pts, h->d_mapctr, h->d_dropped, h->drop_cap,
                    s, nullptr, 0, 0, 0, wk);  // (re-arms the work list)
   rc = map_counters(h);
@@ -657,6 +666,126 @@ int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_i
   local_map_settle(h);
   if (h->lm.h_state->n_deleted != 0) h->have_search = false;
   local_map_info_out(*h->lm.h_state, out);
+  return LII_OK;
+}
+// ------------------------------------------------------------------------------------------------ the history of removed points
+namespace {
+// what the buffer holds (and how many records were asked for) once the stream has passed every delete enqueued so far
+int removed_read(lii_handle h, const char* who, long long* reserved, int* held) {
+  lii_context::Removed& R = h->rm;
+  *reserved = 0; *held = 0;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!R.d_ctr) return LII_OK;  // (only lii_map_removed_set(h, 0) so far: nothing was ever collected)
+  unsigned long long r = 0;
+  HIPCHK(h, hipMemcpy(&r, R.d_ctr, sizeof(r), hipMemcpyDeviceToHost));
+  if (r > (unsigned long long)0x3FFFFFFFFFFFFFFFll) return fail(h, LII_ERR_HIP, std::string(who) + ": counter out of range");
+  *reserved = (long long)r;
+  *held = int(std::min<long long>((long long)r, (long long)R.cap));
+  return LII_OK;
+}
+int removed_entry(lii_handle h, const char* who, bool args_ok) {
+  if (!h) return LII_ERR_INVALID;
+  if (!args_ok) return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, std::string(who) + ": a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  return LII_OK;
+}
+}  // namespace
+int lii_map_removed_set(lii_handle h, int32_t capacity) {
+  int rc = removed_entry(h, "lii_map_removed_set", capacity >= 0);
+  if (rc != LII_OK) return rc;
+  lii_context::Removed& R = h->rm;
+  if (capacity == 0) {  // off: what the buffer holds stays readable
+    R.on = false;
+    R.set = true;
+    return LII_OK;
+  }
+  if (R.d_buf && capacity == R.cap) {  // the same order again: the contents stay
+    R.on = true;
+    R.set = true;
+    return LII_OK;
+  }
+  // a new, empty buffer (the old one goes first: the peak is the new size); the totals start over
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (a delete still on the stream writes to the old one)
+  R.on = false;
+  R.cap = 0;
+  R.d_buf.reset();
+  HIPCHK(h, R.d_buf.alloc(size_t(capacity)));
+  if (!R.d_ctr) HIPCHK(h, R.d_ctr.alloc(2));
+  HIPCHK(h, hipMemset(R.d_ctr, 0, 2 * sizeof(unsigned long long)));
+  R.cap = capacity;
+  R.collected_base = 0;
+  R.lost_base = 0;
+  R.on = true;
+  R.set = true;
+  return LII_OK;
+}
+int lii_map_removed_get(lii_handle h, lii_map_removed_info* out) {
+  static_assert(sizeof(lii_map_removed_info) == 32, "lii_map_removed_info layout");
+  int rc = removed_entry(h, "lii_map_removed_get", out != nullptr && out->struct_size == sizeof(lii_map_removed_info));
+  if (rc != LII_OK) return rc;
+  lii_context::Removed& R = h->rm;
+  if (!R.set) return fail(h, LII_ERR_STATE, "lii_map_removed_get: no history buffer (lii_map_removed_set)");
+  long long reserved = 0;
+  int held = 0;
+  rc = removed_read(h, "lii_map_removed_get", &reserved, &held);
+  if (rc != LII_OK) return rc;
+  out->struct_size = sizeof(lii_map_removed_info);
+  out->capacity = R.on ? R.cap : 0;
+  out->held = held;
+  out->reserved = 0;
+  out->collected_total = R.collected_base + held;
+  out->lost_total = R.lost_base + (reserved - held);
+  return LII_OK;
+}
+int lii_map_removed_acquire(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n, int32_t clear) {
+  int rc = removed_entry(h, "lii_map_removed_acquire", n != nullptr);
+  if (rc != LII_OK) return rc;
+  lii_context::Removed& R = h->rm;
+  if (!R.set) return fail(h, LII_ERR_STATE, "lii_map_removed_acquire: no history buffer (lii_map_removed_set)");
+  long long reserved = 0;
+  int held = 0;
+  rc = removed_read(h, "lii_map_removed_acquire", &reserved, &held);
+  if (rc != LII_OK) return rc;
+  *n = held;
+  const char* const overflowed = "lii_map_removed_acquire: the history buffer overflowed - points were removed that it could not store (what it held is intact)";
+  if (!xyz_out) return reserved > held ? fail(h, LII_ERR_CAPACITY, overflowed) : LII_OK;  // (the count only: nothing is delivered, so nothing is cleared either)
+  if (capacity < held) return fail(h, LII_ERR_CAPACITY, "lii_map_removed_acquire: capacity too small");
+  // through the pinned staging buffer, a piece of it at a time (the history may be larger than the map)
+  const size_t piece = std::max<size_t>(h->h_stage.size(), 1);
+  if (held > 0) HIPCHK(h, hipEventSynchronize(h->ev_stage));  // an asynchronous scan upload may still be reading the staging buffer
+  for (size_t at = 0; at < size_t(held); at += piece) {
+    const size_t m = std::min(piece, size_t(held) - at);
+    HIPCHK(h, hipMemcpyAsync(h->h_stage, R.d_buf + at, sizeof(float4) * m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < m; i++) {
+      xyz_out[3 * (at + i)] = h->h_stage[i].x;
+      xyz_out[3 * (at + i) + 1] = h->h_stage[i].y;
+      xyz_out[3 * (at + i) + 2] = h->h_stage[i].z;
+    }
+  }
+  if (clear) {
+    R.collected_base += held;
+    R.lost_base += reserved - held;
+    HIPCHK(h, hipMemset(R.d_ctr, 0, 2 * sizeof(unsigned long long)));
+  }
+  if (reserved > held)
+    return fail(h, LII_ERR_CAPACITY, overflowed);
+  return LII_OK;
+}
+int lii_map_removed_view(lii_handle h, const void** dev_float4, int32_t* n) {
+  int rc = removed_entry(h, "lii_map_removed_view", dev_float4 != nullptr && n != nullptr);
+  if (rc != LII_OK) return rc;
+  lii_context::Removed& R = h->rm;
+  if (!R.set) return fail(h, LII_ERR_STATE, "lii_map_removed_view: no history buffer (lii_map_removed_set)");
+  long long reserved = 0;
+  int held = 0;
+  rc = removed_read(h, "lii_map_removed_view", &reserved, &held);
+  if (rc != LII_OK) return rc;
+  *dev_float4 = R.d_buf.get();
+  *n = held;
+  if (reserved > held)
+    return fail(h, LII_ERR_CAPACITY, "lii_map_removed_view: the history buffer overflowed - points were removed that it could not store (what it holds is intact)");
   return LII_OK;
 }
 int lii_map_size(lii_handle h, int32_t* n_valid) {

@@ -334,6 +334,16 @@ struct lii_context {
     bool in_job = false;         // scan_register_job -> update_on_device: this update segments behind commit_map, in front of its first search
     bool counts_pending = false; // a call has been enqueued whose deletes the host's copy of the live-point count does not hold yet
   } lm;
+  // ---- the history of what box deletes remove (lii_map_removed_*, lii_capi_map.cpp; collected by the squeeze of a box delete, lii_map.hip):
+  // a standing order, off by default.  Nothing here exists before the first lii_map_removed_set that asks for a buffer.
+  struct Removed {
+    bool set = false;            // lii_map_removed_set has been accepted once (get / acquire / view work from then on)
+    bool on = false;             // box deletes collect
+    int cap = 0;                 // points d_buf holds (the capacity of the last order that asked for a buffer)
+    DevBuf<float4> d_buf;
+    DevBuf<unsigned long long> d_ctr;  // [0]: RemovedSink::reserved
+    long long collected_base = 0, lost_base = 0;  // the totals up to the last clear (what the buffer holds now is counted on top)
+  } rm;
   void* ingest = nullptr;  // lii_ingest.hip state (frames of the last driver message)
   bool ingest_sort_always = false;  // LII_INGEST_SORT=always: the ingest never leaves the time sort out (IngestRing::never_predict)
 
@@ -415,6 +425,7 @@ constexpr int kMapFlagSeqAt = 40;  // (h_mapflag: 64 ints; [0, kMapCtrWords + 8)
 int map_update_early(lii_handle h);  // 1: enqueued behind the passes of the update in progress, 0: not possible this time, < 0: error
 int commit_map(lii_handle h);
 int map_counters(lii_handle h, bool already_synced = false);
+lii::RemovedSink removed_sink(lii_handle h);  // the history buffer as the launches of a box delete take it (buf == nullptr: nothing is collected)
 lii::WinKeep win_keep_view(lii_handle h);  // the window as the update's launches keep it current (win == nullptr: nothing to keep)
 // one lasermap_fov_segment + Delete_Point_Boxes on the handle's stream (three launches); pos_dev: state.pos_end in device memory, else pos by
 // value.  The caller has joined the map update in flight.  mark: lii_set_profiling(h, 3) brackets the launches (LII_KP_VOXEL)

@@ -268,8 +268,16 @@ void launch_add_fold_hashed(const float4* add_pts, int n, const int* n_dev, floa
 void launch_ins_cells(const float4* list, const unsigned int* flags, int n, const int* n_dev, const float4* list2, int n2, const int* n2_dev, unsigned int* ins_e2,
                       BlockEntry* blocks, unsigned int mask, float inv_cs, unsigned int tables_cap, unsigned int* ins_e, unsigned int* tp,
                       unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s);
+// the history of what box deletes remove (lii_map_removed_*): the squeeze of a box delete appends the points it drops.  `reserved` counts the
+// records asked for since the last clear - it runs past `cap` when the buffer is full: min(reserved, cap) records are held, the rest was not stored.
+struct RemovedSink {
+  float4* buf;                   // cap records (nullptr: nothing is collected - the launches take the forms they have without the order)
+  unsigned long long* reserved;
+  unsigned int cap;
+};
+// removed != nullptr with a buffer: the launch serves a box delete and collects (every tombstone is a box tombstone); the fold's updates pass none
 void launch_cell_apply(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
-                       unsigned int pts_cap, int launch_bound, const WinKeep& wk, hipStream_t s);
+                       unsigned int pts_cap, int launch_bound, const WinKeep& wk, hipStream_t s, const RemovedSink* removed = nullptr);
 void launch_ins_write(const float4* list, const unsigned int* ins_e, int n, const int* n_dev, const float4* list2, const unsigned int* ins_e2, int n2, const int* n2_dev,
                       uint2* cells, const unsigned int* cell_cap, float4* pts, int* ctr, float4* dropped, unsigned int drop_cap, hipStream_t s,
                       int* host, int n_words, int seq_at, int seq, const WinKeep& wk)  /* host != nullptr: the last workgroup publishes the counters there */;
@@ -288,7 +296,7 @@ void launch_local_map_tomb(const LocalMapState* in, LocalMapState* out, const Lo
                            const uint2* cells, const unsigned long long* key_of_id, int n_blocks, float cs, unsigned char* tomb, unsigned int* tp,
                            unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s);
 void launch_cell_apply_listed(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
-                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s);
+                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s, const RemovedSink* removed = nullptr);
 void launch_local_map_finish(LocalMapState* st, int* ctr, LocalMapState* host, int seq, hipStream_t s);
 
 // the registered clouds of a scan (lii_publish.hip: k_publish_world)

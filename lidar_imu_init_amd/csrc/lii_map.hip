@@ -12,6 +12,8 @@
 //                         every insert, squeeze the touched cells (moving one to the tail of the array when its slack is used
 //                         up), claim a slot per insert.  Inserts that find no room wait in a list for the host's rebuild.
 //   k_box_tomb_cells      KD_TREE::Delete_Point_Boxes                                  include/ikd-Tree/ikd_Tree.cpp:500-516
+//   k_cell_apply_collect / k_cell_apply_listed_collect   the squeeze of a BOX delete that also keeps what it drops (lii_map_removed_set):
+//                         KD_TREE::acquire_removed_points, include/ikd-Tree/ikd_Tree.cpp:522-534, :1242-1249 - one reservation per wavefront
 //   k_cell_caps / k_spread / k_cell_counts / k_gather_live   (re)build: compact cell-sorted array <-> slack layout
 // Set equivalence with the tree is tested against the oracle's restated tree and against the unmodified reference tree
 // (tests/test_gpu_map.py).  Ties between equal squared distances to the voxel centre are broken by map order here and by
@@ -68,6 +70,40 @@ __device__ __forceinline__ void wave_atomic_add_few(unsigned int* ctr, bool has,
     m &= m - 1ull;
   }
   if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1 && sum != 0u) atomicAdd(ctr, sum);
+}
+
+// wave_reserve: one range of a shared list for the whole wavefront - the lanes' counts laid end to end, ONE atomic on the list's counter;
+// returns where the lane's own part begins.  Any set of active lanes: a full wavefront (what both squeeze kernels of a box delete arrange)
+// scans in six steps, any other set walks the contributors' bits as wave_atomic_add_few does.  Nothing to reserve: no atomic at all.
+__device__ __forceinline__ unsigned long long wave_reserve(unsigned long long* ctr, unsigned int cnt) {
+  const unsigned long long act = __ballot(1);
+  const int lane = threadIdx.x & 63;
+  unsigned int below = 0, total = 0;
+  if (act == ~0ull) {  // (uniform)
+    unsigned int incl = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned int v = (unsigned int)__shfl_up((int)incl, off);
+      if (lane >= off) incl += v;
+    }
+    below = incl - cnt;
+    total = (unsigned int)__shfl((int)incl, 63);
+  } else {
+    unsigned long long m = __ballot(cnt != 0u);
+    while (m) {
+      const int l = __ffsll((long long)m) - 1;
+      const unsigned int v = (unsigned int)__shfl((int)cnt, l);
+      if (l < lane) below += v;
+      total += v;
+      m &= m - 1ull;
+    }
+  }
+  if (total == 0u) return 0ull;  // (uniform)
+  const int leader = __ffsll((long long)act) - 1;
+  unsigned long long base = 0ull;
+  if (lane == leader) base = atomicAdd(ctr, (unsigned long long)total);
+  const unsigned int lo = (unsigned int)__shfl((int)(unsigned int)base, leader), hi = (unsigned int)__shfl((int)(unsigned int)(base >> 32), leader);
+  return (((unsigned long long)hi << 32) | lo) + below;
 }
 
 __device__ __forceinline__ bool d_same_point(float ax, float ay, float az, float bx, float by, float bz) {
@@ -664,10 +700,27 @@ __global__ void k_ins_cells(const float4* __restrict__ list, const unsigned int*
   ins_cell_one(list[i], &ins_e[i], a);
 }
 
+// the tombstones of one listed cell, counted in front of its squeeze (the collecting form: what the wavefront reserves in the history buffer)
+__device__ __forceinline__ unsigned int cell_count_tombs(const unsigned int e, const uint2* __restrict__ cells, const unsigned char* __restrict__ tomb) {
+  const uint2 c = cells[e];
+  unsigned int n = 0;
+  for (unsigned int j0 = c.x; j0 < c.y; j0 += 8u) {
+    unsigned char t[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) t[u] = tomb[min(j0 + (unsigned)u, c.y - 1u)];
+#pragma unroll
+    for (int u = 0; u < 8; u++) n += (j0 + (unsigned)u < c.y && t[u]) ? 1u : 0u;
+  }
+  return n;
+}
 // one listed cell: its tombstones squeezed out, the cell moved to the tail when survivors + pending inserts outgrow it; returns the points gone
+// COLLECT (a box delete with lii_map_removed_set in force): the points that go are appended to the history buffer on the way out - the squeeze
+// holds every slot of the cell together with its tombstone anyway - from place `at` of the wavefront's reservation on; a place past the
+// buffer's capacity is not written (the host takes what was lost from the counter).  COLLECT = false is the squeeze as it was.
+template <bool COLLECT>
 __device__ __forceinline__ int cell_apply_one(const unsigned int e, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap, float4* __restrict__ pts,
                                               unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr, unsigned int pts_cap,
-                                              const WinKeep& wk) {
+                                              const WinKeep& wk, const RemovedSink& rs = RemovedSink(), unsigned long long at = 0ull) {
   const uint2 c = cells[e];
   const unsigned int tpv = tp[e], capv = cell_cap[e];  // (loaded beside the cell entry, not behind the squeeze)
   unsigned int first = c.x, end = c.y, wpos = c.x;
@@ -691,6 +744,10 @@ __device__ __forceinline__ int cell_apply_one(const unsigned int e, uint2* __res
           wpos++;
         } else {
           tomb[j] = 0;
+          if (COLLECT) {
+            if (at < (unsigned long long)rs.cap) rs.buf[at] = p[u];
+            at++;
+          }
         }
       }
     }
@@ -732,7 +789,23 @@ __global__ void k_cell_apply(const unsigned int* __restrict__ work, uint2* __res
   const bool valid = w < n_work && w < launch_bound;
   if (!__any(valid)) return;  // (uniform per wavefront)
   int gone = 0;
-  if (valid) gone = cell_apply_one(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
+  if (valid) gone = cell_apply_one<false>(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
+  wave_atomic_add_all(&ctr[kMapCtrValid], -gone);
+}
+// k_cell_apply behind a box delete whose points are collected (lii_map_delete_boxes with lii_map_removed_set in force): every lane counts its
+// cell's tombstones, the wavefront reserves their sum with one atomic, the squeeze writes them out.  All 64 lanes reach the reservation.
+__global__ void k_cell_apply_collect(const unsigned int* __restrict__ work, uint2* __restrict__ cells, unsigned int* __restrict__ cell_cap,
+                                     float4* __restrict__ pts, unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr,
+                                     unsigned int pts_cap, int launch_bound, WinKeep wk, RemovedSink rs) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n_work = ctr[kMapCtrWork];
+  const bool valid = w < n_work && w < launch_bound;
+  if (!__any(valid)) return;  // (uniform per wavefront)
+  const unsigned int e = valid ? work[w] : 0u;
+  const unsigned int cnt = valid ? cell_count_tombs(e, cells, tomb) : 0u;
+  const unsigned long long at = wave_reserve(rs.reserved, cnt);
+  int gone = 0;
+  if (valid) gone = cell_apply_one<true>(e, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk, rs, at);
   wave_atomic_add_all(&ctr[kMapCtrValid], -gone);
 }
 
@@ -966,7 +1039,28 @@ __global__ __launch_bounds__(256) void k_cell_apply_listed(const unsigned int* _
   const int total = (int)(gridDim.x * blockDim.x);
   int gone = 0;
   for (int w = (int)(blockIdx.x * blockDim.x + threadIdx.x); w < n_work; w += total)
-    gone += cell_apply_one(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
+    gone += cell_apply_one<false>(work[w], cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk);
+  wave_atomic_add_all(&ctr[kMapCtrValid], -gone);  // (every lane of the wavefront arrives here)
+}
+// ... and its collecting form (the moving local map with lii_map_removed_set in force).  The striding loop runs by the WAVEFRONT's trip count -
+// its first lane's - so that all 64 lanes reserve together in every trip, a lane past the end of the list with a count of 0 (wave_reserve
+// would serve any other set of lanes too, at a walk over the contributors instead of a scan).
+__global__ __launch_bounds__(256) void k_cell_apply_listed_collect(const unsigned int* __restrict__ work, uint2* __restrict__ cells,
+                                                                   unsigned int* __restrict__ cell_cap, float4* __restrict__ pts,
+                                                                   unsigned char* __restrict__ tomb, unsigned int* __restrict__ tp, int* __restrict__ ctr,
+                                                                   unsigned int pts_cap, unsigned int work_cap, WinKeep wk, RemovedSink rs) {
+  const int n_work = min(ctr[kMapCtrWork], (int)work_cap);
+  if (n_work <= 0) return;  // (uniform) a scan that moves nothing: the order costs this launch nothing
+  const int total = (int)(gridDim.x * blockDim.x), lane = (int)(threadIdx.x & 63);
+  int gone = 0;
+  for (int w0 = (int)(blockIdx.x * blockDim.x + threadIdx.x) - lane; w0 < n_work; w0 += total) {
+    const int w = w0 + lane;
+    const bool valid = w < n_work;
+    const unsigned int e = valid ? work[w] : 0u;
+    const unsigned int cnt = valid ? cell_count_tombs(e, cells, tomb) : 0u;
+    const unsigned long long at = wave_reserve(rs.reserved, cnt);
+    if (valid) gone += cell_apply_one<true>(e, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, wk, rs, at);
+  }
   wave_atomic_add_all(&ctr[kMapCtrValid], -gone);  // (every lane of the wavefront arrives here)
 }
 __global__ __launch_bounds__(64) void k_local_map_finish(LocalMapState* __restrict__ st, int* __restrict__ ctr, LocalMapState* __restrict__ host, int seq) {
@@ -995,8 +1089,12 @@ void launch_ins_cells(const float4* list, const unsigned int* flags, int n, cons
     hipLaunchKernelGGL(k_ins_cells, dim3(nblk(n + n2, 256)), dim3(256), 0, s, list, flags, n, n_dev, list2, n2, n2_dev, ins_e2, ins_e, a);
 }
 void launch_cell_apply(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
-                       unsigned int pts_cap, int launch_bound, const WinKeep& wk, hipStream_t s) {
-  if (launch_bound > 0) hipLaunchKernelGGL(k_cell_apply, dim3(nblk(launch_bound, 128)), dim3(128), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, launch_bound, wk);
+                       unsigned int pts_cap, int launch_bound, const WinKeep& wk, hipStream_t s, const RemovedSink* removed) {
+  if (launch_bound <= 0) return;
+  if (removed && removed->buf)
+    hipLaunchKernelGGL(k_cell_apply_collect, dim3(nblk(launch_bound, 128)), dim3(128), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, launch_bound, wk, *removed);
+  else
+    hipLaunchKernelGGL(k_cell_apply, dim3(nblk(launch_bound, 128)), dim3(128), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, launch_bound, wk);
 }
 void launch_ins_write(const float4* list, const unsigned int* ins_e, int n, const int* n_dev, const float4* list2, const unsigned int* ins_e2, int n2, const int* n2_dev,
                       uint2* cells, const unsigned int* cell_cap, float4* pts, int* ctr, float4* dropped, unsigned int drop_cap, hipStream_t s,
@@ -1034,8 +1132,11 @@ void launch_local_map_tomb(const LocalMapState* in, LocalMapState* out, const Lo
   hipLaunchKernelGGL(k_local_map_tomb, dim3(kLocalMapGrid), dim3(256), 0, s, a, pts, cells, key_of_id, n_blocks, cs, tomb, tp, work, ctr, work_cap);
 }
 void launch_cell_apply_listed(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
-                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s) {
-  hipLaunchKernelGGL(k_cell_apply_listed, dim3(kLocalMapGrid), dim3(256), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, work_cap, wk);
+                              unsigned int pts_cap, unsigned int work_cap, const WinKeep& wk, hipStream_t s, const RemovedSink* removed) {
+  if (removed && removed->buf)
+    hipLaunchKernelGGL(k_cell_apply_listed_collect, dim3(kLocalMapGrid), dim3(256), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, work_cap, wk, *removed);
+  else
+    hipLaunchKernelGGL(k_cell_apply_listed, dim3(kLocalMapGrid), dim3(256), 0, s, work, cells, cell_cap, pts, tomb, tp, ctr, pts_cap, work_cap, wk);
 }
 void launch_local_map_finish(LocalMapState* st, int* ctr, LocalMapState* host, int seq, hipStream_t s) {
   hipLaunchKernelGGL(k_local_map_finish, dim3(1), dim3(64), 0, s, st, ctr, host, seq);
