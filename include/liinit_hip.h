@@ -183,11 +183,13 @@ int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_i
  * lasermap_fov_segment, :304), which drains KD_TREE::acquire_removed_points (include/ikd-Tree/ikd_Tree.cpp:522-534) into _featsArray - the
  * reference's store for everything that has left the map.  Upstream never deletes, so it loses nothing; the library does delete (quirk A6),
  * and without this order what it deletes is gone: lii_local_map_info only counts it.  A buffer on the device, OFF until asked for: while the
- * order is in force every point a BOX DELETE removes - lii_map_delete_boxes, lii_local_map_segment, the segment call a registration makes
- * itself - is appended to it, by the launch that squeezes the point out of its cell (no launch is added: the moving local map stays at three
- * launches of fixed size, lii_set_profiling(h, 3) counts the same with and without the order).
- *   What is collected: exactly what the box delete removes - the reference's `point_deleted && !point_downsample_deleted`
- *   (ikd_Tree.cpp:1242-1249); a point inside several boxes of one call once.  NOT collected: the points Add_Points replaces while it
+ * order is in force every point a DELETE removes - by box: lii_map_delete_boxes, lii_local_map_segment, the segment call a registration
+ * makes itself; by point: lii_map_delete_points, lii_map_delete_points_dev - is appended to it, by the launch that squeezes the point out of
+ * its cell (no launch is added: the moving local map stays at three launches of fixed size, lii_set_profiling(h, 3) counts the same with
+ * and without the order).
+ *   What is collected: exactly what the delete removes - the reference's `point_deleted && !point_downsample_deleted`
+ *   (ikd_Tree.cpp:1242-1249), which holds for the victims of Delete_by_range and of Delete_by_point alike; a point inside several boxes
+ *   of one call once, a stored point that a list of points names once for every copy it takes.  NOT collected: the points Add_Points replaces while it
  *   down-samples (lii_map_add_points, lii_map_incremental, a registration's own map update); lii_map_reset / lii_map_build /
  *   lii_map_build_from_scan and a rebuild of the index neither collect nor touch the buffer.
  *   When: as the delete runs.  The reference hands the same points over LATER - when a rebuild happens to flatten the sub-tree that holds
@@ -256,6 +258,46 @@ int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_byt
                     float* pts_out /* n*k*3 */, float* d2_out /* n*k */, int32_t* count_out /* n */);
 int lii_map_nearest_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
                         float* pts_dev, float* d2_dev, int32_t* count_dev);
+/* ---- edits and queries by point and box: the rest of what a holder of the tree can do (include/ikd-Tree/ikd_Tree.h:165-187).
+ * lii_map_delete_points <- ikdtree.Delete_Points(PointToDel)  (include/ikd-Tree/ikd_Tree.cpp:479-498, Delete_by_point :672-719,
+ *                       same_point :1269-1271).  Every listed point (float xyz every stride_bytes, as for lii_map_build) takes ONE live
+ *                       stored point out of the map: one that same_point accepts - per axis the float difference, its fabs compared in
+ *                       double against 1e-6.  The map can hold bit-equal twins (lii_map_add_points with downsample_on = 0 stores what it
+ *                       is given): a list that holds a point c times removes min(c, stored copies) of them, wherever in the list the
+ *                       copies stand; *n_deleted is the number actually removed.  The work follows the LIST, not the map: a listed point
+ *                       looks at the one to eight cells it can match in.
+ *                       Unspecified: among stored points that are not bit-equal but lie within 2e-6 of each other on every axis, which of
+ *                       them a listed point takes - and, when several listed points compete for them, how many go (the reference takes the
+ *                       first on its descent: its answer depends on the shape of its tree).  A listed point with a NaN or infinite
+ *                       coordinate matches nothing.  A listed point that is not in the map is not an error; n == 0 or an empty map: LII_OK,
+ *                       count 0.  LII_ERR_INVALID, nothing changed: a bad stride, NULL with n > 0, n < 0.  n is unbounded: the list goes
+ *                       through the handle's staging in chunks of at most 65 536 points, the chunks in order.
+ *                       Everything else is as lii_map_delete_boxes: the call ends a pre-armed launch and joins a map update in flight
+ *                       (never a map with parked inserts), drops the neighbour lists and cached planes when something went, works with a
+ *                       communicator attached (the maps are replicated: give every rank the same list) and under LII_TEST=host_solve.
+ *                       While lii_map_removed_set is in force the points it removes go into the history buffer (see there).
+ * lii_map_delete_points_dev  the list lies in device memory of the caller (lii_dev_alloc, a tensor's data_ptr): enqueued on the handle's
+ *                       stream, returns without waiting.  Nobody knows yet whether anything went, so the neighbour lists and planes of an
+ *                       earlier search are not used again (the rule of lii_local_map_segment(out == NULL)); lii_map_size behind it reads
+ *                       the result.
+ * lii_map_range       <- ikdtree.tree_range()  (ikd_Tree.cpp:90-118): the exact float minimum and maximum of the live points per axis -
+ *                       min xyz, max xyz; the same bits on every run (-0 counts as below +0).  An empty map: six zeros and LII_OK, as the
+ *                       reference's memset on a null root.  Waits for the stream.
+ * lii_map_box_search  <- ikdtree.Search_by_range  (ikd_Tree.cpp:970-998; the tree's own box query, the one Add_Points down-samples with)
+ *                       for n_boxes <= 4096 boxes of 6 floats (min xyz, max xyz): the live points with min <= p < max on every axis in
+ *                       at least one box - the rule of lii_map_delete_boxes -, a point that lies in several boxes once.  Packed xyz in
+ *                       unspecified order.  Capacity as for lii_map_download: *n is ALWAYS the full count; xyz_out == NULL returns the
+ *                       count only; capacity < *n is LII_ERR_CAPACITY and nothing is written.  Zero boxes or an empty map: *n = 0.
+ * lii_map_range and lii_map_box_search are OBSERVERS in the sense of lii_map_nearest: neighbour lists, IMU carry and publish order stay;
+ * they end a pre-armed launch and join a map update in flight first.
+ * NOT offered: Add_Point_Boxes (ikd_Tree.cpp:458-477, Add_by_range :721-767).  In the reference it un-deletes only those lazily deleted
+ * nodes that no rebuild has flattened away yet: its answer depends on the shape of the tree, and the device map squeezes deleted points
+ * out at once.  The library refuses rather than invent a rule; re-insert the points (lii_map_removed_acquire keeps them) with
+ * lii_map_add_points. */
+int lii_map_delete_points(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t* n_deleted /* may be NULL */);
+int lii_map_delete_points_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes);
+int lii_map_range(lii_handle h, float range6[6] /* min xyz, max xyz */);
+int lii_map_box_search(lii_handle h, const float* boxes, int32_t n_boxes, float* xyz_out, int32_t capacity, int32_t* n);
 
 /* ---------------------------------------------------------------- scan in / undistortion / down-sampling
  * lii_scan_upload: host AoS -> device float4 (x,y,z,t_ms).  For pcl::PointXYZINormal use stride 48,

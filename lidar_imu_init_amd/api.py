@@ -137,6 +137,10 @@ _DECLS = {
     "lii_map_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "lii_map_add_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_delete_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_delete_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_delete_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "lii_map_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lii_map_box_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_map_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_commit": (C.c_int, [C.c_void_p]),
@@ -428,6 +432,37 @@ class Registrar:
         self._check(self.L.lii_map_delete_boxes(self.h, _ptr(b) if len(b) else None, len(b), C.byref(n)))
         return n.value
 
+    def map_delete_points(self, xyz) -> int:
+        """ikdtree.Delete_Points: every row of xyz (n, >= 3) takes ONE live stored point that same_point accepts (1e-6 an axis) out of the
+        map - a list that holds a point c times removes min(c, stored copies); returns the number of points removed."""
+        q = np.asarray(xyz, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_delete_points(self.h, _ptr(q) if len(q) else None, len(q), q.strides[0] if len(q) else 12, C.byref(n)))
+        return n.value
+
+    def map_delete_points_dev(self, q_dev, n, stride_bytes=12):
+        """map_delete_points with the list in device memory the caller owns - a raw address or an object with __cuda_array_interface__
+        (a torch tensor): float xyz every stride_bytes.  Enqueued on the handle's stream; map_size() behind it reads the result."""
+        self._check(self.L.lii_map_delete_points_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes)))
+
+    def map_range(self):
+        """ikdtree.tree_range(): (6,) float32 - the exact min xyz, max xyz of the live points; zeros for an empty map."""
+        r = (C.c_float * 6)()
+        self._check(self.L.lii_map_range(self.h, r))
+        return np.array(r, np.float32)
+
+    def map_box_search(self, boxes6):
+        """ikdtree.Search_by_range for boxes6 (n, 6) = min xyz, max xyz: the live points with min <= p < max in at least one box, each
+        once, as (m, 3) float32 in no particular order.  Leaves the handle's neighbour lists and everything else of a registration alone."""
+        b = np.ascontiguousarray(boxes6, np.float32).reshape(-1, 6)
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_box_search(self.h, _ptr(b) if len(b) else None, len(b), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        self._check(self.L.lii_map_box_search(self.h, _ptr(b) if len(b) else None, len(b), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
     # ---- the moving local map (lasermap_fov_segment + the box delete upstream never made)
     @staticmethod
     def _local_map_info(info) -> dict:
@@ -533,6 +568,12 @@ class Registrar:
         self._check(self.L.lii_dev_alloc(self.h, max(int(nbytes), 16), C.byref(p)))
         self._dev_bufs.append(p)
         return int(p.value)
+
+    def dev_upload(self, dev_ptr, a):
+        """Copies the bytes of array `a` to device memory at `dev_ptr` (dev_alloc); synchronous (lii_dev_upload)."""
+        a = np.ascontiguousarray(a)
+        if a.nbytes:
+            self._check(self.L.lii_dev_upload(self.h, C.c_void_p(_dev_address(dev_ptr)), _ptr(a), a.nbytes))
 
     def map_nearest_dev(self, q_dev, n, k, max_dist, pts_dev, d2_dev, count_dev, stride_bytes=12):
         """map_nearest with queries and results in device memory the caller owns - raw addresses, or objects with

@@ -408,8 +408,9 @@ static int create_resources(lii_handle h) {
   HIPCHK(h, hipMemset(h->d_cell_cap, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
   HIPCHK(h, hipMemset(h->d_tp, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
   HIPCHK(h, h->d_counter.alloc(4));
-  HIPCHK(h, h->d_tomb.alloc(size_t(h->pts_cap)));
-  HIPCHK(h, hipMemset(h->d_tomb, 0, size_t(h->pts_cap)));
+  // (whole 32-bit words: k_point_tomb claims a tombstone byte with an atomic on the aligned word that holds it)
+  HIPCHK(h, h->d_tomb.alloc((size_t(h->pts_cap) + 3) & ~size_t(3)));
+  HIPCHK(h, hipMemset(h->d_tomb, 0, h->d_tomb.size()));
   HIPCHK(h, h->d_ins.alloc(M));
   HIPCHK(h, h->d_batch.alloc(M));
   HIPCHK(h, h->d_dropped.alloc(NM));

@@ -1,6 +1,7 @@
 // libliinit_hip — the device-resident local map (host side): index (re)build, in-place updates, the lii_map_* entry points and
 // lii_map_incremental.  Kernels: lii_map.hip, lii_mapindex.hip (index), lii_sort.hip.  Reference: include/ikd-Tree/ikd_Tree.cpp
-// (Build :336-347, Add_Points :381-456, Delete_Point_Boxes :500-516), src/laserMapping.cpp:516-559 (map_incremental).
+// (Build :336-347, Add_Points :381-456, Delete_Points :479-498, Delete_Point_Boxes :500-516, tree_range :90-118, Search_by_range :970-998),
+// src/laserMapping.cpp:516-559 (map_incremental).
 #include "lii_context.h"
 
 using namespace lii_impl;
@@ -602,6 +603,136 @@ int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int3
   if (rc != LII_OK) return rc;
   if (n_deleted) *n_deleted = n_old - h->n_map;
   if (h->n_map != n_old) h->have_search = false;
+  return LII_OK;
+}
+// ------------------------------------------------------------------------------------------------ edits and queries by point and box
+namespace {
+// What lii_map_delete_points and its _dev form share: the claims of one list in device memory (k_point_tomb), the squeeze of the cells that
+// lost a point - at most eight per listed point, never more than the map has - and the launch that re-arms the work list, on the handle's
+// stream.  The caller has read the map's counters and found a map.  publish: the last launch hands the counters to pinned memory as an
+// in-place update does, and whoever uses the map next picks them up there (commit_map / map_counters) - nothing is waited for here.
+int delete_points_enqueue(lii_handle h, const void* list_dev, int n, int stride_bytes, bool publish) {
+  hipStream_t s = h->stream;
+  const long long ne = (long long)std::max(h->n_blocks, 0) * 512;
+  const long long bound = std::min<long long>(8ll * n, ne);
+  if (bound <= 0) return LII_OK;
+  if ((unsigned long long)bound > (unsigned long long)h->work_cap) {  // (nothing is in flight that uses the list: the counters have just been read)
+    h->work_cap = 0;
+    HIPCHK(h, h->d_work.grow(size_t(bound) + 4096));
+    h->work_cap = (unsigned int)h->d_work.size();
+  }
+  h->map_dirty = true;
+  launch_point_tomb(grid_view(h), list_dev, n, stride_bytes, h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
+  const lii::WinKeep wk = win_keep_view(h);
+  if (!wk.win) h->win_valid = false;
+  const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
+  launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, int(bound), wk, s, &rs);
+  if (publish) h->map_seq = h->map_seq == 0x7FFFFFFF ? 1 : h->map_seq + 1;
+  launch_ins_write(h->d_pts, h->d_ins_e, 0, nullptr, nullptr, nullptr, 0, nullptr, h->d_cells, h->d_cell_cap, h->d_pts, h->d_mapctr, h->d_dropped, h->drop_cap,
+                   s, publish ? h->h_mapflag.get() : nullptr, publish ? kMapCtrWords + 8 : 0, publish ? kMapFlagSeqAt : 0, publish ? h->map_seq : 0,
+                   wk);  // (re-arms the work list)
+  HIPCHK(h, hipGetLastError());
+  if (publish) {
+    HIPCHK(h, hipEventRecord(h->ev_mapflag, s));
+    h->map_flag_pending = true;
+  }
+  return LII_OK;
+}
+}  // namespace
+int lii_map_delete_points(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t* n_deleted) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || (!xyz && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4)
+    return fail(h, LII_ERR_INVALID, "lii_map_delete_points: bad arguments (points, n >= 0, stride a multiple of 4 and >= 12)");
+  if (n_deleted) *n_deleted = 0;
+  int rc = map_counters(h);  // (joins a map update in flight: never a map with parked inserts)
+  if (rc != LII_OK) return rc;
+  const int n_old = h->n_map;
+  if (n == 0 || n_old == 0) return LII_OK;
+  // the list goes through the handle's staging a chunk at a time, the chunks in order
+  const size_t chunk = std::min<size_t>(std::min<size_t>(lii_context::MapQuery::kQueriesMax, h->d_batch.size()), h->h_stage.size());
+  if (chunk == 0) return fail(h, LII_ERR_CAPACITY, "lii_map_delete_points: the handle has no staging");
+  const char* src = static_cast<const char*>(xyz);
+  for (size_t at = 0; at < size_t(n); at += chunk) {
+    const int m = int(std::min(chunk, size_t(n) - at));
+    rc = upload_xyz(h, src + at * size_t(stride_bytes), m, stride_bytes, h->d_batch);
+    if (rc != LII_OK) return rc;
+    rc = delete_points_enqueue(h, h->d_batch, m, int(sizeof(float4)), false);
+    if (rc != LII_OK) return rc;
+  }
+  rc = map_counters(h);
+  if (rc != LII_OK) return rc;
+  if (n_deleted) *n_deleted = n_old - h->n_map;
+  if (h->n_map != n_old) h->have_search = false;
+  return LII_OK;
+}
+int lii_map_delete_points_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || (!xyz_dev && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4)
+    return fail(h, LII_ERR_INVALID, "lii_map_delete_points_dev: bad arguments (points, n >= 0, stride a multiple of 4 and >= 12)");
+  int rc = map_counters(h);
+  if (rc != LII_OK) return rc;
+  if (n == 0 || h->n_map == 0) return LII_OK;
+  h->have_search = false;  // (whether anything went is not known here: lists and planes of an earlier search are not used again)
+  return delete_points_enqueue(h, xyz_dev, n, stride_bytes, true);
+}
+int lii_map_range(lii_handle h, float range6[6]) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h) return LII_ERR_INVALID;
+  if (!range6) return fail(h, LII_ERR_INVALID, "lii_map_range: bad arguments");
+  for (int a = 0; a < 6; a++) range6[a] = 0.f;
+  int rc = map_counters(h);
+  if (rc != LII_OK) return rc;
+  hipStream_t s = h->stream;
+  if (h->n_map > 0) {
+    unsigned int* partial = h->d_cs_a;  // (per-cell scratch of gathers and rebuilds, free between calls)
+    float* d_range = reinterpret_cast<float*>(partial + 256 * 6);
+    launch_map_range(h->d_pts, h->d_cells, h->n_blocks * 512, partial, d_range, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->h_small + 3100, d_range, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (h->n_map > 0) std::memcpy(range6, h->h_small + 3100, 6 * sizeof(float));
+  return LII_OK;
+}
+int lii_map_box_search(lii_handle h, const float* boxes, int32_t n_boxes, float* xyz_out, int32_t capacity, int32_t* n) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h) return LII_ERR_INVALID;
+  if (!n || (!boxes && n_boxes > 0) || n_boxes < 0 || n_boxes > 4096) return fail(h, LII_ERR_INVALID, "lii_map_box_search: bad arguments (<= 4096 boxes, n)");
+  *n = 0;
+  int rc = map_counters(h);
+  if (rc != LII_OK) return rc;
+  if (n_boxes == 0 || h->n_map == 0) return LII_OK;
+  hipStream_t s = h->stream;
+  float* d_boxes = reinterpret_cast<float*>(h->d_keys_b.get());  // scratch of the index build (max_map_points * 8 bytes), free between calls
+  if (size_t(n_boxes) * 24 > size_t(h->cfg.max_map_points) * 8)
+    return fail(h, LII_ERR_INVALID, "lii_map_box_search: more boxes than the handle's scratch holds (max_map_points / 3)");
+  std::memcpy(h->h_small + 4096, boxes, sizeof(float) * 6 * size_t(n_boxes));
+  HIPCHK(h, hipMemcpyAsync(d_boxes, h->h_small + 4096, sizeof(float) * 6 * size_t(n_boxes), hipMemcpyHostToDevice, s));
+  unsigned long long* d_hits = reinterpret_cast<unsigned long long*>(h->d_cs_a.get());
+  HIPCHK(h, hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), s));
+  // (the hits land in the staging of gathers and rebuilds: it holds max_map_points, and a box holds no more than the map)
+  const unsigned int room = xyz_out ? (unsigned int)std::min<size_t>(h->d_map_unsorted.size(), 0x7FFFFFFFu) : 0u;
+  launch_box_gather(h->d_pts, h->d_cells, h->d_block_key, std::max(h->n_blocks, 0), h->cell_size, d_boxes, n_boxes, h->d_map_unsorted, room, d_hits, s);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(h->h_small + 3110, d_hits, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  unsigned long long hits = 0;
+  std::memcpy(&hits, h->h_small + 3110, sizeof(hits));
+  if (hits > (unsigned long long)0x7FFFFFFF) return fail(h, LII_ERR_HIP, "lii_map_box_search: counter out of range");
+  const int cnt = int(hits);
+  *n = cnt;
+  if (!xyz_out) return LII_OK;
+  if (capacity < cnt) return fail(h, LII_ERR_CAPACITY, "lii_map_box_search: capacity too small");
+  if (cnt == 0) return LII_OK;
+  if ((unsigned int)cnt > room || size_t(cnt) > h->h_stage.size()) return fail(h, LII_ERR_CAPACITY, "lii_map_box_search: more hits than the handle's staging holds");
+  HIPCHK(h, hipEventSynchronize(h->ev_stage));  // an asynchronous scan upload may still be reading the staging buffer
+  HIPCHK(h, hipMemcpyAsync(h->h_stage, h->d_map_unsorted, sizeof(float4) * size_t(cnt), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  for (int i = 0; i < cnt; i++) {
+    xyz_out[3 * size_t(i)] = h->h_stage[i].x;
+    xyz_out[3 * size_t(i) + 1] = h->h_stage[i].y;
+    xyz_out[3 * size_t(i) + 2] = h->h_stage[i].z;
+  }
   return LII_OK;
 }
 int lii_local_map_set(lii_handle h, const lii_local_map_opts* opts) {

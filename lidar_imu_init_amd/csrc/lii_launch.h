@@ -288,6 +288,14 @@ void launch_cell_counts(const uint2* cells, int n_entries, unsigned int* cnt, hi
 void launch_gather_live(const float4* pts, const uint2* cells, const unsigned int* cntsum, int n_entries, float4* dst, int dst_cap, hipStream_t s);
 void launch_box_tomb_cells(const float4* pts, const uint2* cells, int n_entries, const float* boxes, int n_boxes, unsigned char* tomb, unsigned int* tp,
                            unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s);
+// edits and queries by point and box (lii_map.hip: k_point_tomb, k_map_range -> k_map_range_finish, k_box_gather).  list_dev: float xyz every
+// stride_bytes in device memory; tomb: 4-byte aligned and padded to a multiple of 4 bytes (the claim is a 32-bit atomic).  partial: 256 x 6
+// words of scratch; range6 / n_hits: device memory.  The last two launch a fixed grid.
+void launch_point_tomb(const GridView& g, const void* list_dev, int n, int stride_bytes, unsigned char* tomb, unsigned int* tp, unsigned int* work, int* ctr,
+                       unsigned int work_cap, hipStream_t s);
+void launch_map_range(const float4* pts, const uint2* cells, int n_entries, unsigned int* partial, float* range6, hipStream_t s);
+void launch_box_gather(const float4* pts, const uint2* cells, const unsigned long long* key_of_id, int n_blocks, float cs, const float* boxes, int n_boxes,
+                       float4* out, unsigned int capacity, unsigned long long* n_hits, hipStream_t s);
 // the moving local-map cube (lii_map.hip: k_local_map_tomb -> k_cell_apply_listed -> k_local_map_finish; the arithmetic: lii_fov.h).  `in` / `out`:
 // the two copies of the state in device memory; pos_dev != nullptr: state.pos_end is read there, else `pos` travels by value; `host`: the
 // pinned copy of the state the last launch leaves.  All three launches have a fixed size.

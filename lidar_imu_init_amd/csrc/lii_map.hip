@@ -14,6 +14,9 @@
 //   k_box_tomb_cells      KD_TREE::Delete_Point_Boxes                                  include/ikd-Tree/ikd_Tree.cpp:500-516
 //   k_cell_apply_collect / k_cell_apply_listed_collect   the squeeze of a BOX delete that also keeps what it drops (lii_map_removed_set):
 //                         KD_TREE::acquire_removed_points, include/ikd-Tree/ikd_Tree.cpp:522-534, :1242-1249 - one reservation per wavefront
+//   k_point_tomb          KD_TREE::Delete_Points, sized by the list                    include/ikd-Tree/ikd_Tree.cpp:479-498, :672-719
+//   k_map_range -> k_map_range_finish   KD_TREE::tree_range                            include/ikd-Tree/ikd_Tree.cpp:90-118
+//   k_box_gather          KD_TREE::Search_by_range for a list of boxes                 include/ikd-Tree/ikd_Tree.cpp:970-998
 //   k_cell_caps / k_spread / k_cell_counts / k_gather_live   (re)build: compact cell-sorted array <-> slack layout
 // Set equivalence with the tree is tested against the oracle's restated tree and against the unmodified reference tree
 // (tests/test_gpu_map.py).  Ties between equal squared distances to the voxel centre are broken by map order here and by
@@ -1076,7 +1079,191 @@ __global__ __launch_bounds__(64) void k_local_map_finish(LocalMapState* __restri
   *host = s;
 }
 
+// ------------------------------------------------------------------------------------------------ edits and queries by point and box
+// KD_TREE::Delete_Points (include/ikd-Tree/ikd_Tree.cpp:479-498, Delete_by_point :672-719, same_point :1269-1271), sized by the LIST: one
+// lane per listed point looks at the cells [q - eps, q + eps] overlaps - one nearly always, eight at most; a block that is not in the table
+// and a cell that holds nothing are simply empty - for a live point that same_point accepts, and CLAIMS it: tombstones are bytes, the claim
+// is an atomicOr of the byte's mask on the aligned 32-bit word that holds it, and the lane that finds the byte clear in the word that comes
+// back owns the point.  A lane that loses goes on looking - in the cell, then in the remaining cells -, so a list that holds a point c times
+// takes min(c, stored copies) of them, whichever lanes, wavefronts or workgroups the copies land in.  No other kernel writes tombstones
+// while this one runs (the squeeze behind it clears them with plain stores, as ever).
+// eps is 2e-6 here, twice same_point's: the interval is formed in float, and a stored point that passes the test lies inside it however
+// the sum rounds (cell_of is monotone); the cells are a superset, the rule is d_same_point alone.
+__global__ __launch_bounds__(256) void k_point_tomb(GridView g, const unsigned char* __restrict__ list, int n, int stride_bytes, unsigned char* tomb,
+                                                    unsigned int* __restrict__ tp, unsigned int* __restrict__ work, int* __restrict__ ctr,
+                                                    unsigned int work_cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* f = reinterpret_cast<const float*>(list + (size_t)i * (size_t)stride_bytes);
+  const float q[3] = {f[0], f[1], f[2]};
+  // (NaN and infinity match nothing - and have no cell: inf - inf is NaN in same_point too)
+  if (!(fabsf(q[0]) <= 3.4028234e38f && fabsf(q[1]) <= 3.4028234e38f && fabsf(q[2]) <= 3.4028234e38f)) return;
+  int c0[3], c1[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    // (a coordinate outside the addressable grid clamps to its rim: no map point lies beyond it)
+    const float lo = fminf(fmaxf((q[a] - 2e-6f) * g.inv_cs, -(float)(kCellBias - 8)), (float)(kCellBias - 8));
+    const float hi = fminf(fmaxf((q[a] + 2e-6f) * g.inv_cs, -(float)(kCellBias - 8)), (float)(kCellBias - 8));
+    c0[a] = (int)floorf(lo);
+    c1[a] = min((int)floorf(hi), c0[a] + 1);  // (two cells an axis: a cell is far wider than 4e-6)
+  }
+  for (int cz = c0[2]; cz <= c1[2]; cz++)
+    for (int cy = c0[1]; cy <= c1[1]; cy++)
+      for (int cx = c0[0]; cx <= c1[0]; cx++) {
+        long long e;
+        const uint2 r = cell_range(g, cx, cy, cz, e);
+        for (unsigned int j = r.x; j < r.y; j++) {
+          const float4 p = g.pts[j];
+          if (!d_same_point(q[0], q[1], q[2], p.x, p.y, p.z)) continue;
+          const unsigned int sh = 8u * (j & 3u);
+          const unsigned int old = atomicOr(reinterpret_cast<unsigned int*>(tomb + (j & ~3u)), 1u << sh);
+          if ((old >> sh) & 0xFFu) continue;  // somebody else's: look on
+          touch_cell(tp, work, ctr, work_cap, (unsigned int)e);
+          return;
+        }
+      }
+}
+
+// KD_TREE::tree_range (ikd_Tree.cpp:90-118): the exact float minimum and maximum of the live points per axis.  A launch of fixed size
+// strides over the cell entries; every lane folds its points, the wavefront folds by shuffle, the workgroup through shared memory, ONE
+// partial per workgroup; k_map_range_finish - one workgroup - folds the partials.  No float atomics, and the fold is over a TOTAL order of
+// the float bits (-0 below +0): the six numbers are the same bits on every run, whatever order the points lie in.
+constexpr int kRangeGrid = 256;
+__device__ __forceinline__ unsigned int range_key(float v) {
+  const unsigned int b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float range_unkey(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+// k[0..2]: minima, k[3..5]: maxima (keys); every lane of the workgroup (256) calls it; the result is in thread 0
+__device__ __forceinline__ void range_fold_block(unsigned int (&k)[6], unsigned int (*s_part)[6]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      k[a] = min(k[a], (unsigned int)__shfl_xor((int)k[a], off));
+      k[3 + a] = max(k[3 + a], (unsigned int)__shfl_xor((int)k[3 + a], off));
+    }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int a = 0; a < 6; a++) s_part[w][a] = k[a];
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int ww = 0; ww < 4; ww++)
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        k[a] = min(k[a], s_part[ww][a]);
+        k[3 + a] = max(k[3 + a], s_part[ww][3 + a]);
+      }
+}
+__global__ __launch_bounds__(256) void k_map_range(const float4* __restrict__ pts, const uint2* __restrict__ cells, int n_entries,
+                                                   unsigned int* __restrict__ partial /* kRangeGrid x 6 keys */) {
+  __shared__ unsigned int s_part[4][6];
+  unsigned int k[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+  const int total = (int)(gridDim.x * blockDim.x);
+  for (int e = (int)(blockIdx.x * blockDim.x + threadIdx.x); e < n_entries; e += total) {
+    const uint2 c = cells[e];
+    for (unsigned int j = c.x; j < c.y; j++) {
+      const float4 p = pts[j];
+      const unsigned int kx = range_key(p.x), ky = range_key(p.y), kz = range_key(p.z);
+      k[0] = min(k[0], kx); k[1] = min(k[1], ky); k[2] = min(k[2], kz);
+      k[3] = max(k[3], kx); k[4] = max(k[4], ky); k[5] = max(k[5], kz);
+    }
+  }
+  range_fold_block(k, s_part);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int a = 0; a < 6; a++) partial[blockIdx.x * 6 + a] = k[a];
+}
+__global__ __launch_bounds__(256) void k_map_range_finish(const unsigned int* __restrict__ partial, int n_partial, float* __restrict__ range6) {
+  __shared__ unsigned int s_part[4][6];
+  unsigned int k[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+  for (int b = (int)threadIdx.x; b < n_partial; b += (int)blockDim.x)
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      k[a] = min(k[a], partial[b * 6 + a]);
+      k[3 + a] = max(k[3 + a], partial[b * 6 + 3 + a]);
+    }
+  range_fold_block(k, s_part);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int a = 0; a < 6; a++) range6[a] = k[0] <= k[3] ? range_unkey(k[a]) : 0.f;  // (no live point: zeros, the reference's memset on a null root)
+}
+
+// KD_TREE::Search_by_range (ikd_Tree.cpp:970-998) for a list of boxes: the live points with min <= p < max on every axis in at least one
+// box, each once.  A launch of fixed size; one wavefront per 8 x 8 x 8 block, striding over the block ids as k_local_map_tomb does: the
+// block's (slightly wide) extent against the boxes, the boxes dealt out to the lanes - a block that touches none is not read.  Else the 64
+// lanes take 8 cells each: they count their hits, the wavefront reserves its range of the output with ONE atomic (wave_reserve), and the
+// lanes walk their cells again and write.  A hit past `capacity` is counted and not stored; the order is whatever the atomics make it.
+__device__ __forceinline__ bool in_any_box(const float4 p, const float* __restrict__ boxes, int n_boxes) {
+  bool in = false;
+  for (int b = 0; b < n_boxes; b++) {
+    const float* q = boxes + 6 * b;
+    in = in || (q[0] <= p.x && q[3] > p.x && q[1] <= p.y && q[4] > p.y && q[2] <= p.z && q[5] > p.z);
+  }
+  return in;
+}
+__global__ __launch_bounds__(256) void k_box_gather(const float4* __restrict__ pts, const uint2* __restrict__ cells,
+                                                    const unsigned long long* __restrict__ key_of_id, int n_blocks, float cs,
+                                                    const float* __restrict__ boxes, int n_boxes, float4* __restrict__ out, unsigned int capacity,
+                                                    unsigned long long* __restrict__ n_hits) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), n_waves = (int)((gridDim.x * blockDim.x) >> 6);
+  const int bb = kCellBias >> kCoarseShift;
+  for (int bid = wave; bid < n_blocks; bid += n_waves) {  // (uniform per wavefront)
+    unsigned int kx, ky, kz;
+    unpack_block(key_of_id[bid], kx, ky, kz);
+    const int c0[3] = {((int)kx - bb) * 8, ((int)ky - bb) * 8, ((int)kz - bb) * 8};
+    float lo[3], hi[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const float l = (float)c0[i] * cs, h = (float)(c0[i] + 8) * cs;
+      const float m = 1e-5f * (fabsf(l) + fabsf(h)) + 1e-3f * cs;
+      lo[i] = l - m; hi[i] = h + m;
+    }
+    bool touches = false;
+    for (int b = lane; b < n_boxes; b += 64) {
+      const float* q = boxes + 6 * b;
+      bool dis = false;
+#pragma unroll
+      for (int i = 0; i < 3; i++) dis = dis || hi[i] < q[i] || lo[i] >= q[3 + i];
+      touches = touches || !dis;
+    }
+    if (!__any(touches)) continue;  // (uniform per wavefront) nothing of this block is read
+    unsigned int cnt = 0;
+    for (int u = 0; u < 8; u++) {
+      const uint2 c = cells[(unsigned int)bid * kBlockCells + (unsigned int)(lane * 8 + u)];
+      for (unsigned int j = c.x; j < c.y; j++) cnt += in_any_box(pts[j], boxes, n_boxes) ? 1u : 0u;
+    }
+    unsigned long long at = wave_reserve(n_hits, cnt);  // (all 64 lanes are here)
+    for (int u = 0; u < 8 && cnt != 0u; u++) {
+      const uint2 c = cells[(unsigned int)bid * kBlockCells + (unsigned int)(lane * 8 + u)];
+      for (unsigned int j = c.x; j < c.y; j++) {
+        const float4 p = pts[j];
+        if (in_any_box(p, boxes, n_boxes)) {
+          if (at < (unsigned long long)capacity) out[at] = p;
+          at++;
+        }
+      }
+    }
+  }
+}
+
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }
+void launch_point_tomb(const GridView& g, const void* list_dev, int n, int stride_bytes, unsigned char* tomb, unsigned int* tp, unsigned int* work, int* ctr,
+                       unsigned int work_cap, hipStream_t s) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_point_tomb, dim3(nblk(n, 256)), dim3(256), 0, s, g, static_cast<const unsigned char*>(list_dev), n, stride_bytes, tomb, tp, work, ctr,
+                       work_cap);
+}
+void launch_map_range(const float4* pts, const uint2* cells, int n_entries, unsigned int* partial, float* range6, hipStream_t s) {
+  hipLaunchKernelGGL(k_map_range, dim3(kRangeGrid), dim3(256), 0, s, pts, cells, n_entries, partial);
+  hipLaunchKernelGGL(k_map_range_finish, dim3(1), dim3(256), 0, s, partial, kRangeGrid, range6);
+}
+void launch_box_gather(const float4* pts, const uint2* cells, const unsigned long long* key_of_id, int n_blocks, float cs, const float* boxes, int n_boxes,
+                       float4* out, unsigned int capacity, unsigned long long* n_hits, hipStream_t s) {
+  hipLaunchKernelGGL(k_box_gather, dim3(kLocalMapGrid), dim3(256), 0, s, pts, cells, key_of_id, n_blocks, cs, boxes, n_boxes, out, capacity, n_hits);
+}
 void launch_ins_cells(const float4* list, const unsigned int* flags, int n, const int* n_dev, const float4* list2, int n2, const int* n2_dev, unsigned int* ins_e2,
                       BlockEntry* blocks, unsigned int mask, float inv_cs, unsigned int tables_cap, unsigned int* ins_e, unsigned int* tp,
                       unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s) {
