@@ -308,8 +308,9 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     static int cnt = 0;
     if (++cnt % 100 == 0) {
       auto row = [&](const long long* t) {
-        fprintf(stderr, " loads+sums %lld | A %lld | elimination %lld (its own %lld) | solution %lld | state %lld (schedule %lld, rotations %lld, stores %lld) | cov %lld ;",
-                t[1] - t[0], t[2] - t[1], t[4] - t[3], t[5] - t[3], t[8] - t[4], t[9] - t[8], t[6] - t[8], t[7] - t[6], t[9] - t[7], t[10] - t[9]);
+        fprintf(stderr, " loads+sums %lld | A %lld | elimination %lld (its own %lld) | solution %lld | state %lld (rotations %lld, pose stores %lld) | barrier + cov %lld | all %lld | clock %.2f GHz ;",
+                t[1] - t[0], t[2] - t[1], t[4] - t[3], t[5] - t[3], t[8] - t[4], t[9] - t[8], t[7] - t[8], t[9] - t[7], t[10] - t[9], t[10] - t[0],
+                t[5] > t[3] ? (double)(t[12] - t[11]) / (10.0 * (double)(t[5] - t[3])) : 0.0);
       };
       fprintf(stderr, "[solve trace, 10 ns ticks] stopping pass:");
       row(hr->ts);

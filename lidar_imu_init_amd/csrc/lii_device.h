@@ -499,7 +499,7 @@ struct IekfResult {
   int search_log[16];
   int parked_search;  // ... and that iteration searches (1) or not (0): the host puts a k-NN launch in front of it only then
   int unfinished;     // queries the scan's search passes left unfinished (max over its two most recent search launches; k_reduce_solve)
-  long long ts[16];  // LII_SOLVE_TRACE builds: wall_clock64 stamps of the solve phases (stopping iteration)
+  long long ts[16];  // LII_SOLVE_TRACE builds: wall_clock64 stamps of the solve phases (stopping iteration); [11], [12]: s_memtime at the start and end of the elimination
   long long ts0[16]; // ... of iteration 0
 };
 

@@ -263,12 +263,16 @@ __device__ __forceinline__ double boxplus_rot_entry(const double* v, const doubl
 //   phase A2 A = I + P11 G (144 lanes)
 //   phase B  the 12-step register-resident Gauss-Jordan (first and second wavefront - inherently serial) | the two rotation
 //            logarithms, u = H^T z - G vec (third)
-//   phase C  solution (24 lanes), schedule, boxplus, and on the stopping iteration K H (288 entries) and the covariance
-//            (576 entries, 12 MACs each) over all 256 lanes.
+//   phase C  solution (24 lanes); boxplus of the two rotations (first wavefront, alone) | schedule, vector blocks, solution and control
+//            words, and on the stopping iteration K H (288 entries) and the covariance rows (576 entries, 12 MACs each) on the three
+//            others; barrier; on the stopping iteration the symmetric part and the result block over all 256 lanes.
 #ifdef LII_SOLVE_TRACE
 #define LII_TS(k) do { if (threadIdx.x == 0) s_ts[k] = wall_clock64(); } while (0)
+// (the shader clock next to the 100 MHz one: over the elimination their ratio is the clock the solver's compute unit runs at in the launch)
+#define LII_TS_CLK(k) do { if (threadIdx.x == 0) s_ts[k] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define LII_TS(k)
+#define LII_TS_CLK(k)
 #endif
 constexpr int kSolveThreads = 256;
 // The iteration that ends the loop tells the host so through the mapped result block: every lane's stores to `res` have been
@@ -307,11 +311,15 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   __shared__ double s_ne[96], s_st[36], s_prop[36];
   __shared__ int s_int[12];
   __shared__ int s_ok;
+  __shared__ int s_log[16];  // IekfCtrl::search_log as the passes before left it (the stopping pass copies it into the result block)
+  __shared__ int s_sched;    // the schedule's verdict for the wavefront that does not evaluate it: bit 0 = this pass stops the loop (do_cov), bit 1 = it parks it
+  __shared__ double s_rot[18];  // the updated rotations, for the result block of the stopping pass
   __shared__ double s_rx[2][3][9];  // boxplus: K, c1 K and Exp of the two rotations on their way between lanes
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   {
     const int* ci = &c->max_it;  // max_it, imu_en, it, search_next, stop, rematch_num, converged, searches, effect_num, singular, seq, plan_mask
     if (tid < 12) s_int[tid] = ci[tid];
+    if (tid >= 64 && tid < 80) s_log[tid - 64] = c->search_log[tid - 64];  // (entries below `it`: written by the passes before, read behind the last row otherwise)
     if (tid >= 160 && tid < 196) { s_st[tid - 160] = c->st[tid - 160]; s_prop[tid - 160] = c->prop[tid - 160]; }
     const double* cov = c->st + 36;
     for (int e = tid; e < N * N; e += kSolveThreads) s_cov[e] = cov[e];
@@ -357,6 +365,7 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   __syncthreads();
   LII_TS(2);
   LII_TS(3);
+  LII_TS_CLK(11);
   // ---- phase B: K_1[:, :12]^T = A^-1 P[:12, :]  (A = I + P11 G;  K_1[:, :12] = P[:, :12] (I + G P11)^-1 and G, P symmetric).
   // Gauss-Jordan on [A | P[:12, :]]: every 16-lane row of the first two wavefronts holds the columns of A in its lanes 0..11 and four of
   // the 24 columns of P[:12, :] in lanes 12..15 (gj12_dpp: wavefront 0 columns 0..15, wavefront 1 columns 16..23 in its rows 0 - 1);
@@ -377,6 +386,7 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
       for (int r = 0; r < H; r++) K1c[j * LDH + r] = col[r];
     }
     LII_TS(5);  // (the elimination itself; stamp 4 includes the wait for the third wavefront at the barrier)
+    LII_TS_CLK(12);
   } else if (wave == 2) {
     if (lane < 2) {
       const int o = lane * 12, so = lane * 6;  // rot_end / offset_R_L_I
@@ -425,41 +435,49 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
   }
   __syncthreads();
   LII_TS(8);
-  // schedule (uniform: every lane evaluates it from LDS)
-  const double rn = sqrt(sol[0] * sol[0] + sol[1] * sol[1] + sol[2] * sol[2]);
-  const double tn = sqrt(sol[3] * sol[3] + sol[4] * sol[4] + sol[5] * sol[5]);
-  const int converged = (rn * 57.3 < 0.01) && (tn * 100 < 0.015);
-  int rematch = rematch0, search = 0;
-  if (converged || ((rematch == 0) && (it == (max_it - 2)))) { search = 1; rematch++; }
-  const int do_cov = (rematch >= 2 || (it == max_it - 1));
-  // the next pass searches but the host did not enqueue a k-NN launch for it: park the loop and say so (IekfCtrl::plan_mask)
-  // ... or the host did not enqueue the next pass at all (bit 16 + k: the launches of pass k are there)
-  const unsigned int pm = (unsigned int)s_int[11];
-  const bool pass_there = it + 1 >= 16 || ((pm >> (16 + it + 1)) & 1u), knn_there = it + 1 >= 16 || ((pm >> (it + 1)) & 1u);
-  const int parked = !do_cov && (!pass_there || (search && !knn_there));
-  // state += solution : the two rotations on 2 x 9 lanes of the first wavefront (an entry each), the vector blocks on 18; on the stopping
-  // iteration the other three wavefronts start on K H = K_1[:, :12] G (needed for the covariance only) right away
-  LII_TS(6);
+  // state += solution.  The launch ends when its LAST wavefront has ended, and on every pass but the stopping one that is the wavefront with
+  // the two rotations (a square root, a quotient, sin, cos and two exchanges through LDS, one behind the other).  The first wavefront
+  // therefore takes the rotations on 2 x 9 lanes (an entry each) and NOTHING ELSE: it goes into boxplus straight from the barrier, stores
+  // its part of the pose and is done.  The three other wavefronts evaluate the schedule (the same expressions on the same numbers, so
+  // every lane arrives at the same verdict, as before), leave it in s_sched for the first, and share out what does not feed the rotations:
+  // the vector blocks (second wavefront), the solution (third), the loop's control words and the search log (fourth) - then, on the
+  // stopping pass, their rows of K H and of the covariance.  One barrier ends every pass; the first wavefront is the last to arrive at
+  // it on all but the stopping pass.  (Before: schedule, vector blocks, solution and rotations one behind the other on the first
+  // wavefront - 0.3 + 0.2 us in front of the rotations of every pass: profiles/solve_phases.md.)
   if (wave == 0) {
-    if (lane >= 8 && lane < 26) {
-      const int q = lane - 8;  // 0..17 : six 3-vectors
-      const int blk = q / 3, i = q % 3;
-      const int sto = blk == 0 ? 9 : (blk == 1 ? 21 : (blk == 2 ? 24 : (blk == 3 ? 27 : (blk == 4 ? 30 : 33))));
-      const int soo = blk == 0 ? 3 : (blk == 1 ? 9 : (blk == 2 ? 12 : (blk == 3 ? 15 : (blk == 4 ? 18 : 21))));
-      const double v = s_st[sto + i] + sol[soo + i];
-      c->st[sto + i] = v;
-      if (do_cov) res_store(&res->st[sto + i], v);
-    } else if (lane >= 32 && lane < 32 + N) {
-      c->solution[lane - 32] = sol[lane - 32];
-    }
     if (lane < 32 && (lane & 15) < 9) {  // lanes 0..8: rot_end, 16..24: offset_R_L_I - one entry each (boxplus_rot_entry)
       const int rho = lane >> 4, e = lane & 15, o = 12 * rho;
       const double v = boxplus_rot_entry(sol + 6 * rho, s_st + o, s_rx[rho][0], s_rx[rho][1], s_rx[rho][2], e);
       LII_TS(7);
       c->st[o + e] = v;
-      if (do_cov) res_store(&res->st[o + e], v);
+      s_rot[9 * rho + e] = v;  // (for the result block of the stopping pass: behind the barrier)
     }
-    if (lane == 63) {
+  } else {
+    // schedule (uniform over the three wavefronts: every lane evaluates it from LDS)
+    const double rn = sqrt(sol[0] * sol[0] + sol[1] * sol[1] + sol[2] * sol[2]);
+    const double tn = sqrt(sol[3] * sol[3] + sol[4] * sol[4] + sol[5] * sol[5]);
+    const int converged = (rn * 57.3 < 0.01) && (tn * 100 < 0.015);
+    int rematch = rematch0, search = 0;
+    if (converged || ((rematch == 0) && (it == (max_it - 2)))) { search = 1; rematch++; }
+    const int do_cov = (rematch >= 2 || (it == max_it - 1));
+    // the next pass searches but the host did not enqueue a k-NN launch for it: park the loop and say so (IekfCtrl::plan_mask)
+    // ... or the host did not enqueue the next pass at all (bit 16 + k: the launches of pass k are there)
+    const unsigned int pm = (unsigned int)s_int[11];
+    const bool pass_there = it + 1 >= 16 || ((pm >> (16 + it + 1)) & 1u), knn_there = it + 1 >= 16 || ((pm >> (it + 1)) & 1u);
+    const int parked = !do_cov && (!pass_there || (search && !knn_there));
+    if (wave == 1) {
+      if (lane < 18) {  // six 3-vectors
+        const int blk = lane / 3, i = lane % 3;
+        const int sto = blk == 0 ? 9 : (blk == 1 ? 21 : (blk == 2 ? 24 : (blk == 3 ? 27 : (blk == 4 ? 30 : 33))));
+        const int soo = blk == 0 ? 3 : (blk == 1 ? 9 : (blk == 2 ? 12 : (blk == 3 ? 15 : (blk == 4 ? 18 : 21))));
+        const double v = s_st[sto + i] + sol[soo + i];
+        c->st[sto + i] = v;
+        if (do_cov) res_store(&res->st[sto + i], v);
+      }
+    } else if (wave == 2) {
+      if (lane < N) c->solution[lane] = sol[lane];
+    } else if (lane == 0) {
+      s_sched = do_cov | (parked << 1);
       c->converged = converged;
       c->rematch_num = rematch;
       c->search_next = search;
@@ -481,33 +499,35 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
         res_store(&res->singular, 0);
       }
     }
-  } else if (do_cov) {
-    // Round 6: every one of the three wavefronts takes EIGHT ROWS of K H and then the same eight rows of
-    // state.cov = (I - K H) cov = cov - (K H) cov[0:12, :]   (:1111-1114, all operands already in LDS) - a row of the product needs its
-    // own row of K H and nothing else, so no workgroup barrier stands between the two and both run in the shadow of the state update on
-    // the first wavefront (round 5: K H here, then barrier - product over 256 lanes - barrier behind the state update: 1.4 us of the
-    // stopping pass; the sums of every entry are formed in the same order as before).
-    const int r0 = 8 * (wave - 1);
-    for (int e = lane; e < 8 * H; e += 64) {
-      const int r = r0 + e / H, cc = e % H;
-      double s2 = 0;
+    if (do_cov) {
+      // Round 6: every one of the three wavefronts takes EIGHT ROWS of K H and then the same eight rows of
+      // state.cov = (I - K H) cov = cov - (K H) cov[0:12, :]   (:1111-1114, all operands already in LDS) - a row of the product needs its
+      // own row of K H and nothing else, so no workgroup barrier stands between the two and both run in the shadow of the state update on
+      // the first wavefront (round 5: K H here, then barrier - product over 256 lanes - barrier behind the state update: 1.4 us of the
+      // stopping pass; the sums of every entry are formed in the same order as before).
+      const int r0 = 8 * (wave - 1);
+      for (int e = lane; e < 8 * H; e += 64) {
+        const int r = r0 + e / H, cc = e % H;
+        double s2 = 0;
 #pragma unroll
-      for (int k = 0; k < H; k++) s2 += K1c[r * LDH + k] * G[k * LDH + cc];
-      s_KH[r * H + cc] = s2;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int e = lane; e < 8 * N; e += 64) {
-      const int r = r0 + e / N, cc = e % N;
-      double s2 = s_cov[r * N + cc];
-      for (int k = 0; k < H; k++) s2 -= s_KH[r * H + k] * s_cov[k * N + cc];
-      s_x[r * N + cc] = s2;
+        for (int k = 0; k < H; k++) s2 += K1c[r * LDH + k] * G[k * LDH + cc];
+        s_KH[r * H + cc] = s2;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int e = lane; e < 8 * N; e += 64) {
+        const int r = r0 + e / N, cc = e % N;
+        double s2 = s_cov[r * N + cc];
+        for (int k = 0; k < H; k++) s2 -= s_KH[r * H + k] * s_cov[k * N + cc];
+        s_x[r * N + cc] = s2;
+      }
     }
   }
   LII_TS(9);
-  if (do_cov) {  // uniform
-    __syncthreads();
+  __syncthreads();
+  const int do_cov = s_sched & 1, parked = (s_sched >> 1) & 1;  // (uniform)
+  if (do_cov) {
     // the posterior leaves as its symmetric part: the gain above relies on P = P^T, and whatever asymmetry rounding puts into
     // (I - K H) P must not feed back into the next scan's gain (it compounds otherwise: the pose block of P grew to 0.4 within
     // 200 scans of a LIO run; the literal two-inversion algebra stays at 4e-5)
@@ -519,18 +539,22 @@ __device__ __forceinline__ void iekf_solve_body(IekfCtrl* c, IekfResult* res, Ne
       res_store(&res->st[36 + e], v);
     }
     if (tid < 91) res_store(&res->ne[tid], s_ne[tid]);
-    if (tid >= 96 && tid < 112) {
+    if (tid >= 96 && tid < 112) {  // (the log of the passes before was fetched with the control block: s_log)
       const int q = tid - 96;
-      res_store(&res->search_log[q], (q < it) ? c->search_log[q] : (q == it ? (search_now | (s_ok == 2 ? 2 : 0)) : 0));
+      res_store(&res->search_log[q], (q < it) ? s_log[q] : (q == it ? (search_now | (s_ok == 2 ? 2 : 0)) : 0));
+    }
+    if (tid >= 128 && tid < 146) {  // the two rotations: 2 x 9 entries
+      const int q = tid - 128;
+      res_store(&res->st[12 * (q / 9) + q % 9], s_rot[q]);
     }
     publish_done(res, s_int[10]);
-  } else if (parked) {  // uniform
+  } else if (parked) {
     publish_done(res, s_int[10] | kLoopParked);
   }
 #ifdef LII_SOLVE_TRACE
   __syncthreads();
   LII_TS(10);
-  if (threadIdx.x < 11) { if (it == 0) res->ts0[threadIdx.x] = s_ts[threadIdx.x]; else res->ts[threadIdx.x] = s_ts[threadIdx.x]; }
+  if (threadIdx.x < 16) { if (it == 0) res->ts0[threadIdx.x] = s_ts[threadIdx.x]; else res->ts[threadIdx.x] = s_ts[threadIdx.x]; }
 #endif
 }
 
@@ -561,7 +585,7 @@ __device__ __forceinline__ int warm_code() {
   int acc = 0;
   if (threadIdx.x < 192) {
 #pragma unroll
-    for (int u = 0; u < 2; u++) {
+    for (int u = 0; u < 3; u++) {  // (36 KB: the whole of k_reduce_solve, wherever the compiler has put the state update and the covariance tail)
       const char* a = pc + (size_t)(threadIdx.x + 192 * u) * 64;
       if (a + 64 <= end) acc ^= *reinterpret_cast<const volatile int*>(a);
     }
