@@ -214,6 +214,9 @@ int lii_replay_create(const lii_replay_config* cfg, lii_replay** out) {
   if (rc == LII_OK) rc = lii_params_apply(&r->prm, cfg->device, cfg->max_scan_points, cfg->max_map_points, &lc, &r->ing, &r->opts, &r->leaf);
   if (rc == LII_OK) rc = lii_create(&lc, &r->h);
   if (rc != LII_OK) { delete r; return rc; }
+  // preprocess/feature_extract_en (src/laserMapping.cpp:784 -> p_pre->feature_enabled): a whole-message ingest then hands on give_feature's pl_surf
+  rc = lii_ingest_set_features(r->h, r->prm.feature_extract_en ? 1 : 0);
+  if (rc != LII_OK) { lii_destroy(r->h); delete r; return rc; }
   if (cfg->result_path) r->result_path = cfg->result_path;
   r->stop_after_init = cfg->stop_after_init != 0;
   r->cut_frame_num = r->prm.cut_frame ? r->prm.cut_frame_num : 1;

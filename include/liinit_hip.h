@@ -392,7 +392,8 @@ int lii_scan_intensity_download(lii_handle h, int32_t which, float* out, int32_t
  * ... and, with lii_ingest_opts::cut_frame_num = 0, the callbacks' branch for `initialization/cut_frame: false`
  *                     (laserMapping.cpp:337-342, :374-379): Preprocess::process - oust_handler / velodyne_handler / l515_handler
  *                     (PointCloud2; any other lidar_type is "Error LiDAR Type" there, LII_ERR_INVALID here) and avia_handler
- *                     (CustomMsg) with feature extraction disabled, src/preprocess.cpp:337-713: the handler's filters (they are not
+ *                     (CustomMsg), src/preprocess.cpp:337-713 - with feature extraction disabled unless lii_ingest_set_features
+ *                     (below) turned it on: the handler's filters (they are not
  *                     the cutting functions' in every detail: velodyne_handler has no ring test), no time sort, no cut - ONE frame
  *                     holding pl_surf in input order, its first point included, begin_time_s = header.stamp; hand such a frame to
  *                     lii_scan_register with scan_sorted = 2 (sorted on the device first: the reference's bits - its
@@ -449,6 +450,38 @@ int lii_frame_select(lii_handle h, int32_t frame);
 int lii_ingest_pcl2_begin(lii_handle h, const void* data, int32_t n_points, const lii_pc2_fields* fields, const lii_ingest_opts* opts);
 int lii_ingest_livox_begin(lii_handle h, const void* points, int32_t n_points, const lii_livox_fields* fields, const lii_ingest_opts* opts);
 int lii_ingest_end(lii_handle h, lii_frame_info* frames, int32_t max_frames, int32_t* n_frames);
+/* Feature extraction (preprocess/feature_extract_en): Preprocess::give_feature :715-965, plane_judge :976-1071, edge_jump_judge :1073-1102
+ * and the feature branches of avia_handler :373-418, oust_handler :487-536 and velodyne_handler :585-652, on the device.
+ *   lii_ingest_set_features      a STANDING ORDER like lii_ingest_set_intensity, off by default.  With it on, a whole-message ingest
+ *                                (cut_frame_num == 0) of AVIA, VELO or OUSTER - one-call or overlapped form - returns ONE frame holding
+ *                                pl_surf of the feature branch: lines ascending, positions ascending within a line; begin_time_s = stamp_s,
+ *                                last_offset_ms = the curvature of its last point; an empty pl_surf yields no frame.  point_filter_num
+ *                                acts in the emission only (every point_filter_num-th point of a plane run, the float mean of an
+ *                                unfinished remainder); 1 <= n_scans <= 128 (else LII_ERR_INVALID).  Every other ingest is unaffected:
+ *                                any cut_frame_num > 0, and L515.  Under lii_ingest_set_intensity such a frame's intensities are all
+ *                                0.0f (the emitted surface points carry x, y, z and curvature only).  Messages under way keep what
+ *                                they were enqueued with.  The buffers the extraction needs are created by the first message that is
+ *                                ingested under the order; a handle that never hears of it holds what it held before.
+ *   lii_ingest_corners_download  pl_corn of the message whose frames are current (Edge_Jump / Edge_Plane points, whole): x, y, z,
+ *                                curvature per point into xyzt, the points' intensities into `intensity`; either may be NULL, both NULL
+ *                                return *n only.  With the order off, or before any such message: *n = 0, LII_OK.
+ *   lii_ingest_features_get      the order, and of the message whose frames are current: pl_surf.size(), pl_corn.size() and the number of
+ *                                lines the passes ran on (0 for a message that did not go through the feature branch).
+ * Every decision is an IEEE add / mul / div / sqrt in the reference's types and order; results are the reference's bits wherever the
+ * reference defines them.  It does NOT define them in these places, and the library does:
+ *   - Preprocess::disB is never initialised (src/preprocess.cpp:15-16 sets disA twice), yet plane_judge adds it: it is 0 here.
+ *   - types[plsize - 1].dista is never written, yet plane_judge pushes it into disarr whenever a group runs to the end of its line
+ *     (:1008): it is 0 here.  (What a node's first message sees when its heap is fresh; later messages there see recycled memory.)
+ *   - `while (types[head].range < blind) head++` (:724) runs off a line that is blind throughout: nothing is emitted for that line.
+ *   - an empty OUSTER line indexes types[-1] (:534): it yields nothing.
+ *   - in the edge-jump pass vecs[j] stays unset beside a blind neighbour (:846-853) and `intersect` is formed from it (:866): it is the
+ *     zero vector here - the quotient is NaN and every comparison with it is false.
+ *   - a plane group that runs to the end of its line marks types[plsize] (:750-756): only the points the line has are marked here.
+ * NULL handle / bad arguments: LII_ERR_INVALID; from inside lii_scan_job::while_waiting: LII_ERR_STATE.  Like every entry point they end a
+ * pre-armed launch first. */
+int lii_ingest_set_features(lii_handle h, int32_t on);
+int lii_ingest_corners_download(lii_handle h, float* xyzt, float* intensity, int32_t capacity, int32_t* n);
+int lii_ingest_features_get(lii_handle h, int32_t* on, int32_t* n_surf, int32_t* n_corn, int32_t* n_lines);
 
 /* ---------------------------------------------------------------- scan-to-map registration
  * lii_iekf_iterate: ONE pass of the per-point loop + Jacobian + normal-equation reduction at a fixed state —

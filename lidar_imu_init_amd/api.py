@@ -200,6 +200,9 @@ _DECLS = {
     "lii_scan_intensity_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_intensity_set_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_ingest_set_intensity": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_ingest_set_features": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_ingest_corners_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_ingest_features_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_scan_intensity_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lii_calib_set_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -675,6 +678,26 @@ class Registrar:
     def ingest_set_intensity(self, on=True):
         """The standing order: every ingest call from now on also forms its frames' intensities; frame_select attaches them."""
         self._check(self.L.lii_ingest_set_intensity(self.h, int(bool(on))))
+
+    def ingest_set_features(self, on=True):
+        """The standing order (preprocess/feature_extract_en; `on` may be Params.feature_extract_en): a whole-message ingest
+        (cut_frame_num = 0) of AVIA, VELO or OUSTER returns ONE frame holding the feature branch's pl_surf; ingest_corners gives pl_corn."""
+        self._check(self.L.lii_ingest_set_features(self.h, int(bool(on))))
+
+    def ingest_corners(self):
+        """pl_corn of the message whose frames are current: ((n, 4) float32 x y z curvature, (n,) float32 intensity)."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_ingest_corners_download(self.h, None, None, 0, C.byref(n)))
+        xyzt = np.zeros((max(n.value, 1), 4), np.float32)
+        inten = np.zeros(max(n.value, 1), np.float32)
+        self._check(self.L.lii_ingest_corners_download(self.h, _ptr(xyzt), _ptr(inten), len(xyzt), C.byref(n)))
+        return xyzt[:n.value], inten[:n.value]
+
+    def ingest_features(self):
+        """dict(on, n_surf, n_corn, n_lines): the order, and the counts of the message whose frames are current."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._check(self.L.lii_ingest_features_get(self.h, *[C.byref(x) for x in v]))
+        return dict(on=bool(v[0].value), n_surf=v[1].value, n_corn=v[2].value, n_lines=v[3].value)
 
     def scan_intensity_download(self, which=0):
         """which=0: the current scan's intensities; 1: the down-sampled cloud's, in the order scan_download(1) returns its points."""

@@ -2,7 +2,8 @@
 // sub-frame cutting, straight into device-resident scan frames (gfx950).  Replaces
 //   Preprocess::process_cut_frame_livox   reference src/preprocess.cpp:50-113
 //   Preprocess::process_cut_frame_pcl2    reference src/preprocess.cpp:115-335
-//   Preprocess::process (oust_handler / velodyne_handler / l515_handler / avia_handler, feature extraction disabled)
+//   Preprocess::process (oust_handler / velodyne_handler / l515_handler / avia_handler; their feature branches - lii_ingest_set_features -
+//                                         run behind this file's decode in lii_feature.hip)
 //                                         reference src/preprocess.cpp:337-713 - lii_ingest_opts::cut_frame_num == 0: the callbacks'
 //                                         branch for initialization/cut_frame: false (no time sort, no cut, input order)
 // for the point layouts of src/preprocess.h:35-116.  HBM-bound byte work: one pass over the raw records, one scan, one
@@ -25,6 +26,7 @@
 
 #include "../../include/liinit_hip.h"
 #include "lii_device.h"
+#include "lii_feature.h"
 #include "lii_launch.h"
 #include "lii_owned.h"
 
@@ -32,20 +34,7 @@ namespace lii {
 
 namespace {
 
-constexpr int kMaxLines = 128;   // MAX_LINE_NUM, src/preprocess.cpp:114
-constexpr int kMaxFrames = 64;
-
-struct IngestTable {  // written by k_cut_plan into mapped host memory
-  int n_frames;
-  int n_kept;        // pl_surf.size()
-  int n_emitted;     // points inside frames
-  int unsorted;      // 1: the kept points did NOT arrive in ascending time order (k_cut_apply)
-  int first[kMaxFrames];   // sorted index of the first point of frame c
-  int last[kMaxFrames];    // sorted index of the boundary point of frame c
-  double begin_ms[kMaxFrames];
-  double delta[kMaxFrames];  // stamp_ms - last_frame_end_time while frame c is filled
-  double tail_ms[kMaxFrames];  // adjusted curvature of the frame's last (boundary) point
-};
+// (kMaxLines, kMaxFrames and the frame table IngestTable: lii_feature.h - the feature launches write the table too)
 
 struct IngestCtx {
   DevBuf<uint8_t> d_raw;         // the message as it arrived (size(): its bytes + 64)
@@ -69,6 +58,12 @@ struct IngestCtx {
   DevBuf<float> d_fint;
   bool with_int = false;            // the message in this context was enqueued under the order: d_fint belongs to its frames
   int int_kind = 0, int_off = 0, int_step = 0;  // how a raw record yields the value (k_frame_intensity), for ingest_redo_sorted as well
+  // lii_ingest_set_features: the message in this context went through the feature branch (lii_feature.hip) - its one frame is pl_surf,
+  // fb.d_corn / fb.d_corn_int hold pl_corn.  The buffers are created by the first message that is ingested under the order.
+  FeatureBufs fb;
+  bool feat = false;
+  FeatureParams fp;
+  int corn_kind = 2, corn_off = 0, corn_step = 0;  // how a raw record yields a corner's intensity
 };
 
 template <class T>
@@ -94,6 +89,9 @@ __device__ __forceinline__ bool pc2_given_time(const uint8_t* raw, int n, const 
 }
 
 // one thread per raw point: decode, blind / NaN test, decimation and ring filter (the per-type loops :141-294)
+// FEAT: the collection loops of the feature branches (oust_handler :493-518, velodyne_handler :591-633) - `ring < N_SCANS` for both
+// types and NO decimation (point_filter_num acts in give_feature's emission loop only)
+template <bool FEAT>
 __global__ void k_pc2_decode(const uint8_t* __restrict__ raw, int n, Pc2Arg a, float4* __restrict__ pts, double* __restrict__ yaw,
                              uint8_t* __restrict__ ring_out, unsigned int* __restrict__ pass0, unsigned int* __restrict__ keep) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -128,7 +126,7 @@ __global__ void k_pc2_decode(const uint8_t* __restrict__ raw, int n, Pc2Arg a, f
   pass0[i] = ok ? 1u : 0u;
   // (velodyne_handler's feature-less branch, :661-700, has no `ring < N_SCANS` test; oust_handler's, :545-563, has)
   const bool ring_ok = (a.whole && a.lidar_type != LII_LIDAR_OUSTER) || ring < a.n_scans;
-  keep[i] = (ok && (i % a.pfn == 0) && ring_ok) ? 1u : 0u;
+  keep[i] = FEAT ? ((ok && ring < a.n_scans) ? 1u : 0u) : ((ok && (i % a.pfn == 0) && ring_ok) ? 1u : 0u);
 }
 
 // Time synthesis from the azimuth when the driver gives none (:163-185, :272-294): a sequential recurrence per ring —
@@ -177,16 +175,27 @@ struct LivoxArg {
   double blind2;
 };
 // v_i = the tag / line test of point i >= 1 (:60-62)
-__global__ void k_livox_valid(const uint8_t* __restrict__ raw, int n, LivoxArg a, unsigned int* __restrict__ valid) {
+// FEAT: the test of avia_handler's feature branch (:375-376), whose precedence lets a tag-0x00 point of a line >= N_SCANS pass (it is
+// populated in pl_full - the next record's duplicate test sees it - and lands in a buffer that is never processed: k_livox_decode
+// drops it); the line of every record goes to line_out for the partition by line
+template <bool FEAT>
+__global__ void k_livox_valid(const uint8_t* __restrict__ raw, int n, LivoxArg a, unsigned int* __restrict__ valid, uint8_t* __restrict__ line_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint8_t* p = raw + (size_t)i * a.f.point_step;
   const int line = rd<uint8_t>(p + a.f.line), tag = rd<uint8_t>(p + a.f.tag);
-  valid[i] = (i >= 1 && line < a.n_scans && ((tag & 0x30) == 0x10 || (tag & 0x30) == 0x00)) ? 1u : 0u;
+  if (FEAT) {
+    valid[i] = (i >= 1 && ((line < a.n_scans && (tag & 0x30) == 0x10) || (tag & 0x30) == 0x00)) ? 1u : 0u;
+    line_out[i] = (uint8_t)line;
+  } else {
+    valid[i] = (i >= 1 && line < a.n_scans && ((tag & 0x30) == 0x10 || (tag & 0x30) == 0x00)) ? 1u : 0u;
+  }
 }
 // cnt = inclusive scan of v (valid_point_num).  A point is decoded ("populated" in pl_full) when v_i and cnt_i % pfn == 0;
 // it is kept when it is outside the blind zone and differs from pl_full[i-1], which is the previous RAW point if that one
 // was populated and the zero point otherwise (:64-81).
+// FEAT (a.pfn is 1 there: every valid point is populated, :377-393): a kept point's line is one the sensor has
+template <bool FEAT>
 __global__ void k_livox_decode(const uint8_t* __restrict__ raw, int n, LivoxArg a, const unsigned int* __restrict__ valid,
                                const unsigned int* __restrict__ cnt, float4* __restrict__ pts, unsigned int* __restrict__ keep) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -207,6 +216,7 @@ __global__ void k_livox_decode(const uint8_t* __restrict__ raw, int n, LivoxArg 
       }
       k = ((double)fabsf(__fsub_rn(x, px)) > 1e-7) || ((double)fabsf(__fsub_rn(y, py)) > 1e-7) ||
           ((double)fabsf(__fsub_rn(z, pz)) > 1e-7);
+      if (FEAT) k = k && (int)rd<uint8_t>(p + a.f.line) < a.n_scans;
     }
   }
   pts[i] = out;
@@ -348,6 +358,8 @@ struct IngestRing {
   bool predict_sorted = false;
   bool never_predict = false;
   bool want_int = false;  // lii_ingest_set_intensity: every message enqueued from now on also forms its frames' intensities
+  bool want_feat = false;  // lii_ingest_set_features: every whole-message ingest of AVIA, VELO or OUSTER enqueued from now on extracts features
+  FeatureParams feat_params = feature_params_default();  // (the four cosines of src/preprocess.cpp:30-33, formed once)
   bool diag = false;  // LII_DIAG (the handle's switches, taken when the ring is created)
   long long n_unsorted_skipped = 0, n_redone = 0;
 };
@@ -429,7 +441,11 @@ int ingest_tail(lii_handle h, IngestCtx* c, int n, const lii_ingest_opts* o, int
   IngestTable* d_table = reinterpret_cast<IngestTable*>(c->d_aux.get());  // d_aux is free again after the Livox scan
   c->sort_skipped = false;
   c->cut_msg = o->cut_frame_num != 0;
-  if (o->cut_frame_num == 0) {  // Preprocess::process: no sort, no cut
+  if (c->feat) {  // Preprocess::process with feature_enabled: the one frame is give_feature's pl_surf (lii_feature.hip)
+    feature_launch(c->fb, c->fp, c->d_pts, c->d_ring, c->d_idx_a, c->d_rank, n, c->d_raw, c->corn_step, c->corn_off, c->corn_kind, o->stamp_s * 1000,
+                   c->d_frames, d_table, c->h_table, s);
+    ingest_intensity_launch(c, c->d_idx_a, n, 0, s);  // (int_kind 2: the emitted surface points carry no intensity - the reference's `ap`)
+  } else if (o->cut_frame_num == 0) {  // Preprocess::process: no sort, no cut
     hipLaunchKernelGGL(k_whole_apply, dim3(nb), dim3(256), 0, s, c->d_pts, c->d_idx_a, c->d_rank, n, o->stamp_s * 1000, c->d_frames, d_table, c->h_table);
     ingest_intensity_launch(c, c->d_idx_a, n, 0, s);
   } else {
@@ -516,6 +532,25 @@ int livox_check(lii_handle h, const void* points, int32_t n_points, const lii_li
   return LII_OK;
 }
 
+// A message that goes through the feature branch: its buffers (created by the first such message, grown with the per-point buffers),
+// the parameters of its launches, how a raw record yields a corner's intensity; its frame's own intensities are all 0.0f.
+int feature_prepare(lii_handle h, IngestCtx* c, const lii_ingest_opts* o, int corn_kind, int corn_off, int corn_step) {
+  if (o->n_scans < 1 || o->n_scans > kMaxLines)
+    return lii_internal_fail(h, LII_ERR_INVALID, "lii_ingest: feature extraction needs 1 <= n_scans <= 128 (MAX_LINE_NUM)");
+  HIPCHK(h, feature_reserve(&c->fb, c->d_pts.size()));
+  c->fp = ring_of(h)->feat_params;
+  c->fp.lidar_type = o->lidar_type;
+  c->fp.n_scans = o->n_scans;
+  c->fp.pfn = o->point_filter_num;
+  c->fp.blind = o->blind;
+  c->corn_kind = corn_kind;
+  c->corn_off = corn_kind == 2 ? 0 : corn_off;
+  c->corn_step = corn_step;
+  c->int_kind = 2;
+  c->int_off = 0;
+  return LII_OK;
+}
+
 // H2D of the raw bytes on `s_copy`, the message's launches on `s_kern` behind it (one stream for the one-call forms)
 int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points, const lii_pc2_fields* f, const lii_ingest_opts* o,
                  hipStream_t s_copy, hipStream_t s, hipEvent_t ev_copied) {
@@ -523,6 +558,7 @@ int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points,
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
   c->with_int = ring_of(h)->want_int;
+  c->feat = ring_of(h)->want_feat && o->cut_frame_num == 0 && (o->lidar_type == LII_LIDAR_VELO || o->lidar_type == LII_LIDAR_OUSTER);
   if (c->with_int) {
     rc = ingest_reserve_intensity(h, c);
     if (rc != LII_OK) return rc;
@@ -531,6 +567,10 @@ int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points,
     if (f->intensity < 0 || f->intensity + width > f->point_step) c->int_kind = 2;  // (a layout without the field)
     c->int_off = c->int_kind == 2 ? 0 : f->intensity;
     c->int_step = f->point_step;
+  }
+  if (c->feat) {
+    rc = feature_prepare(h, c, o, (f->intensity < 0 || f->intensity + 4 > f->point_step) ? 2 : 0, f->intensity, f->point_step);
+    if (rc != LII_OK) return rc;
   }
   HIPCHK(h, hipMemcpyAsync(c->d_raw, data, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
@@ -546,7 +586,8 @@ int pcl2_enqueue(lii_handle h, IngestCtx* c, const void* data, int32_t n_points,
   a.stamp_s = o->stamp_s;
   a.whole = o->cut_frame_num == 0 ? 1 : 0;
   const int nb = (n_points + 255) / 256;
-  hipLaunchKernelGGL(k_pc2_decode, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_pts, c->d_yaw, c->d_ring, c->d_aux, c->d_flag);
+  if (c->feat) hipLaunchKernelGGL(k_pc2_decode<true>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_pts, c->d_yaw, c->d_ring, c->d_aux, c->d_flag);
+  else hipLaunchKernelGGL(k_pc2_decode<false>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_pts, c->d_yaw, c->d_ring, c->d_aux, c->d_flag);
   if (o->lidar_type == LII_LIDAR_VELO || o->lidar_type == LII_LIDAR_ROBOSENSE) {
     hipLaunchKernelGGL(k_pc2_ring_times, dim3(1), dim3(kMaxLines), 0, s, c->d_raw, n_points, a, c->d_pts, c->d_yaw, c->d_ring, c->d_aux,
                        c->d_flag);
@@ -560,12 +601,17 @@ int livox_enqueue(lii_handle h, IngestCtx* c, const void* points, int32_t n_poin
   int rc = ingest_reserve(h, c, n_points, bytes);
   if (rc != LII_OK) return rc;
   c->with_int = ring_of(h)->want_int;
+  c->feat = ring_of(h)->want_feat && o->cut_frame_num == 0;
   if (c->with_int) {
     rc = ingest_reserve_intensity(h, c);
     if (rc != LII_OK) return rc;
     c->int_kind = (f->reflectivity < 0 || f->reflectivity + 1 > f->point_step) ? 2 : 1;
     c->int_off = c->int_kind == 2 ? 0 : f->reflectivity;
     c->int_step = f->point_step;
+  }
+  if (c->feat) {
+    rc = feature_prepare(h, c, o, (f->reflectivity < 0 || f->reflectivity + 1 > f->point_step) ? 2 : 1, f->reflectivity, f->point_step);
+    if (rc != LII_OK) return rc;
   }
   HIPCHK(h, hipMemcpyAsync(c->d_raw, points, bytes, hipMemcpyHostToDevice, s_copy));
   if (s_copy != s) {
@@ -575,12 +621,14 @@ int livox_enqueue(lii_handle h, IngestCtx* c, const void* points, int32_t n_poin
   LivoxArg a;
   a.f = *f;
   a.n_scans = o->n_scans;
-  a.pfn = o->point_filter_num;
+  a.pfn = c->feat ? 1 : o->point_filter_num;
   a.blind2 = o->blind * o->blind;
   const int nb = (n_points + 255) / 256;
-  hipLaunchKernelGGL(k_livox_valid, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux);
+  if (c->feat) hipLaunchKernelGGL(k_livox_valid<true>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_ring);
+  else hipLaunchKernelGGL(k_livox_valid<false>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_ring);
   inclusive_scan_u32(c->d_temp, c->d_temp.size(), c->d_aux, c->d_aux_rank, n_points, s);
-  hipLaunchKernelGGL(k_livox_decode, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_aux_rank, c->d_pts, c->d_flag);
+  if (c->feat) hipLaunchKernelGGL(k_livox_decode<true>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_aux_rank, c->d_pts, c->d_flag);
+  else hipLaunchKernelGGL(k_livox_decode<false>, dim3(nb), dim3(256), 0, s, c->d_raw, n_points, a, c->d_aux, c->d_aux_rank, c->d_pts, c->d_flag);
   return ingest_tail(h, c, n_points, o, 5, s);
 }
 
@@ -749,6 +797,45 @@ int lii_ingest_set_intensity(lii_handle h, int32_t on) {
   if (on && lii_internal_intensity_refused(h))
     return lii_internal_fail(h, LII_ERR_STATE, "lii_ingest_set_intensity: single rank only for now (a communicator is attached, or LII_TEST=host_solve)");
   ring_of(h)->want_int = on != 0;  // (messages under way keep what they were enqueued with)
+  return LII_OK;
+}
+
+int lii_ingest_set_features(lii_handle h, int32_t on) {
+  if (lii_internal_in_wait_hook(h)) return lii_internal_fail(h, LII_ERR_STATE, "lii_ingest_set_features: not from lii_scan_job::while_waiting");
+  lii_internal_prearm_cancel(h);
+  if (!h || (on != 0 && on != 1)) return lii_internal_fail(h, LII_ERR_INVALID, "lii_ingest_set_features: bad arguments");
+  ring_of(h)->want_feat = on != 0;  // (messages under way keep what they were enqueued with)
+  return LII_OK;
+}
+
+int lii_ingest_features_get(lii_handle h, int32_t* on, int32_t* n_surf, int32_t* n_corn, int32_t* n_lines) {
+  if (lii_internal_in_wait_hook(h)) return lii_internal_fail(h, LII_ERR_STATE, "lii_ingest_features_get: not from lii_scan_job::while_waiting");
+  lii_internal_prearm_cancel(h);
+  if (!h || !on || !n_surf || !n_corn || !n_lines) return lii_internal_fail(h, LII_ERR_INVALID, "lii_ingest_features_get: bad arguments");
+  IngestRing* r = ring_of(h);
+  const IngestCtx* c = &r->slot[r->front];
+  const bool have = c->have && c->feat;
+  *on = r->want_feat ? 1 : 0;
+  *n_surf = have ? c->table.n_kept : 0;
+  *n_corn = have ? c->table.n_corn : 0;
+  *n_lines = have ? c->table.n_feat_lines : 0;
+  return LII_OK;
+}
+
+int lii_ingest_corners_download(lii_handle h, float* xyzt, float* intensity, int32_t capacity, int32_t* n) {
+  if (lii_internal_in_wait_hook(h)) return lii_internal_fail(h, LII_ERR_STATE, "lii_ingest_corners_download: not from lii_scan_job::while_waiting");
+  lii_internal_prearm_cancel(h);
+  if (!h || !n || capacity < 0) return lii_internal_fail(h, LII_ERR_INVALID, "lii_ingest_corners_download: bad arguments");
+  IngestRing* r = ring_of(h);
+  const IngestCtx* c = &r->slot[r->front];
+  const int cnt = (c->have && c->feat) ? c->table.n_corn : 0;
+  *n = cnt;
+  if (cnt == 0 || (!xyzt && !intensity)) return LII_OK;
+  if (cnt > capacity) return lii_internal_fail(h, LII_ERR_CAPACITY, "lii_ingest_corners_download: more corners than capacity");
+  hipStream_t s = lii_internal_stream(h);
+  if (xyzt) HIPCHK(h, hipMemcpyAsync(xyzt, c->fb.d_corn.get(), (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, s));
+  if (intensity) HIPCHK(h, hipMemcpyAsync(intensity, c->fb.d_corn_int.get(), (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
   return LII_OK;
 }
 
