@@ -190,6 +190,9 @@ struct lii_replay {
   // lii_replay_set_map_history: points_cache_collect (:249-254, :304) - what the box delete removes is kept on the device; off by default
   int32_t history_capacity = 0;
   bool history_placed = false;
+  // lii_replay_set_li_init_resident: LI_Initialization as the one call lii_li_init_resident (interpolate = 1); off by default
+  bool li_init_resident = false;
+  lii_li_init_report init_report{};
 };
 
 static int fail(lii_replay* r, int code, const std::string& msg) {
@@ -248,6 +251,22 @@ lii_handle lii_replay_handle(lii_replay* r) { return r ? r->h : nullptr; }
 int lii_replay_set_device_imu(lii_replay* r, int32_t on) {
   if (!r) return LII_ERR_INVALID;
   r->device_imu = on != 0;
+  return LII_OK;
+}
+
+// 1: LI_Initialization (src/laserMapping.cpp:1179) is the one call lii_li_init_resident with interpolate = 1 - the accumulated IMU and
+// LiDAR-odometry states go up once and the whole initialization runs on the device.  0 (default): lii_li_init_interpolate on the host,
+// then lii_li_init_run, as before.
+int lii_replay_set_li_init_resident(lii_replay* r, int32_t on) {
+  if (!r) return LII_ERR_INVALID;
+  r->li_init_resident = on != 0;
+  return LII_OK;
+}
+// the report of that call (LII_ERR_STATE before the initialization has run with the switch on)
+int lii_replay_li_init_report(lii_replay* r, lii_li_init_report* out) {
+  if (!r || !out) return LII_ERR_INVALID;
+  if (r->init_report.struct_size == 0) return fail(r, LII_ERR_STATE, "lii_replay_li_init_report: no resident initialization yet");
+  *out = r->init_report;
   return LII_OK;
 }
 
@@ -866,11 +885,32 @@ static int process(lii_replay* r) {
     }
     if (sufficient) {
       r->data_accum_finished = true;
-      std::vector<lii_calib_state> oi(r->lidar_states.size()), ol(r->lidar_states.size());
-      int32_t n = 0;
-      rc = lii_li_init_interpolate(r->imu_all.data(), int32_t(r->imu_all.size()), r->lidar_states.data(), int32_t(r->lidar_states.size()),
-                                   r->move_start_time, oi.data(), ol.data(), &n);
-      if (rc == LII_OK) rc = lii_li_init_run(r->h, oi.data(), ol.data(), n, r->prm.orig_odom_freq, r->cut_frame_num, &r->init, &r->init_lag1, &r->init_total);
+      if (r->li_init_resident) {
+        lii_li_init_job job{};
+        job.struct_size = sizeof(job);
+        job.interpolate = 1;
+        job.imu = r->imu_all.data();
+        job.n_imu = int32_t(r->imu_all.size());
+        job.lidar = r->lidar_states.data();
+        job.n_lidar = int32_t(r->lidar_states.size());
+        job.move_start_time = r->move_start_time;
+        job.orig_odom_freq = r->prm.orig_odom_freq;
+        job.cut_frame_num = r->cut_frame_num;
+        lii_li_init_report rep{};
+        rep.struct_size = sizeof(rep);
+        rc = lii_li_init_resident(r->h, &job, &r->init, &rep);
+        if (rc == LII_OK) {
+          r->init_report = rep;
+          r->init_lag1 = rep.time_lag_1;
+          r->init_total = rep.total_time_lag;
+        }
+      } else {
+        std::vector<lii_calib_state> oi(r->lidar_states.size()), ol(r->lidar_states.size());
+        int32_t n = 0;
+        rc = lii_li_init_interpolate(r->imu_all.data(), int32_t(r->imu_all.size()), r->lidar_states.data(), int32_t(r->lidar_states.size()),
+                                     r->move_start_time, oi.data(), ol.data(), &n);
+        if (rc == LII_OK) rc = lii_li_init_run(r->h, oi.data(), ol.data(), n, r->prm.orig_odom_freq, r->cut_frame_num, &r->init, &r->init_lag1, &r->init_total);
+      }
       if (rc != LII_OK) return fail(r, rc, std::string("LI_Initialization: ") + lii_last_error(r->h));
       r->online_calib_starts_time = r->lidar_end_time;
       // Transfer to FAST-LIO2 (:1183-1212): the body frame becomes the IMU frame

@@ -802,6 +802,65 @@ int lii_zero_phase_filter(lii_handle h, const lii_calib_state* in, int32_t n_seq
 int lii_xcorr_lag(lii_handle h, const lii_calib_state* imu, const lii_calib_state* lidar, int32_t n, int32_t* lag_imu_wrt_lidar);
 int lii_li_init_set_device(lii_handle h, int32_t on_device);
 
+/* LI_Init::LI_Initialization resident on the device (include/LI_init/LI_init.cpp:586-632): one upload of the accumulated states, then
+ * a fixed sequence of launches on the handle's stream - downsample_interpolate_IMU (:82-125), IMU_time_compensate (:195-221), both
+ * zero_phase_filt (:260-315), normalize_acc (:494-504), cut_sequence_tail (:223-238), xcorr_temporal_init (:160-193), central_diff
+ * (:127-158), acc_interpolate (:240-258) and the three least-squares solves (:317-492), each a whole Levenberg-Marquardt in one launch -
+ * and ONE wait of the host, at the end.  The sequences stay in place: what the host chain erases is a start index and a length in a
+ * control block in device memory that the later launches read; no length visits the host before the end.  The conditioning is the
+ * host chain's arithmetic operation for operation (same bits); the solves evaluate with lii_calib_eval's device function (same bits at
+ * the same parameters) and restate lii_calib_solve_stage's trust-region loop on the device, where sin / cos / pow come from the device
+ * library: the path of a solve can differ from the host LM's in the last bits.
+ *   interpolate = 1: imu = every raw IMU CalibState (ang_vel, linear_acc in m/s^2, timestamp), lidar = every LiDAR-odometry CalibState;
+ *                    downsample_interpolate_IMU runs first (what lii_li_init_interpolate does on the host).
+ *   interpolate = 0: the aligned sequences lii_li_init_run takes (n_imu == n_lidar).
+ * Refused on the host before anything is enqueued, LII_ERR_INVALID: NULL handle / job / out / sequences, a wrong struct_size,
+ * interpolate other than 0 or 1, orig_odom_freq < 1 or cut_frame_num < 1, n < 200 or n_imu != n_lidar (aligned form), n_imu < 6 or
+ * n_lidar < 1 (raw form).  What only the data decides is found on the device, which then skips the rest of the sequence; the call
+ * returns LII_ERR_INVALID (fewer than 6 raw IMU states or fewer than 200 aligned states after interpolation; "fewer than 61 aligned
+ * states left to filter", the text of lii_li_init_run) and the handle stays usable.  From inside lii_scan_job::while_waiting:
+ * LII_ERR_STATE.  Like every entry point it ends a pre-armed launch of the handle first.
+ * After a successful call the stage-3 sequences are the handle's calibration buffers, as after lii_li_init_run: lii_calib_eval may follow.
+ * The call allocates only when its inputs are longer than any before (the buffers grow geometrically). */
+typedef struct lii_li_init_job {
+  uint32_t struct_size;
+  int32_t interpolate;
+  const lii_calib_state* imu;
+  int32_t n_imu;
+  const lii_calib_state* lidar;
+  int32_t n_lidar;
+  double move_start_time; /* interpolate == 1 only */
+  int32_t orig_odom_freq, cut_frame_num;
+} lii_li_init_job;
+/* lii_li_init_report::termination - the exits of the trust-region loop (Ceres' order of tests) */
+enum lii_lm_termination {
+  LII_LM_GRADIENT_AT_START = 0, /* gradient tolerance at the projected start point: no iteration */
+  LII_LM_MAX_ITERATIONS = 1,
+  LII_LM_MIN_RADIUS = 2,
+  LII_LM_INVALID_STEPS = 3,     /* five steps in a row without a positive model decrease */
+  LII_LM_PARAMETER_TOLERANCE = 4,
+  LII_LM_FUNCTION_TOLERANCE = 5,
+  LII_LM_GRADIENT_TOLERANCE = 6 /* after an accepted step */
+};
+typedef struct lii_li_init_report {
+  uint32_t struct_size;
+  int32_t n_aligned, n_stage12, n_stage3; /* states after interpolation / entering stages 1-2 / entering stage 3 */
+  int32_t lag_samples;                    /* lag_IMU_wtr_Lidar of the cross-correlation */
+  int32_t launches, host_waits;           /* kernel launches enqueued by the call (a constant of the build); stream waits made by it (1) */
+  int32_t termination[3];                 /* enum lii_lm_termination per stage */
+  double time_lag_1, total_time_lag;
+  double params[3][24];                   /* the final point of each stage in lii_calib_eval's parameter layout */
+} lii_li_init_report;
+int lii_li_init_resident(lii_handle h, const lii_li_init_job* job, lii_calib_result* out, lii_li_init_report* rep /* may be NULL */);
+/* The sequences the last successful resident run solved on - what the reference dumps into Log/IMU_meas.txt, Log/LiDAR_meas.txt and
+ * Log/acc_cost.txt (LI_init.cpp:606-623).  which = 1: entering stages 1 / 2; which = 2: entering stage 3.  Both pointers NULL: *n
+ * only.  capacity < *n: LII_ERR_CAPACITY, nothing written.  No resident run yet: LII_ERR_STATE.  Any other `which`: LII_ERR_INVALID. */
+int lii_li_init_resident_fetch(lii_handle h, int32_t which, lii_calib_state* imu, lii_calib_state* lidar, int32_t capacity, int32_t* n);
+/* solve_Rotation_only / solve_Rot_bias_gyro / solve_trans_biasacc_grav (LI_init.cpp:317-492) with the contract of
+ * lii_calib_solve_stage on the buffers of lii_calib_set_buffers, the whole Levenberg-Marquardt in one launch: `inout` goes up, the
+ * launch runs, the result comes back.  No buffers uploaded: LII_ERR_STATE. */
+int lii_calib_solve_stage_dev(lii_handle h, int32_t stage, lii_calib_result* inout);
+
 /* ---------------------------------------------------------------- multi-GPU (points of one scan sharded across ranks)
  * One process per GPU.  Rank 0 creates an id, the caller ships the 128 bytes to the other ranks (e.g.
  * torch.distributed broadcast), every rank calls lii_comm_init with the SAME state / options per scan; afterwards

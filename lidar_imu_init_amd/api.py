@@ -124,6 +124,19 @@ class lii_calib_result(C.Structure):
                 ("iterations", C.c_int32 * 3), ("final_cost", C.c_double * 3)]
 
 
+class lii_li_init_job(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("interpolate", C.c_int32), ("imu", C.c_void_p), ("n_imu", C.c_int32),
+                ("lidar", C.c_void_p), ("n_lidar", C.c_int32), ("move_start_time", C.c_double),
+                ("orig_odom_freq", C.c_int32), ("cut_frame_num", C.c_int32)]
+
+
+class lii_li_init_report(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_aligned", C.c_int32), ("n_stage12", C.c_int32), ("n_stage3", C.c_int32),
+                ("lag_samples", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32),
+                ("termination", C.c_int32 * 3), ("time_lag_1", C.c_double), ("total_time_lag", C.c_double),
+                ("params", (C.c_double * 24) * 3)]
+
+
 _DECLS = {
     # name: (restype, argtypes)
     "lii_abi_version": (C.c_int, []),
@@ -216,6 +229,10 @@ _DECLS = {
     "lii_zero_phase_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lii_xcorr_lag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_li_init_set_device": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_li_init_resident": (C.c_int, [C.c_void_p, C.POINTER(lii_li_init_job), C.POINTER(lii_calib_result),
+                                       C.POINTER(lii_li_init_report)]),
+    "lii_li_init_resident_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_calib_solve_stage_dev": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(lii_calib_result)]),
     "lii_comm_unique_id": (C.c_int, [C.c_void_p]),
     "lii_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lii_comm_init_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
@@ -1049,6 +1066,37 @@ class Registrar:
 
     def li_init_set_device(self, on: bool):
         self._check(self.L.lii_li_init_set_device(self.h, int(on)))
+
+    def li_init_resident(self, imu22, lidar22, orig_odom_freq, cut_frame_num, interpolate=False, move_start_time=0.0):
+        """LI_Init::LI_Initialization resident on the device: one upload, a fixed sequence of launches, one wait.
+        interpolate = False: the aligned sequences li_init_run takes; True: every raw IMU state and every LiDAR-odometry state
+        (downsample_interpolate_IMU runs first).  Returns (lii_calib_result, lii_li_init_report)."""
+        imu = np.ascontiguousarray(imu22, np.float64).reshape(-1, 22)
+        lid = np.ascontiguousarray(lidar22, np.float64).reshape(-1, 22)
+        job = lii_li_init_job(C.sizeof(lii_li_init_job), int(bool(interpolate)), imu.ctypes.data, len(imu), lid.ctypes.data, len(lid),
+                              float(move_start_time), int(orig_odom_freq), int(cut_frame_num))
+        res, rep = lii_calib_result(), lii_li_init_report()
+        rep.struct_size = C.sizeof(lii_li_init_report)
+        self._check(self.L.lii_li_init_resident(self.h, C.byref(job), C.byref(res), C.byref(rep)))
+        return res, rep
+
+    def li_init_resident_fetch(self, which):
+        """The sequences the last resident run solved on: which = 1 entering stages 1 / 2, which = 2 entering stage 3.
+        Returns (imu22, lidar22)."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_li_init_resident_fetch(self.h, int(which), None, None, 0, C.byref(n)))
+        imu, lid = calib_state_array(n.value), calib_state_array(n.value)
+        if n.value:
+            self._check(self.L.lii_li_init_resident_fetch(self.h, int(which), _ptr(imu), _ptr(lid), n.value, C.byref(n)))
+        return imu, lid
+
+    def calib_solve_stage_dev(self, stage, result=None):
+        """calib_solve_stage with the whole Levenberg-Marquardt in one launch."""
+        res = result if result is not None else lii_calib_result()
+        if result is None:
+            res.R_LI[:] = list(np.eye(3).reshape(-1))
+        self._check(self.L.lii_calib_solve_stage_dev(self.h, stage, C.byref(res)))
+        return res
 
     # ------------------------------------------------------------------ multi-GPU
     def comm_unique_id(self) -> bytes:

@@ -275,6 +275,18 @@ struct lii_context {
     int n_cal = 0;
 
     bool li_init_device = false;  // lii_li_init_set_device: zero-phase filter + cross-correlation of lii_li_init_run on the device
+
+    // lii_li_init_resident / lii_calib_solve_stage_dev (lii_li_init_resident.hip).  Nothing here exists before the first such call; the
+    // buffers grow geometrically and are never released before the handle goes.
+    struct Resident {
+      DevBuf<double> d_seq;    // sized by cap_n: the sequences (in place, as views), the stage-3 copies, the filter's hand-over, the correlation
+      DevBuf<double> d_raw;    // sized by cap_raw: the raw IMU states of the interpolating form, their filtered accelerations and stamps
+      DevBuf<double> d_small;  // the control block and the result block
+      int cap_n = 0, cap_raw = 0;
+      bool have_run = false;            // a resident run has succeeded: lii_li_init_resident_fetch serves it
+      int ib12 = 0, lb12 = 0, n12 = 0;  // ... the view of the stage 1/2 sequences in d_seq
+      int n3 = 0;                       // ... the length of the stage 3 copies
+    } res;
   } cal;
   // ---- IMU processing (lii_capi_imu.cpp, lii_imu.hip)
   struct ImuState {

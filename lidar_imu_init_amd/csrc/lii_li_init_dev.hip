@@ -8,7 +8,8 @@
 //   k_xcorr        LI_Init::xcorr_temporal_init (:160-193): O(N^2) cross-correlation of the |omega| series; one lane per lag
 //                  (2N - 1 lanes), each summing its products in the host's index order; the first maximum in lag order wins,
 //                  as the reference's strict `>` does.
-//   k_calib_eval   include/LI_init/LI_init.h:91-205 residuals + analytic Jacobians of the three calibration stages (lii_calib.cpp drives them)
+//   k_calib_eval   include/LI_init/LI_init.h:91-205 residuals + analytic Jacobians of the three calibration stages (lii_calib.cpp drives them;
+//                  the arithmetic is calib_eval_block of lii_li_init_dev.h, shared with the device LM of lii_li_init_resident.hip)
 // The first two exist so that the calibration can be re-run on device-resident buffers during accumulation without a round trip of the
 // sequences; at N_s ~ 10^3 the filter is latency (a 1 000-step dependent chain), the correlation is where the device wins.
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 #include "../../include/liinit_hip.h"
 #include "lii_device.h"
 #include "lii_launch.h"
+#include "lii_li_init_dev.h"
 #include "lii_owned.h"
 
 namespace lii {
@@ -69,9 +71,6 @@ __global__ __launch_bounds__(64) void k_zero_phase(double* __restrict__ seqs, in
   butter_pass(tmp, 1, n, base, 22, x, y, false, true);   // base = reverse(butter(tmp))
 }
 
-__device__ __forceinline__ double norm3_at(const double* __restrict__ rec) {
-  return sqrt(rec[9] * rec[9] + rec[10] * rec[10] + rec[11] * rec[11]);
-}
 // a[i] = |w_imu|, b[i] = |w_lidar| and their running means (sequential, as the host forms them): one lane
 __global__ void k_xcorr_prepare(const double* __restrict__ imu, const double* __restrict__ lidar, int n, double* __restrict__ a,
                                 double* __restrict__ b, double* __restrict__ means) {
@@ -90,146 +89,24 @@ __global__ void k_xcorr_prepare(const double* __restrict__ imu, const double* __
 // corr[k] for lag = k - (n - 1), one lane per lag, products summed in ascending i
 __global__ __launch_bounds__(256) void k_xcorr(const double* __restrict__ a, const double* __restrict__ b, const double* __restrict__ means,
                                                int n, double* __restrict__ corr) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= 2 * n - 1) return;
-  const int lag = k - (n - 1);
-  const double ma = means[0], mb = means[1];
-  const int i0 = max(0, -lag), i1 = min(n, n - lag);
-  double c = 0;
-  for (int i = i0; i < i1; i++) c += (a[i] - ma) * (b[i + lag] - mb);
-  corr[k] = c;
+  xcorr_lane(a, b, means, n, corr, blockIdx.x * 256 + threadIdx.x);
 }
 // first maximum in ascending lag order (the reference: `if (c > best)`), result = lag_IMU_wtr_Lidar = -lag
 __global__ __launch_bounds__(256) void k_xcorr_argmax(const double* __restrict__ corr, int n, int* __restrict__ out_lag) {
   __shared__ double s_v[256];
   __shared__ int s_k[256];
-  const int m = 2 * n - 1;
-  double best = -1.7976931348623157e308;
-  int bk = 0x7FFFFFFF;
-  for (int k = threadIdx.x; k < m; k += 256) {
-    const double v = corr[k];
-    if (v > best) { best = v; bk = k; }  // a lane walks its lags in ascending order: strict '>' keeps its first maximum
-  }
-  s_v[threadIdx.x] = best;
-  s_k[threadIdx.x] = bk;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const double v = s_v[threadIdx.x + s];
-      const int k = s_k[threadIdx.x + s];
-      if (v > s_v[threadIdx.x] || (v == s_v[threadIdx.x] && k < s_k[threadIdx.x])) { s_v[threadIdx.x] = v; s_k[threadIdx.x] = k; }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out_lag = s_k[0] == 0x7FFFFFFF ? 0 : -(s_k[0] - (n - 1));
+  xcorr_argmax_block(corr, n, out_lag, s_v, s_k);
 }
 
 }  // namespace
 
-// ------------------------------------------------------------------------------------------------
-// LI-Init residual / Jacobian evaluators (include/LI_init/LI_init.h:91-205).  Records are 22 doubles:
-// rot_end[9], ang_vel[3], linear_vel[3], ang_acc[3], linear_acc[3], timestamp.
-// Tangent convention R <- Exp(delta) R  (Appendix B of SURVEY.md):
-//   stage 1/2: r = R w_L - w_I [- (dT + t_d) a_I + b_g];  dr/ddelta = -[R w_L]x, dr/db_g = I, dr/dt_d = -alpha_I
-//   stage 3:   r = R_LL0 R_LI^T a_I - R_LL0 b_a + R_GL0 g - a_L - R_LL0 ([w]x^2 + [alpha]x) T_IL
-//              dr/ddelta_G = -[R_GL0 g]x, dr/db_a = -R_LL0, dr/dT_IL = -R_LL0 ([w]x^2 + [alpha]x)
-// Output per block: dof*dof + dof + 1 doubles (J^T J row-major, J^T r, 0.5 sum r^2), reduced on one block.
-
+// LI-Init residual / Jacobian evaluators (include/LI_init/LI_init.h:91-205): calib_eval_block of lii_li_init_dev.h, which the
+// device Levenberg-Marquardt (lii_li_init_resident.hip) calls as well.
 template <int STAGE>
 __global__ __launch_bounds__(256) void k_calib_eval(const double* __restrict__ imu, const double* __restrict__ lidar, int n,
                                                     const double* __restrict__ params, double* __restrict__ out) {
-  constexpr int DOF = STAGE == 1 ? 3 : (STAGE == 2 ? 7 : 9);
-  constexpr int NOUT = DOF * DOF + DOF + 1;
-  __shared__ double sh[256];
-  double acc[NOUT];
-#pragma unroll
-  for (int k = 0; k < NOUT; k++) acc[k] = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const double* I = imu + 22 * (size_t)i;
-    const double* L = lidar + 22 * (size_t)i;
-    double r[3];
-    double J[3][DOF];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-      for (int b = 0; b < DOF; b++) J[a][b] = 0;
-    if (STAGE == 1 || STAGE == 2) {
-      const double* R = params;
-      double Rw[3];
-      mat3_vec(R, L + 9, Rw);
-#pragma unroll
-      for (int a = 0; a < 3; a++) r[a] = Rw[a] - I[9 + a];
-      // -[Rw]x
-      J[0][1] = Rw[2]; J[0][2] = -Rw[1];
-      J[1][0] = -Rw[2]; J[1][2] = Rw[0];
-      J[2][0] = Rw[1]; J[2][1] = -Rw[0];
-      if (STAGE == 2) {
-        const double* bg = params + 9;
-        double td = params[12];
-        double dT = L[21] - I[21];
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-          r[a] = r[a] - (dT + td) * I[15 + a] + bg[a];
-          J[a][(3 + a) % DOF] = 1.0;
-          J[a][6 % DOF] = -I[15 + a];
-        }
-      }
-    } else {
-      const double* RG = params;        // R_GL0
-      const double* ba = params + 9;    // bias_aL
-      const double* Til = params + 12;  // T_IL
-      const double* RLI = params + 15;  // R_LI (fixed)
-      const double* RLL0 = L;           // rot_end
-      const double g[3] = {0, 0, -9.81};  // STD_GRAV (LI_init.h:27)
-      double aI_L[3], t1[3], Rg[3];
-      mat3t_vec(RLI, I + 18, aI_L);  // R_LI^T a_I
-      mat3_vec(RLL0, aI_L, t1);      // R_LL0 R_LI^T a_I
-      mat3_vec(RG, g, Rg);
-      const double* w = L + 9;
-      const double* al = L + 15;
-      double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-      double A[9] = {0, -al[2], al[1], al[2], 0, -al[0], -al[1], al[0], 0};
-      double M[9], RM[9];
-      mat3_mul(W, W, M);
-#pragma unroll
-      for (int e = 0; e < 9; e++) M[e] += A[e];
-      mat3_mul(RLL0, M, RM);
-      double Rb[3], RMt[3];
-      mat3_vec(RLL0, ba, Rb);
-      mat3_vec(RM, Til, RMt);
-#pragma unroll
-      for (int a = 0; a < 3; a++) r[a] = t1[a] - Rb[a] + Rg[a] - L[18 + a] - RMt[a];
-      J[0][1] = Rg[2]; J[0][2] = -Rg[1];
-      J[1][0] = -Rg[2]; J[1][2] = Rg[0];
-      J[2][0] = Rg[1]; J[2][1] = -Rg[0];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-          J[a][(3 + b) % DOF] = -RLL0[3 * a + b];
-          J[a][(6 + b) % DOF] = -RM[3 * a + b];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < DOF; a++) {
-#pragma unroll
-      for (int b = 0; b < DOF; b++) acc[a * DOF + b] += J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b];
-      acc[DOF * DOF + a] += J[0][a] * r[0] + J[1][a] * r[1] + J[2][a] * r[2];
-    }
-    acc[DOF * DOF + DOF] += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-  }
-  // fixed-order block reduction (tree over 256 threads), one output at a time
-#pragma unroll
-  for (int k = 0; k < NOUT; k++) {
-    sh[threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[k] = sh[0];
-    __syncthreads();
-  }
+  __shared__ double sh[kEvalLds];
+  calib_eval_block<STAGE>(imu, lidar, n, params, sh, out);
 }
 template __global__ void k_calib_eval<1>(const double*, const double*, int, const double*, double*);
 template __global__ void k_calib_eval<2>(const double*, const double*, int, const double*, double*);
