@@ -579,6 +579,24 @@ int lii_destroy(lii_handle h) {
                    double(t[20]) / double(t[16]), 0.01 * t[17] / double(t[16]), 0.01 * t[18] / double(t[16]), 0.01 * t[19] / double(t[16]));
   }
 #endif
+#ifdef LII_FRONT_TRACE
+  {
+    unsigned long long t[32] = {};
+    lii::front_trace_read(t);
+    if (t[0] > 0) {
+      const double n = double(t[0]);
+      std::fprintf(stderr, "[libliinit_hip front trace] de-skew: %llu workgroups, us since the workgroup's start: point loaded %.2f, pose times in LDS %.2f, head found %.2f, "
+                   "de-skewed %.2f, box row written %.2f, CAS returned %.2f, end %.2f; wait for the record's tag (pre-armed form) %.2f\n", t[0], 0.01 * t[2] / n,
+                   0.01 * t[3] / n, 0.01 * t[4] / n, 0.01 * t[5] / n, 0.01 * t[6] / n, 0.01 * t[7] / n, 0.01 * t[8] / n, 0.01 * t[9] / n);
+    }
+    if (t[16] > 0) {
+      const double n = double(t[16]);
+      std::fprintf(stderr, "[libliinit_hip front trace] emit: %llu workgroups, us since the workgroup's start: point and slot number back %.2f, slot line back %.2f, "
+                   "box folded %.2f, count published %.2f, lower counts collected %.2f, end %.2f\n", t[16], 0.01 * t[18] / n,
+                   0.01 * t[19] / n, 0.01 * t[20] / n, 0.01 * t[21] / n, 0.01 * t[23] / n, 0.01 * t[24] / n);
+    }
+  }
+#endif
 #ifdef LII_GAP_TRACE
   if (h->d_gran) {
     unsigned long long g[4] = {0, 0, 0, 0};

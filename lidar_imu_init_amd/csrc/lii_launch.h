@@ -108,6 +108,9 @@ void launch_loop_resume(IekfCtrl* c, unsigned int plan_mask, hipStream_t s);
 void launch_iekf_solve(IekfCtrl* c, const double* ne, IekfResult* res, hipStream_t s);
 int register_blocks(int n);  // (lii_fit.hip)
 // undistortion (lii_scan.hip)
+#ifdef LII_FRONT_TRACE
+void front_trace_read(unsigned long long out[32]);  // (measurement builds: the phase sums of the de-skew and emit workgroups)
+#endif
 void launch_time_extent(const float4* pts, int n, unsigned long long* extent, unsigned long long* extent_next, float4* copy_to,
                         const void* ctrl_src, void* ctrl_dst, size_t ctrl_bytes, hipStream_t s);
 // the time sort of a scan: key[i] = order-preserving image of t (-0.0 as +0.0), idx[i] = i; then sort_pairs_u32; then dst[i] = src[idx[i]]

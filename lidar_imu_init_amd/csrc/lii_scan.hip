@@ -15,6 +15,49 @@
 
 namespace lii {
 
+// Measurement builds (-DLII_FRONT_TRACE, tools/ab_build.sh): where the time of a de-skew and of an emit workgroup goes - 100 MHz stamps
+// taken by thread 0 of every scan workgroup behind the phases named below, kept in LDS and added up at the workgroup's end as
+// "ticks since the workgroup's first stamp", read back by lii_destroy.  A stamp marked W first waits for the wavefront's outstanding
+// loads and atomics (vmcnt(0)): it says when the data was there, and it serialises what the product build may overlap - the table
+// prices the chain of thread 0's wavefront, not the launch.
+//   [0] de-skew workgroups; [1 + k]: 0 start (gated form: the record's tag seen), 1 point loaded W, 2 pose times / record in LDS,
+//       3 head found, 4 point de-skewed, 5 bounding-box row written, 6 CAS returned W, 7 end; [9] the gated form's wait for the tag
+//   [16] emit workgroups; [17 + k]: 0 start, 1 point and slot number back W, 2 slot line back W, 3 box folded, 4 count published,
+//        6 lower counts collected, 7 end W (centroid stored)
+#ifdef LII_FRONT_TRACE
+__device__ unsigned long long g_front_trace[32];
+__device__ __forceinline__ long long* ft_lds() {
+  __shared__ long long s_ft[8];
+  return s_ft;
+}
+#define LII_FT(k) do { if (threadIdx.x == 0) ft_lds()[k] = wall_clock64(); } while (0)
+#define LII_FT_W(k) do { if (threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ft_lds()[k] = wall_clock64(); } } while (0)
+// (thread 0 alone: a stamp the workgroup did not take repeats the one before it)
+__device__ __forceinline__ void ft_flush(int base) {
+  if (threadIdx.x != 0) return;
+  const long long* s = ft_lds();
+  atomicAdd(&g_front_trace[base], 1ull);
+  long long last = s[0];
+  for (int k = 1; k < 8; k++) {
+    if (s[k] != 0) last = s[k];
+    atomicAdd(&g_front_trace[base + 1 + k], (unsigned long long)(last - s[0]));
+  }
+}
+__device__ __forceinline__ void ft_begin() {
+  if (threadIdx.x != 0) return;
+  for (int k = 1; k < 8; k++) ft_lds()[k] = 0;
+  ft_lds()[0] = wall_clock64();
+}
+#define LII_FT_BEGIN() ft_begin()
+#define LII_FT_END(base) ft_flush(base)
+void front_trace_read(unsigned long long out[32]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_front_trace), sizeof(unsigned long long) * 32); }
+#else
+#define LII_FT(k)
+#define LII_FT_W(k)
+#define LII_FT_BEGIN()
+#define LII_FT_END(base)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // undistortion
 // extent[0] = (ord(t_min) << 32) | index of the first point with that time ; extent[1] = ord(t_max)
@@ -136,20 +179,42 @@ __device__ __forceinline__ void backprop_once(const double* __restrict__ head /*
   p[0] = o[0]; p[1] = o[1]; p[2] = o[2];
 }
 
-// Bounding box of the points a 256-lane workgroup holds (non-finite points excluded; order-preserving uints): wave shuffle +
-// LDS reduction; afterwards lanes 0..2 hold the min / max of axis threadIdx.x in lo[0] / hi[0].  Every lane must call it.
+// Minimum / maximum over the wavefront on DPP row operations (lii_fit.hip: wave_min_f32 - ~60 cycles where six rounds of __shfl_xor,
+// LDS permutes, take ~700): lane 63 ends up with the result, the other lanes with partial ones.  Every lane of the wavefront must be
+// active.  min and max of unsigned integers: exact in any order.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned int bbox_dpp(unsigned int v) {
+  return (unsigned int)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ unsigned int wave_min_to_lane63(unsigned int x) {
+  x = min(x, bbox_dpp<0xB1, 0xF>(x));    // quad_perm [1, 0, 3, 2]
+  x = min(x, bbox_dpp<0x4E, 0xF>(x));    // quad_perm [2, 3, 0, 1]
+  x = min(x, bbox_dpp<0x141, 0xF>(x));   // row_half_mirror
+  x = min(x, bbox_dpp<0x140, 0xF>(x));   // row_mirror: every lane of a row of 16 holds the row's minimum
+  x = min(x, bbox_dpp<0x142, 0xA>(x));   // row_bcast15 into rows 1 and 3
+  x = min(x, bbox_dpp<0x143, 0xC>(x));   // row_bcast31 into rows 2 and 3
+  return x;
+}
+__device__ __forceinline__ unsigned int wave_max_to_lane63(unsigned int x) {
+  x = max(x, bbox_dpp<0xB1, 0xF>(x));
+  x = max(x, bbox_dpp<0x4E, 0xF>(x));
+  x = max(x, bbox_dpp<0x141, 0xF>(x));
+  x = max(x, bbox_dpp<0x140, 0xF>(x));
+  x = max(x, bbox_dpp<0x142, 0xA>(x));
+  x = max(x, bbox_dpp<0x143, 0xC>(x));
+  return x;
+}
+// Bounding box of the points a 256-lane workgroup holds (non-finite points excluded; order-preserving uints): DPP reduction per
+// wavefront + LDS; afterwards lanes 0..2 hold the min / max of axis threadIdx.x in lo[0] / hi[0].  Every lane must call it.
 __device__ __forceinline__ void block_bbox_reduce(unsigned int (&lo)[3], unsigned int (&hi)[3]) {
   __shared__ unsigned int s_lo[4][3], s_hi[4][3];
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    for (int off = 32; off > 0; off >>= 1) {
-      unsigned int x = __shfl_xor(lo[a], off), y = __shfl_xor(hi[a], off);
-      lo[a] = min(lo[a], x);
-      hi[a] = max(hi[a], y);
-    }
+    lo[a] = wave_min_to_lane63(lo[a]);
+    hi[a] = wave_max_to_lane63(hi[a]);
   }
   const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
+  if ((threadIdx.x & 63) == 63) {
 #pragma unroll
     for (int a = 0; a < 3; a++) { s_lo[wave][a] = lo[a]; s_hi[wave][a] = hi[a]; }
   }
@@ -232,14 +297,32 @@ __device__ __forceinline__ unsigned int voxel_rank(unsigned long long key, unsig
 // its member entry, and the smallest index among the later arrivals (atomicMin).  The voxel's owner - its first point in input
 // order - is min(creator, `first`), which the emit launch evaluates when every point has arrived; it also puts the members in
 // input order.  (Round 3: CAS + atomicMin per point here and a launch of its own, k_vhash_link, to collect the members.)
-__device__ __forceinline__ void vh_insert(const VhTable& tb, unsigned long long key, int i) {
-  unsigned int slot = (unsigned int)vh_mix(key) & tb.mask;
+// In two halves, so that a caller can put work of its own between the issue of the first CAS and the use of its result (the de-skew
+// kernels: the bounding-box reduction runs while the atomic travels): vh_insert_begin issues the CAS on the key's home slot,
+// vh_insert_end takes its outcome and does everything else.  The atomics a point performs, and their order, are those of the one loop.
+struct VhPending {
+  unsigned long long key, prev;
+  unsigned int slot;
+  bool active;  // false: nothing was issued (a non-finite point, another rank's voxel, a lane without a point)
+};
+__device__ __forceinline__ VhPending vh_insert_begin(const VhTable& tb, unsigned long long key) {
+  VhPending pd;
+  pd.key = key;
+  pd.slot = (unsigned int)vh_mix(key) & tb.mask;
+  pd.prev = atomicCAS(&tb.slots[pd.slot].key, ~0ull, key);
+  pd.active = true;
+  return pd;
+}
+__device__ __forceinline__ void vh_insert_end(const VhTable& tb, const VhPending& pd, int i) {
+  const unsigned long long key = pd.key;
+  unsigned int slot = pd.slot;
+  unsigned long long prev = pd.prev;
   bool created;
   for (;;) {  // the table has four times as many slots as there are points: a free slot always turns up
-    const unsigned long long prev = atomicCAS(&tb.slots[slot].key, ~0ull, key);
     created = prev == ~0ull;
     if (created || prev == key) break;
     slot = (slot + 1u) & tb.mask;
+    prev = atomicCAS(&tb.slots[slot].key, ~0ull, key);
   }
   VhSlot* s = tb.slots + slot;
   if (created) {
@@ -257,12 +340,18 @@ __device__ __forceinline__ void vh_insert(const VhTable& tb, unsigned long long 
   }
   tb.slot_of[i] = slot;
 }
+__device__ __forceinline__ void vh_insert(const VhTable& tb, unsigned long long key, int i) { vh_insert_end(tb, vh_insert_begin(tb, key), i); }
 // The insert of the fused form.  The grid PCL lays over the cloud starts at the cloud's bounding box, which is only known when
 // every point has been de-skewed - but which points share a voxel is not: floor(x / leaf) decides it (PCL's index is
 // floor(x * inv_leaf) - min_b, the same classes).  So the table is keyed by the absolute voxel coordinates (three 21-bit fields
 // around a bias of 2^20: +- 52 km at a 5 cm leaf), and the PCL index of a voxel - the key the output is ordered by on the host -
 // is computed by k_vhash_emit<true>, which knows the box.  A point outside the 21-bit range is a voxel of its own.
-__device__ __forceinline__ void vhash_insert_abs(const float4 P, int i, float leaf, const VhTable& tb) {
+// Two halves like vh_insert: _begin issues the point's first CAS (`has_point` false: a lane beyond the scan, nothing happens), _end
+// settles it.  Every lane of the workgroup may call both.
+__device__ __forceinline__ VhPending vhash_insert_abs_begin(const float4 P, int i, bool has_point, float leaf, const VhTable& tb) {
+  VhPending pd;
+  pd.key = 0ull; pd.prev = 0ull; pd.slot = 0u; pd.active = false;
+  if (!has_point) return pd;
   if (isfinite(P.x) && isfinite(P.y) && isfinite(P.z)) {  // (non-finite points are dropped, as PCL drops them)
     const float inv_leaf = 1.0f / leaf;
     const float fx = floorf(P.x * inv_leaf), fy = floorf(P.y * inv_leaf), fz = floorf(P.z * inv_leaf);
@@ -273,14 +362,13 @@ __device__ __forceinline__ void vhash_insert_abs(const float4 P, int i, float le
     } else {
       key = (1ull << 63) | (unsigned long long)(unsigned)i;
     }
-    if (tb.part_world > 1u && voxel_rank(key, tb.part_world) != tb.part_rank) {  // another rank's voxel
-      tb.slot_of[i] = kVhEmpty;
-      return;
-    }
-    vh_insert(tb, key, i);
-    return;
+    if (!(tb.part_world > 1u && voxel_rank(key, tb.part_world) != tb.part_rank)) return vh_insert_begin(tb, key);  // (else: another rank's voxel)
   }
   tb.slot_of[i] = kVhEmpty;
+  return pd;
+}
+__device__ __forceinline__ void vhash_insert_abs_end(const VhPending& pd, int i, const VhTable& tb) {
+  if (pd.active) vh_insert_end(tb, pd, i);
 }
 
 // What the two de-skew kernels share.  `in` is the scan as it arrived - the caller's device buffer (lii_scan_job::scan_dev:
@@ -354,9 +442,11 @@ __global__ __launch_bounds__(256) void k_deskew_imu(DeskewIo io, UndistArg u, in
   gap_trace(io);
   if ((int)blockIdx.x == n_scan_blocks) { pull_ctrl(io); return; }
   const double* __restrict__ poses = KP > 0 ? tab.v : poses_g;
+  LII_FT_BEGIN();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = i < io.n;
   float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
+  LII_FT_W(1);
   deskew_imu_point<FUSE>(io, u, K, poses, (int)blockIdx.x, i, in_range, P);
 }
 // The form behind k_imu_propagate (lii_imu.hip; lii_scan_register_imu): end pose, extrinsic, number of poses and the table come from
@@ -364,12 +454,19 @@ __global__ __launch_bounds__(256) void k_deskew_imu(DeskewIo io, UndistArg u, in
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_deskew_imu_dev(DeskewIo io, const UndistArg* __restrict__ u_g, const int* __restrict__ k_g, const double* __restrict__ poses_g) {
   gap_trace(io);
+  LII_FT_BEGIN();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = i < io.n;
   float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
   const UndistArg u = *u_g;
   const int K = *k_g;
+  LII_FT_W(1);
   deskew_imu_point<FUSE>(io, u, K, poses_g, (int)blockIdx.x, i, in_range, P);
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane /* uniform */) {
+  const long long b = __double_as_longlong(v);
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)b, lane), hi = (unsigned int)__builtin_amdgcn_readlane((int)(b >> 32), lane);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 template <bool FUSE>
 __device__ __forceinline__ void deskew_imu_point(const DeskewIo& io, const UndistArg& u, int K, const double* __restrict__ poses, int row, int i, bool in_range,
@@ -382,17 +479,43 @@ __device__ __forceinline__ void deskew_imu_point(const DeskewIo& io, const Undis
     if ((int)threadIdx.x < K) s_time[threadIdx.x] = poses[22 * threadIdx.x];
     __syncthreads();
   }
+  LII_FT(2);
   bool moved = false;
+  const double t = P.w / double(1000);
+  // The head of a WAVEFRONT.  The head of a time is the last k <= K - 2 with time > s_time[k]: the highest bit of a ballot in which lane k
+  // holds pose k's time (tables of up to 65 poses).  It does not decrease as the time grows, so where the wavefront's first and last
+  // point have the same head and every point's time lies between theirs - the scans arrive time-sorted: all but the few wavefronts
+  // that straddle a pose time - that head is every point's, found with one LDS read instead of a walk of up to K - 1 dependent ones.
+  // Any other wavefront (a pose time inside it, points out of order, a time that is not a number) walks as before.
+  int h = -1;
+  bool wave_head = false;
+  if (staged && K >= 2 && K <= 65) {  // (uniform)
+    const int lane = threadIdx.x & 63;
+    const unsigned long long have = __ballot(in_range);
+    if (have != 0ull) {
+      const int l_first = __ffsll((long long)have) - 1, l_last = 63 - __clzll((long long)have);
+      const double t_first = readlane_f64(t, l_first), t_last = readlane_f64(t, l_last);
+      const bool pose_lane = lane <= K - 2;
+      const double tk = s_time[pose_lane ? lane : 0];
+      const unsigned long long b_first = __ballot(pose_lane && t_first > tk), b_last = __ballot(pose_lane && t_last > tk);
+      const bool between = !in_range || (t >= t_first && t <= t_last);
+      if (b_first == b_last && __all(between)) {
+        wave_head = true;
+        h = b_last != 0ull ? 63 - __clzll((long long)b_last) : -1;
+      }
+    }
+  }
   if (in_range) {
-    double t = P.w / double(1000);
-    int h = -1;
-    if (staged) {
+    if (wave_head) {
+      // (taken)
+    } else if (staged) {
       for (int k = K - 2; k >= 0; k--)
         if (t > s_time[k]) { h = k; break; }
     } else {
       for (int k = K - 2; k >= 0; k--)
         if (t > poses[22 * k]) { h = k; break; }
     }
+    LII_FT(3);
     if (h >= 0) {
       double p[3] = {P.x, P.y, P.z};
       backprop_once(poses + 22 * h, t, u, p);
@@ -409,10 +532,18 @@ __device__ __forceinline__ void deskew_imu_point(const DeskewIo& io, const Undis
       P = make_float4((float)p[0], (float)p[1], (float)p[2], P.w);
       moved = true;
     }
+    LII_FT(4);
     if (moved || io.in != io.out) io.out[i] = P;
   }
+  // the point's CAS goes out first: the box reduction runs while the atomic travels to the memory side and back
+  VhPending pd;
+  if (FUSE) pd = vhash_insert_abs_begin(P, i, in_range, io.leaf, io.tb);
   deskew_bbox(P, in_range, io.bbox_rows, row);
-  if (FUSE && in_range) vhash_insert_abs(P, i, io.leaf, io.tb);
+  LII_FT(5);
+  if (FUSE) vhash_insert_abs_end(pd, i, io.tb);
+  LII_FT_W(6);
+  LII_FT(7);
+  LII_FT_END(0);
 }
 
 // The pre-armed form (lii_launch.h: DeskewGate).  Every workgroup requests its point, then one lane polls the tag of the record's first
@@ -450,11 +581,26 @@ __global__ __launch_bounds__(256) void k_deskew_imu_gated(DeskewIo io, DeskewGat
       if (gate_wg) {
         const unsigned long long w = gate_load_u64(&gate.host->word);
         if (w == cancel) { verdict = cancel; break; }
-        if (w == armed && (spins & 31u) == 0u && wall_clock64() - t0 > gate.timeout_ticks) {
-          // nobody came: EXPIRED - unless the host moves the word in this very moment, then its verdict stands (GO: the record follows)
-          unsigned long long expect = armed;
-          if (__hip_atomic_compare_exchange_strong(&gate.host->word, &expect, (gate.seq << 2) | kGateExpired, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE,
-                                                   __HIP_MEMORY_SCOPE_SYSTEM) || expect == cancel) { verdict = cancel; break; }
+        if ((spins & 31u) == 0u) {
+          // The wait is bounded WHATEVER the word holds.  A word of another sequence number is neither `cancel` nor `armed`: the host has
+          // moved on to a later launch and will never write this one's record - and a word of this launch that is not `armed` any more
+          // (the host's GO: it can only come while the word is armed, so before the bound) gets the bound once more for its record, which
+          // the host writes right behind the GO.  Either way: one more look at the record's tag (a record that arrived in this very
+          // moment stands), then the launch ends as a cancelled one.
+          const long long waited = wall_clock64() - t0;
+          const bool foreign = (w >> 2) != gate.seq, overdue = waited > gate.timeout_ticks;
+          if (foreign || (w != armed && waited > 2 * gate.timeout_ticks)) {
+            const unsigned long long t1w = gate_load_u64(gate.rec + 7);
+            if ((t1w & 0x00FFFFFFFFFFFFFFull) == go) { s_k = (int)(t1w >> 56); break; }
+            verdict = cancel;
+            break;
+          }
+          if (overdue && w == armed) {
+            // nobody came: EXPIRED - unless the host moves the word in this very moment, then its verdict stands (GO: the record follows)
+            unsigned long long expect = armed;
+            if (__hip_atomic_compare_exchange_strong(&gate.host->word, &expect, (gate.seq << 2) | kGateExpired, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE,
+                                                     __HIP_MEMORY_SCOPE_SYSTEM) || expect == cancel) { verdict = cancel; break; }
+          }
         }
       } else if ((spins & 3u) == 0u) {
         if (gate_load_u64(gate.dev_flag) == cancel) { verdict = cancel; break; }
@@ -464,6 +610,9 @@ __global__ __launch_bounds__(256) void k_deskew_imu_gated(DeskewIo io, DeskewGat
       __builtin_amdgcn_s_sleep(1);
     }
     if (gate_wg && verdict == cancel) __hip_atomic_store(gate.dev_flag, cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#ifdef LII_FRONT_TRACE
+    if (!gate_wg && verdict == go) atomicAdd(&g_front_trace[9], (unsigned long long)(wall_clock64() - t0));
+#endif
     s_verdict = verdict;
     s_bad = 0;
   }
@@ -476,7 +625,9 @@ __global__ __launch_bounds__(256) void k_deskew_imu_gated(DeskewIo io, DeskewGat
     if (io.ctrl_vec > 0) pull_ctrl(io);
     return;
   }
+  LII_FT_BEGIN();
   if (in_range && gate.late_load) P = io.in[i];
+  LII_FT_W(1);
   // the record -> LDS
   const int K = s_k;
   const int n_lines = (25 + 22 * (K < 2 ? 2 : (K > kGateMaxPoses ? kGateMaxPoses : K)) + 6) / 7;
@@ -506,9 +657,11 @@ struct CvArg {
 // shared by the two kernels below.
 template <bool FUSE>
 __device__ __forceinline__ void deskew_cv_point(const DeskewIo& io, const double (&omega)[3], const double (&rv)[3] /* endR^T vel */) {
+  LII_FT_BEGIN();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in_range = i < io.n;
   float4 P = in_range ? io.in[i] : make_float4(0, 0, 0, 0);
+  LII_FT_W(1);
   if (in_range) {
     const bool is_begin = io.sorted ? i == 0 : ((unsigned)(io.extent[0] & 0xFFFFFFFFull) == (unsigned)i);
     if (!is_begin) {
@@ -528,8 +681,15 @@ __device__ __forceinline__ void deskew_cv_point(const DeskewIo& io, const double
       io.out[i] = P;
     }
   }
+  LII_FT(4);
+  VhPending pd;  // (the CAS first, the box reduction in its shadow: deskew_imu_point)
+  if (FUSE) pd = vhash_insert_abs_begin(P, i, in_range, io.leaf, io.tb);
   deskew_bbox(P, in_range, io.bbox_rows);
-  if (FUSE && in_range) vhash_insert_abs(P, i, io.leaf, io.tb);
+  LII_FT(5);
+  if (FUSE) vhash_insert_abs_end(pd, i, io.tb);
+  LII_FT_W(6);
+  LII_FT(7);
+  LII_FT_END(0);
 }
 template <bool FUSE>
 __global__ __launch_bounds__(256) void k_deskew_cv(DeskewIo io, CvArg a) {
@@ -738,6 +898,35 @@ __device__ __forceinline__ void fold_bbox_rows(const unsigned int* __restrict__ 
   if (threadIdx.x < 3) { s_mm[threadIdx.x] = lo[0]; s_mm[3 + threadIdx.x] = hi[0]; }
   __syncthreads();
 }
+// The same fold in two halves (k_vhash_emit): the first two rows of a lane - scans of up to 131 072 points have no more - are REQUESTED
+// with the lane's other loads, and reduced when the result is needed.  min / max: the same box whatever the order.
+// (The request is written as relaxed atomic loads of wavefront scope - ordinary load instructions - because the compiler sinks an
+// ordinary load to its first use, behind the publication: the rows' round trip would then start where the result is needed.)
+struct BoxRows { uint4 a0, b0, a1, b1; };
+__device__ __forceinline__ uint4 box_row_half(const unsigned int* p /* 16-byte aligned */) {
+  const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
+  const unsigned long long u = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT), w = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  return make_uint4((unsigned int)u, (unsigned int)(u >> 32), (unsigned int)w, (unsigned int)(w >> 32));
+}
+__device__ __forceinline__ BoxRows fold_bbox_rows_request(const unsigned int* __restrict__ bbox_rows, int n_rows) {
+  // (n_rows >= 1.  A lane beyond the rows reads the last one again - the box does not change, and no lane waits to choose)
+  BoxRows q;
+  const int r0 = min((int)threadIdx.x, n_rows - 1), r1 = min((int)threadIdx.x + 256, n_rows - 1);
+  q.a0 = box_row_half(bbox_rows + r0 * 8); q.b0 = box_row_half(bbox_rows + r0 * 8 + 4);
+  q.a1 = box_row_half(bbox_rows + r1 * 8); q.b1 = box_row_half(bbox_rows + r1 * 8 + 4);
+  return q;
+}
+__device__ __forceinline__ void fold_bbox_rows_finish(const BoxRows& q, const unsigned int* __restrict__ bbox_rows, int n_rows, unsigned int* s_mm /*[8] LDS*/) {
+  unsigned int lo[3] = {min(q.a0.x, q.a1.x), min(q.a0.y, q.a1.y), min(q.a0.z, q.a1.z)}, hi[3] = {max(q.b0.x, q.b1.x), max(q.b0.y, q.b1.y), max(q.b0.z, q.b1.z)};
+  for (int r = threadIdx.x + 512; r < n_rows; r += 256) {
+    const uint4 a = *reinterpret_cast<const uint4*>(bbox_rows + r * 8), b = *reinterpret_cast<const uint4*>(bbox_rows + r * 8 + 4);
+    lo[0] = min(lo[0], a.x); lo[1] = min(lo[1], a.y); lo[2] = min(lo[2], a.z);
+    hi[0] = max(hi[0], b.x); hi[1] = max(hi[1], b.y); hi[2] = max(hi[2], b.z);
+  }
+  block_bbox_reduce(lo, hi);
+  if (threadIdx.x < 3) { s_mm[threadIdx.x] = lo[0]; s_mm[3 + threadIdx.x] = hi[0]; }
+  __syncthreads();
+}
 __global__ __launch_bounds__(256) void k_vhash_insert(const float4* __restrict__ pts, int n, const unsigned int* __restrict__ mm,
                                                       const unsigned int* __restrict__ bbox_rows, int n_rows, float leaf,
                                                       VhTable tb, int* __restrict__ filtered) {
@@ -791,19 +980,29 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
                                                     int n_rows, float leaf, int* __restrict__ filtered, int test_late,
                                                     const float* __restrict__ inten, float* __restrict__ inten_out) {
   __shared__ unsigned int s_w[4], s_sum[12];
+  LII_FT_BEGIN();
   const int tid = threadIdx.x, i = blockIdx.x * blockDim.x + tid;
   // everything a lane needs of its own point is requested at once: the point, its slot, and (dependent) the slot's line
   const bool in_range = i < n;
   const float4 p0 = in_range ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   const unsigned int slot = in_range ? tb.slot_of[i] : kVhEmpty;
   const float q0 = (INT && in_range) ? inten[i] : 0.f;
+  // ABS: the box.  Its fold - a reduction over the workgroup, two barriers - is needed for pcl_out and the overflow guard, not for the
+  // ownership, the count or its publication: the rows are requested here with the lane's other loads and folded BEHIND the
+  // publication of the count, which every workgroup above this one waits for.  Two forms need
+  // the box before: a job shared by voxel (ident_part enters `first`) and LII_TEST=emit_late (`hold` reads v.identity): they fold here.
+  __shared__ unsigned int s_mm[8];
+  const bool fold_first = ABS && (tb.part_world > 1u || test_late != 0 || n_rows < 1);  // (uniform)
+  BoxRows box_rows = {};
+  if (ABS && !fold_first) box_rows = fold_bbox_rows_request(bbox_rows, n_rows);
+  LII_FT_W(1);
   VoxelArg v;
   v.identity = 0;
-  if (ABS) {
-    __shared__ unsigned int s_mm[8];
+  if (fold_first) {
     fold_bbox_rows(bbox_rows, n_rows, s_mm);
     v = voxel_prepare(s_mm, leaf);
     if (i == 0) *filtered = v.identity ? 0 : 1;
+    LII_FT(3);
   }
   VhSlot* const sl = tb.slots + (slot != kVhEmpty ? slot : 0u);
   uint4 hd = make_uint4(0u, 0u, kVhEmpty, 0u), m0 = make_uint4(kVhEmpty, kVhEmpty, kVhEmpty, kVhEmpty), m1 = m0;
@@ -821,6 +1020,7 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
     const uint4 c = line[2], d = line[3];  // members 3..6, 7..9 (+ padding)
     m0.w = c.x; m1 = make_uint4(c.y, c.z, c.w, d.x); m2 = make_uint2(d.y, d.z);
   }
+  LII_FT_W(2);
   // (a voxel-partitioned job whose cloud passes unfiltered - PCL's overflow guard - still shares it by voxel: every point of a
   // voxel of this rank leaves on its own)
   const bool ident_part = ABS && v.identity && tb.part_world > 1u;
@@ -832,6 +1032,15 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
   // the workgroups above it have to count its block themselves - the path a launch takes whose workgroups are not all resident.
   const bool hold = test_late != 0 && (blockIdx.x % 7u) == 3u && !(ABS && v.identity && !ident_part);
   if (tid == 0 && !hold) __hip_atomic_store(counts + blockIdx.x, ((unsigned long long)epoch << 32) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  LII_FT(4);
+  // (The words of the workgroups below are NOT requested here: the workgroups publish within a microsecond of each other, a look this
+  // early finds most words missing and pays a second round trip where `base` is needed - measured, 1.5 us per launch, profiles/front_end.md.)
+  if (ABS && !fold_first) {
+    fold_bbox_rows_finish(box_rows, bbox_rows, n_rows, s_mm);
+    v = voxel_prepare(s_mm, leaf);
+    if (i == 0) *filtered = v.identity ? 0 : 1;
+    LII_FT(3);
+  }
   if (ABS && v.identity && !ident_part) {  // (uniform) the cloud passes unfiltered; the voxels' owners still hand their slots back
     if (in_range) { out[i] = p0; pcl_out[i] = (unsigned)i; }
     if (INT && in_range) inten_out[i] = q0;
@@ -910,6 +1119,7 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
     (void)block_rank_of_flag(f, s_w, &tot);
     return tot;
   }).y;
+  LII_FT(6);
   if (hold) {  // (uniform; tests only) the word must be out before ANY lane of this workgroup frees a slot: a helper that recounts this
                // block from freed slots trusts its own count only while the word is missing (prefix_below)
     if (tid == 0) {
@@ -926,25 +1136,28 @@ __global__ __launch_bounds__(256) void k_vhash_emit(const float4* __restrict__ p
     }
     *n_out = n_down;
   }
-  if (!first) return;
-  const unsigned int pos = base + rank;
-  out[pos] = cen;
-  if (INT) inten_out[pos] = cen_i;
-  if (ident_part) {
-    pcl_out[pos] = (unsigned)i;
-  } else if (ABS) {
-    // PCL's index of this voxel, from any of its points (the first): as k_vhash_insert computes it
-    const int i0 = (int)(floorf(p0.x * v.inv_leaf) - (float)v.min_b[0]);
-    const int i1 = (int)(floorf(p0.y * v.inv_leaf) - (float)v.min_b[1]);
-    const int i2 = (int)(floorf(p0.z * v.inv_leaf) - (float)v.min_b[2]);
-    pcl_out[pos] = (unsigned)(i0 * v.mul[0] + i1 * v.mul[1] + i2 * v.mul[2]);
-  } else {
-    pcl_out[pos] = (unsigned int)key;
+  if (first) {
+    const unsigned int pos = base + rank;
+    out[pos] = cen;
+    if (INT) inten_out[pos] = cen_i;
+    if (ident_part) {
+      pcl_out[pos] = (unsigned)i;
+    } else if (ABS) {
+      // PCL's index of this voxel, from any of its points (the first): as k_vhash_insert computes it
+      const int i0 = (int)(floorf(p0.x * v.inv_leaf) - (float)v.min_b[0]);
+      const int i1 = (int)(floorf(p0.y * v.inv_leaf) - (float)v.min_b[1]);
+      const int i2 = (int)(floorf(p0.z * v.inv_leaf) - (float)v.min_b[2]);
+      pcl_out[pos] = (unsigned)(i0 * v.mul[0] + i1 * v.mul[1] + i2 * v.mul[2]);
+    } else {
+      pcl_out[pos] = (unsigned int)key;
+    }
+    // the slot is free again for the next scan
+    uint4* line = reinterpret_cast<uint4*>(sl);
+    line[0] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, kVhEmpty, kVhEmpty);
+    line[1] = make_uint4(0u, kVhEmpty, kVhEmpty, kVhEmpty);
   }
-  // the slot is free again for the next scan
-  uint4* line = reinterpret_cast<uint4*>(sl);
-  line[0] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, kVhEmpty, kVhEmpty);
-  line[1] = make_uint4(0u, kVhEmpty, kVhEmpty, kVhEmpty);
+  LII_FT_W(7);
+  LII_FT_END(16);
 }
 
 // ------------------------------------------------------------------------------------------------
