@@ -557,6 +557,12 @@ __device__ __forceinline__ void knn_fallback_wave(const GridView& g, float wx, f
   }
   LII_FB_TS(fb_t1);
   const float bound1 = fminf(od[4], bound0);  // exact 5th distance over the inner cells (inf if they hold fewer than 5)
+  // What a far candidate must stay BELOW: a fifth distance that exists (dist < q.top().dist, ikd_Tree.cpp:842).  Where no list has five
+  // entries yet the bound is max_d2 itself, and Nearest_Search takes a point AT max_d2 (dist <= max_dist): the candidates' own test
+  // d <= max_d2 is the only one then.  (With `d < bound1` alone a fifth neighbour at exactly 5 m^2 was dropped: tests/test_gpu_plane_rows.py,
+  // family I.)  Left open on purpose: a fifth distance that exists and IS max_d2 also lifts the bound, so far candidates tied with it at
+  // exactly max_d2 enter the selection - a tie across the 5th / 6th place, which the tree decides by its visiting order and nobody reproduces.
+  const float cand_bound = bound1 < g.max_d2 ? bound1 : __builtin_inff();
   // pass 2: the rest of the cube around the ball of radius sqrt(bound1) (nothing farther can enter the list), pruned with bound1
   const float r1 = fminf(r0, sqrtf(bound1) + 2.f * eps);
   int ix0 = cell_of(wx - r1, g.inv_cs), ix1 = cell_of(wx + r1, g.inv_cs);
@@ -641,7 +647,7 @@ __device__ __forceinline__ void knn_fallback_wave(const GridView& g, float wx, f
           rr[2 * tt] = act[2 * tt] ? make_uint2(v[tt].x, v[tt].y) : make_uint2(0u, 0u);
           rr[2 * tt + 1] = act[2 * tt + 1] ? make_uint2(v[tt].z, v[tt].w) : make_uint2(0u, 0u);
         }
-        far_list_trip<2 * NVP>(g, far_list, n_far, rr, wx, wy, wz, bound1, k);
+        far_list_trip<2 * NVP>(g, far_list, n_far, rr, wx, wy, wz, cand_bound, k);
       }
     }
   } else if (nparts > 1 && part != 0) {
@@ -704,7 +710,7 @@ __device__ __forceinline__ void knn_fallback_wave(const GridView& g, float wx, f
 #ifdef LII_FALLBACK_TRACE
         const long long fb_c = wall_clock64();
 #endif
-        far_list_trip<2 * NV>(g, far_list, n_far, rr, wx, wy, wz, bound1, k);
+        far_list_trip<2 * NV>(g, far_list, n_far, rr, wx, wy, wz, cand_bound, k);
 #ifdef LII_FALLBACK_TRACE
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         fb_tr += wall_clock64() - fb_c;
@@ -737,7 +743,7 @@ __device__ __forceinline__ void knn_fallback_wave(const GridView& g, float wx, f
         rr[b] = g.cells[(size_t)id * kBlockCells + local];
       }
     }
-    far_list_trip<NB>(g, far_list, n_far, rr, wx, wy, wz, bound1, k);
+    far_list_trip<NB>(g, far_list, n_far, rr, wx, wy, wz, cand_bound, k);
   }
   } else {
   // Which cells survive (inside the ball, outside the inner cube, closer than bound1) does not depend on the candidates found on
@@ -779,12 +785,12 @@ __device__ __forceinline__ void knn_fallback_wave(const GridView& g, float wx, f
       for (int b = 0; b < NB; b++) rr[b] = g.cells[ci[b]];
 #pragma unroll
       for (int b = 0; b < NB; b++) rr[b] = act[b] ? rr[b] : make_uint2(0u, 0u);
-      far_list_trip<NB>(g, far_list, n_far, rr, wx, wy, wz, bound1, k);
+      far_list_trip<NB>(g, far_list, n_far, rr, wx, wy, wz, cand_bound, k);
     }
   }
   }
   LII_FB_TS(fb_t2);
-  far_list_scan(g, far_list, n_far, wx, wy, wz, bound1, k);
+  far_list_scan(g, far_list, n_far, wx, wy, wz, cand_bound, k);
   LII_FB_TS(fb_t3);
   wave_select5(k, od, oi);
 #ifdef LII_FALLBACK_TRACE

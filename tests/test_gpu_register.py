@@ -1,8 +1,9 @@
 """GPU parity of one registration pass (k_knn_ck + k_fit_reduce + k_reduce91) and of the full iterated update
 against the oracle, through the C-ABI.  Tolerances (stated per SURVEY.md Appendix B):
   * neighbour lists: BIT-EXACT (same 5 points, same float32 squared distances, same order);
-  * selected set: identical except at 1-ulp threshold flips (Jaccard >= 0.999);
-  * H^T R^-1 H / H^T R^-1 z: relative 1e-9 when the selected sets are identical;
+  * selected set: identical on the three scans of test_iterate_matches_oracle (asserted); in general identical except at 1-ulp
+    threshold flips (Jaccard >= 0.999);
+  * H^T R^-1 H / H^T R^-1 z: relative 1e-9, always compared (single points are held far tighter by tests/test_gpu_plane_rows.py);
   * final pose of the update: |dp| <= 1e-6 m, |dtheta| <= 1e-7 rad.
 """
 import numpy as np
@@ -63,17 +64,19 @@ def test_iterate_matches_oracle(reg, oracle, small_world, sensor, imu_en):
     inter = np.logical_and(sel, ref["selected"]).sum()
     union = np.logical_or(sel, ref["selected"]).sum()
     assert inter / union >= 0.999
-    if inter == union:
-        assert int(out[90]) == int(ref["out91"][90])
-        assert _rel(out[:90], ref["out91"][:90]) < 1e-9
+    # (measured on the MI355X, profiles/plane_rows.md: on all three scans every selection flag equals the oracle's, in both passes - the
+    # sums were compared only behind `if inter == union`, which a single flipped flag would have skipped without a word)
+    assert inter == union
+    assert int(out[90]) == int(ref["out91"][90])
+    assert _rel(out[:90], ref["out91"][:90]) < 1e-9
     # a second, non-search pass at a moved pose must reuse the cached planes and the sticky selection
     st2 = oracle.state_boxplus(st, np.r_[0.001, -0.002, 0.0015, 0.01, -0.005, 0.004, np.zeros(18)])
     ref2 = tree.iterate_once(scan, st2, search=False, imu_en=imu_en, threads=4, selected=ref["selected"])
     out2 = reg.iekf_iterate(lii.State(st2), False, imu_en)
     _, _, sel2 = reg.neighbors(n)
-    if inter == union and np.array_equal(sel2, ref2["selected"]):
-        assert _rel(out2[:90], ref2["out91"][:90]) < 1e-9
-    assert np.logical_xor(sel2, ref2["selected"]).sum() <= max(2, int(0.001 * n))
+    assert np.array_equal(sel2, ref2["selected"])
+    assert int(out2[90]) == int(ref2["out91"][90])
+    assert _rel(out2[:90], ref2["out91"][:90]) < 1e-9
 
 
 @pytest.mark.parametrize("imu_en,max_it", [(False, 4), (True, 5)])

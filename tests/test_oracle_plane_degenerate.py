@@ -11,8 +11,10 @@ from fractions import Fraction
 import numpy as np
 
 
-def colpiv_qr_solve_numpy(A, b):
-    """Eigen 3.3 ColPivHouseholderQR(A).solve(b), written with numpy vectors (rows x cols = 5 x 3)."""
+def colpiv_qr_solve_numpy(A, b, diag=None):
+    """Eigen 3.3 ColPivHouseholderQR(A).solve(b), written with numpy vectors (rows x cols = 5 x 3).  `diag`, a dict, receives which
+    branches ran: nonzero_pivots, perm (the pivot order), tau0 (a reflector with tau = 0), renorm (a column norm computed afresh)."""
+    tau0 = renorm = False
     qr = np.array(A, np.float64)
     rows, cols = qr.shape
     eps = np.finfo(np.float64).eps
@@ -36,6 +38,7 @@ def colpiv_qr_solve_numpy(A, b):
         tail = float(x[1:] @ x[1:])
         if tail <= np.finfo(np.float64).tiny:
             tau, beta, v = 0.0, x[0], np.r_[1.0, np.zeros(len(x) - 1)]
+            tau0 = True
         else:
             beta = -np.copysign(np.sqrt(x[0] * x[0] + tail), x[0]) if x[0] != 0 else -np.sqrt(tail)
             v = np.r_[1.0, x[1:] / (x[0] - beta)]
@@ -52,6 +55,7 @@ def colpiv_qr_solve_numpy(A, b):
                 t = max((1 + t) * (1 - t), 0.0)
                 if t * (upd[j] / direct[j]) ** 2 <= downdate:
                     direct[j] = upd[j] = np.linalg.norm(qr[k + 1:, j])
+                    renorm = True
                 else:
                     upd[j] *= np.sqrt(t)
     for k in range(nz):
@@ -64,6 +68,8 @@ def colpiv_qr_solve_numpy(A, b):
     x = np.zeros(cols)
     for i in range(nz):
         x[perm[i]] = y[i]
+    if diag is not None:
+        diag.update(nonzero_pivots=nz, perm=tuple(perm), tau0=tau0, renorm=renorm)
     return x, nz
 
 
