@@ -740,6 +740,83 @@ int lii_publish_saved(lii_handle h, float* out_float4, int32_t capacity, int32_t
 int lii_publish_fetch_intensity(lii_handle h, int32_t cloud, const float** host_float, const void** dev_float, int32_t* n);
 int lii_publish_saved_intensity(lii_handle h, float* out, int32_t capacity, int32_t* n);
 
+/* ---------------------------------------------------------------- the registered clouds as message bytes (pcl::toROSMsg / writeBinary)
+ * The reference ends every scan with pcl::toROSMsg(*laserCloudWorld, msg) (src/laserMapping.cpp:578-586, :619, :632) and, every
+ * pcd_save/interval scans, pcd_writer.writeBinary (:609).  lii_publish_wire_set places a SECOND STANDING ORDER beside lii_publish_set: the
+ * same publish launch also forms each ordered cloud as the bytes of sensor_msgs/PointCloud2::data - records of pcl::PointXYZINormal,
+ * point_step 48, little endian, twelve 32-bit words:
+ *   word   0 1 2     3             4 5 6                         7     8          9          10 11
+ *   field  x y z     pad data[3]   normal_x normal_y normal_z    pad   intensity  curvature  pad
+ * msg.fields as pcl::toROSMsg writes them: x 0, y 4, z 8, normal_x 16, normal_y 20, normal_z 24, intensity 32, curvature 36 - all
+ * FLOAT32 (datatype 7), count 1 (lii_publish_wire_layout hands the table out).  Contents, restating publish_frame_world :561-586 with
+ * pointBodyToWorld :209-220, publish_frame_body :616-623 and publish_effect_world :625-636:
+ *   LII_PUB_DENSE, LII_PUB_DOWN  laserCloudWorld is a cloud of default-constructed points of which pointBodyToWorld sets x, y, z and the
+ *                   intensity only: x, y, z the world coordinates (the bits lii_publish_fetch gives), word 3 = 1.0f, words 4 - 7 = +0.0f,
+ *                   intensity that of the scan (DENSE) or the voxel's mean (DOWN) where the registered scan carries intensities,
+ *                   +0.0f where it does not; CURVATURE +0.0f - the time is NOT copied: the float4 clouds remain the place to get
+ *                   t_ms; words 10 - 11 = 0.
+ *   LII_PUB_EFFECT  as DOWN over the selected points, in the order of the float4 effect cloud; the intensity of every point is
+ *                   (float)sqrt(1000.0) (:1050-1051: sqrt(R_inv)), whatever the scan carries - this form delivers the channel
+ *                   lii_publish_fetch_intensity refuses.
+ *   LII_PUB_BODY    feats_undistort as it is: x, y, z the de-skewed coordinates, word 3 = 1.0f, normals 0, intensity as for DENSE,
+ *                   CURVATURE = t_ms, words 10 - 11 = 0.
+ * The normals are 0 because every handler the library serves writes 0 there (src/preprocess.cpp:143-145 and siblings); the colours
+ * the L515 handler puts into them (:470-472) are not carried, as everywhere else in the library.  Every zero word is 0x00000000.
+ * NOT PINNED BY A BUILD: the pad values (1.0f in word 3 - PCL's PCL_ADD_POINT4D constructor -, zeros elsewhere) and the binary PCD
+ * layout below are restated from knowledge of PCL's point_types.hpp and pcd_io.hpp; no PCL was available to run against (as
+ * SURVEY.md Appendix B says of VoxelGrid).
+ *   lii_publish_wire_set    clouds: a set of LII_PUB_DENSE | DOWN | EFFECT | BODY; off by default; NULL or clouds == 0: off.
+ *                      INDEPENDENT of lii_publish_set - either order may be on alone, or both: an update enqueues ONE publish launch
+ *                      either way (LII_KP_PUBLISH counts as before).  Buffers: two deep, 48 * max_scan_points bytes each, for the
+ *                      ordered clouds only; with to_host they travel to pinned memory on the copy stream behind events of their own.
+ *                      Bad struct_size, unknown bits (LII_PUB_INTENSITY is one here: the records always have the field), to_host
+ *                      other than 0 / 1, reserved != 0: LII_ERR_INVALID.  A communicator attached, LII_TEST=host_solve, or a call from
+ *                      while_waiting: LII_ERR_STATE.  PLACING OR CHANGING EITHER ORDER (lii_publish_set, lii_publish_wire_set) FORGETS THE
+ *                      CLOUDS OF EARLIER REGISTRATIONS FOR BOTH: the fetches answer LII_ERR_STATE until the next registration.
+ *   lii_publish_wire_fetch  the counterpart of lii_publish_fetch: *host_bytes (NULL without to_host) / *dev_bytes, 48 * *n_points
+ *                      bytes, of the last finished registration (or lii_publish_now, which honours this order as the other); the same
+ *                      lifetime (until the registration after the next one begins), waits for that cloud's event only, MAY BE CALLED
+ *                      FROM while_waiting; the same errors.
+ *   lii_publish_wire_layout  host only: point_step, the eight fields and the PCD row size - what fills msg.fields / point_step / row_step.
+ *                      out->struct_size is the caller's sizeof(lii_wire_layout) (another value: LII_ERR_INVALID).
+ *   lii_publish_saved_pcd  the save buffer (lii_publish_opts::save_capacity) as the rows of a binary PCD, as PCDWriter::writeBinary packs
+ *                      the registered fields without padding - 32 bytes: x y z normal_x normal_y normal_z intensity curvature -, repacked
+ *                      ON THE DEVICE from the buffer and its intensities (none kept: 0.0f; normals 0, curvature 0) and brought over
+ *                      through a fixed staging area in chunks of at most 65 536 rows.  *n_points, capacity (here in BYTES: 32 * *n_points
+ *                      needed), clear and the sticky overflow report are those of lii_publish_saved; rows_out == NULL: the count only.
+ *   lii_pcd_header     host only: the text in front of the rows -
+ *                        # .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z normal_x normal_y normal_z intensity curvature\n
+ *                        SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH n\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\n
+ *                        POINTS n\nDATA binary\n
+ *                      - into out (no terminating 0 is counted; one is written if it fits); *len: its length; capacity < *len:
+ *                      LII_ERR_CAPACITY (*len is set); out == NULL: the length only. */
+enum { LII_WIRE_POINT_STEP = 48, LII_WIRE_PCD_ROW = 32, LII_WIRE_FIELDS = 8, LII_WIRE_FLOAT32 = 7 };
+typedef struct lii_wire_opts {
+  uint32_t struct_size;   /* sizeof(lii_wire_opts) */
+  int32_t clouds;         /* LII_PUB_DENSE 1 | LII_PUB_DOWN 2 | LII_PUB_EFFECT 4 | LII_PUB_BODY 8 */
+  int32_t to_host;        /* 1: also copy each cloud's bytes to pinned host memory on the copy stream */
+  int32_t reserved;       /* 0 */
+} lii_wire_opts;
+typedef struct lii_wire_field {
+  char name[16];          /* 0-terminated */
+  int32_t offset;         /* bytes from the start of the record */
+  int32_t datatype;       /* sensor_msgs/PointField: 7 = FLOAT32 */
+  int32_t count;
+  int32_t pcd_offset;     /* bytes from the start of the binary PCD row */
+} lii_wire_field;
+typedef struct lii_wire_layout {
+  uint32_t struct_size;   /* sizeof(lii_wire_layout), set by the caller */
+  int32_t point_step;     /* 48 */
+  int32_t n_fields;       /* 8 */
+  int32_t pcd_row_bytes;  /* 32 */
+  lii_wire_field fields[8];
+} lii_wire_layout;
+int lii_publish_wire_set(lii_handle h, const lii_wire_opts* opts);
+int lii_publish_wire_fetch(lii_handle h, int32_t cloud, const void** host_bytes, const void** dev_bytes, int32_t* n_points);
+int lii_publish_wire_layout(lii_wire_layout* out);
+int lii_publish_saved_pcd(lii_handle h, void* rows_out, int64_t capacity_bytes, int32_t* n_points, int32_t clear);
+int lii_pcd_header(int32_t n_points, char* out, int32_t capacity, int32_t* len);
+
 /* ---------------------------------------------------------------- LI-Init batch calibration evaluators
  * CalibState record (include/LI_init/LI_init.h:31-89). */
 typedef struct lii_calib_state {

@@ -66,6 +66,19 @@ class lii_publish_opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("clouds", C.c_int32), ("to_host", C.c_int32), ("save_capacity", C.c_int32)]
 
 
+class lii_wire_opts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("clouds", C.c_int32), ("to_host", C.c_int32), ("reserved", C.c_int32)]
+
+
+class lii_wire_field(C.Structure):
+    _fields_ = [("name", C.c_char * 16), ("offset", C.c_int32), ("datatype", C.c_int32), ("count", C.c_int32), ("pcd_offset", C.c_int32)]
+
+
+class lii_wire_layout(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("point_step", C.c_int32), ("n_fields", C.c_int32), ("pcd_row_bytes", C.c_int32),
+                ("fields", lii_wire_field * 8)]
+
+
 class lii_local_map_opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_int32), ("cube_len", C.c_double), ("det_range", C.c_float),
                 ("reserved", C.c_int32)]
@@ -210,6 +223,11 @@ _DECLS = {
     "lii_publish_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "lii_publish_fetch_intensity": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "lii_publish_saved_intensity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_publish_wire_set": (C.c_int, [C.c_void_p, C.POINTER(lii_wire_opts)]),
+    "lii_publish_wire_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "lii_publish_wire_layout": (C.c_int, [C.POINTER(lii_wire_layout)]),
+    "lii_publish_saved_pcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
+    "lii_pcd_header": (C.c_int, [C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_scan_intensity_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_intensity_set_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "lii_ingest_set_intensity": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -301,6 +319,27 @@ def _ptr(a):
     # the raw address (ctypes converts an int for a c_void_p parameter); ndarray.ctypes.data_as() is two orders of
     # magnitude slower once a large framework is loaded in the process (measured: 60 us per call next to torch)
     return a.__array_interface__["data"][0]
+
+
+def wire_layout():
+    """lii_publish_wire_layout (host only): dict(point_step, pcd_row_bytes, fields=[(name, offset, datatype, count, pcd_offset), ...]) -
+    what fills msg.fields, msg.point_step and msg.row_step of a PointCloud2 made of publish_wire_fetch's bytes."""
+    lay = lii_wire_layout(struct_size=C.sizeof(lii_wire_layout))
+    rc = load_library().lii_publish_wire_layout(C.byref(lay))
+    if rc != 0:
+        raise LIIError(rc, "lii_publish_wire_layout")
+    return dict(point_step=lay.point_step, pcd_row_bytes=lay.pcd_row_bytes,
+                fields=[(f.name.decode(), f.offset, f.datatype, f.count, f.pcd_offset) for f in lay.fields[:lay.n_fields]])
+
+
+def pcd_header(n_points):
+    """lii_pcd_header (host only): the text in front of publish_saved_pcd's rows, as bytes."""
+    n = C.c_int32(0)
+    buf = C.create_string_buffer(512)
+    rc = load_library().lii_pcd_header(int(n_points), buf, len(buf), C.byref(n))
+    if rc != 0:
+        raise LIIError(rc, "lii_pcd_header")
+    return buf.raw[:n.value]
 
 
 def _dev_address(a):
@@ -1000,6 +1039,51 @@ class Registrar:
         out = np.zeros((max(n.value, 1), 4), np.float32)
         self._check(self.L.lii_publish_saved(self.h, _ptr(out), len(out), C.byref(n), int(bool(clear))))
         return out[:n.value]
+
+    # ------------------------------------------------------------------ ... as message bytes (pcl::toROSMsg / PCDWriter::writeBinary)
+    def publish_wire_set(self, clouds=0, to_host=False):
+        """The second standing order (lii_publish_wire_set): the ordered clouds (PUB_DENSE | PUB_DOWN | PUB_EFFECT | PUB_BODY) as the
+        bytes of sensor_msgs/PointCloud2::data, 48-byte pcl::PointXYZINormal records; nothing ordered: off."""
+        if not clouds:
+            self._check(self.L.lii_publish_wire_set(self.h, None))
+            return
+        o = lii_wire_opts(C.sizeof(lii_wire_opts), int(clouds), int(bool(to_host)), 0)
+        self._check(self.L.lii_publish_wire_set(self.h, C.byref(o)))
+
+    def publish_wire_fetch(self, cloud, copy=True):
+        """One cloud of the last finished registration as an (n, 48) uint8 array - msg.data, row for row with publish_fetch(cloud): a
+        view of the library's pinned buffer (to_host; copy=False - valid until the registration after the next one begins) or a copy;
+        without to_host the device buffer is downloaded.  Callable from while_waiting of the next call."""
+        hp, dp, n = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self._check(self.L.lii_publish_wire_fetch(self.h, int(cloud), C.byref(hp), C.byref(dp), C.byref(n)))
+        if n.value == 0:
+            return np.zeros((0, 48), np.uint8)
+        if hp.value:
+            a = np.ctypeslib.as_array(C.cast(hp, C.POINTER(C.c_uint8)), shape=(n.value, 48))
+            return a.copy() if copy else a
+        import torch  # (device only: the buffer is read through torch, the project's plumbing)
+        return torch.as_tensor(_DeviceFloat(dp.value, 12 * n.value), device="cuda").cpu().numpy().view(np.uint8).reshape(n.value, 48).copy()
+
+    def publish_saved_pcd(self, clear=False):
+        """The save buffer as the rows of a binary PCD, an (n, 32) uint8 array (x y z normal_x normal_y normal_z intensity curvature),
+        repacked on the device; pcd_header(n) + rows.tobytes() is the file.  LIIError(-4) if a scan did not fit since the last clear."""
+        n = C.c_int32(0)
+        rc = self.L.lii_publish_saved_pcd(self.h, None, 0, C.byref(n), 0)
+        if rc not in (0, -4):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), 32), np.uint8)
+        self._check(self.L.lii_publish_saved_pcd(self.h, _ptr(out), out.nbytes, C.byref(n), int(bool(clear))))
+        return out[:n.value]
+
+    @staticmethod
+    def wire_layout():
+        """lii_publish_wire_layout (host only, no handle): see the module's wire_layout()."""
+        return wire_layout()
+
+    @staticmethod
+    def pcd_header(n_points):
+        """lii_pcd_header (host only, no handle): see the module's pcd_header()."""
+        return pcd_header(n_points)
 
     def neighbors(self, n):
         pts = np.zeros((n, 5, 3), np.float32)

@@ -219,7 +219,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   }
   // lii_publish_set: the registered clouds go out now as well - behind the passes and the map update, in front of a pre-armed prologue.
   // The launch reads the final state from the control block and does nothing if the loop has parked (then it is enqueued again below).
-  if (h->pub.on) { rc = publish_enqueue(h, h->d_ctrl, nullptr, true); if (rc != LII_OK) return rc; }
+  if (h->pub.any()) { rc = publish_enqueue(h, h->d_ctrl, nullptr, true); if (rc != LII_OK) return rc; }
   // THE NEXT SCAN'S PROLOGUE, pre-armed (lii_launch.h: DeskewGate): the job announced the scan the next call will bring - its de-skew +
   // filter-insert launch goes out now, behind this update's passes (and its map update), and waits on the device for the record
   // the next lii_scan_register writes.
@@ -284,7 +284,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     rc = wait_result(true);
     if (rc != LII_OK) return rc;
   }
-  if (h->pub.on && parked_once) {  // (the launch behind the planned passes saw a parked loop and did nothing: once more, behind the passes that ended it)
+  if (h->pub.any() && parked_once) {  // (the launch behind the planned passes saw a parked loop and did nothing: once more, behind the passes that ended it)
     if (h->pub.kp_idx >= 0) h->prof.kp_kind[size_t(h->pub.kp_idx)] = LII_KP_KINDS * 64;  // (lii_set_profiling(h, 3): that launch did not execute)
     rc = publish_enqueue(h, h->d_ctrl, nullptr, false);
     if (rc != LII_OK) return rc;
@@ -299,7 +299,7 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     if (wide) h->wide_scans++;
   }
   h->staging_busy = false;  // the wait above covers everything enqueued before the stopping pass
-  h->scan_buf_idle = !h->pub.on;  // ... every launch that read or wrote the current scan buffer among it (what was enqueued behind - drained passes, the map update, a pre-armed launch on the OTHER buffer - does not touch it;
+  h->scan_buf_idle = !h->pub.any();  // ... every launch that read or wrote the current scan buffer among it (what was enqueued behind - drained passes, the map update, a pre-armed launch on the OTHER buffer - does not touch it;
                                    // the launch and the body copy of a standing lii_publish_set order DO read it behind the stopping pass: with one, lii_scan_upload_next puts its event pair between the streams)
   const IekfResult* hr = h->h_res;
   h->have_search = true;

@@ -331,6 +331,19 @@ struct lii_context {
     int n_scan_at[2] = {0, 0};              // points of the dense / body cloud in the slot
     int clouds_at[2] = {0, 0};              // the clouds the slot holds
     int kp_idx = -1;                        // lii_set_profiling(h, 3): the mark of the launch enqueued behind the planned passes
+    // lii_publish_wire_set: the second standing order - the clouds as 48-byte pcl::PointXYZINormal records, formed by the same launch.
+    // Independent of `on`: either order alone keeps the launch, the slots (cur / have), the counts and the prefix words going.
+    struct Wire {
+      bool on = false;
+      int clouds = 0, to_host = 0;
+      DevBuf<uint4> d_cloud[kClouds][2];     // lii::kWireQuads * max_scan_points each (the ordered ones)
+      PinnedBuf<uint4> h_cloud[kClouds][2];  // to_host: their pinned copies, filled on the copy stream behind the float4 clouds'
+      lii::Event ev_copy[kClouds][2];        // the slot's records have arrived in h_cloud (copy stream)
+      int last_copy[2] = {-1, -1};           // as Publish::last_copy, for these copies
+      int clouds_at[2] = {0, 0};             // the clouds the slot holds as records
+      DevBuf<uint4> d_pcd;                   // lii_publish_saved_pcd: the staging area, 2 * lii::kPcdChunkRows (one chunk of 32-byte rows)
+    } wire;
+    bool any() const { return on || wire.on; }
   } pub;
   // ---- the moving local-map cube (lii_local_map_*, lii_capi_map.cpp; kernels: lii_map.hip, arithmetic: lii_fov.h): durable handle state,
   // off until lii_local_map_set asks for it.  Nothing here exists before the first lii_local_map_set.

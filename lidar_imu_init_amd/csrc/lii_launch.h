@@ -339,8 +339,22 @@ struct PublishArgs {
   const IekfCtrl* guard;    // != nullptr: pose from the control block, and nothing is done unless update `seq` has stopped
   int seq;
   int test_late;            // LII_TEST=emit_late: every seventh workgroup of the down-sampled cloud publishes its word late (as k_vhash_emit / k_map_decide)
+  // lii_publish_wire_set (every pointer nullptr: the launch without it).  The clouds as 48-byte pcl::PointXYZINormal records, three
+  // uint4 each (kWireQuads): w_dense / w_body by the workgroups of the scan, w_down / w_effect by those of the down-sampled cloud.
+  // Intensities of their own, because this order hands them on whether or not the other asks for LII_PUB_INTENSITY: w_scan_int the
+  // scan's, w_body_int the down-sampled cloud's (nullptr: none - the records get +0.0f).
+  uint4* w_dense;
+  uint4* w_body;
+  uint4* w_down;
+  uint4* w_effect;
+  const float* w_scan_int;
+  const float* w_body_int;
 };
+constexpr int kWireQuads = 3;       // a record: 48 bytes = 3 x 16
+constexpr int kPcdChunkRows = 65536;  // lii_publish_saved_pcd's staging area (the chunk of lii_map_delete_points)
 void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s);
+// the save buffer as binary PCD rows (8 floats: x y z 0 0 0 intensity 0): rows [first, first + n) -> out[0, n); inten == nullptr: 0.0f
+void launch_pcd_rows(const float4* save, const float* inten, int first, int n, uint4* out, hipStream_t s);
 
 // rocPRIM wrappers (lii_sort.hip)
 size_t sort_temp_bytes(int max_n);
