@@ -258,6 +258,45 @@ int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_byt
                     float* pts_out /* n*k*3 */, float* d2_out /* n*k */, int32_t* count_out /* n */);
 int lii_map_nearest_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
                         float* pts_dev, float* d2_dev, int32_t* count_dev);
+/* lii_map_radius <- the ball query: upstream ikd-Tree's Radius_Search; in the reference's copy of the tree the idiom
+ *                  Nearest_Search(point, k, Nearest_Points, Point_Distance, max_dist) with k above the ball's population, which
+ *                  lii_map_nearest cannot serve (k <= 64, max_dist >= 1).
+ * Query i (float xyz every stride_bytes, as for lii_map_nearest) receives EVERY live map point with d2 <= max_dist, however many there
+ * are: d2 is the reference's float32 calc_dist (left to right, no FMA), compared as a float against the double max_dist, inclusive -
+ * the rule of lii_map_nearest and of Search (quirk A5); max_dist is a SQUARED distance.  The points stand in rows
+ * offsets[i] .. offsets[i + 1] - 1 of pts (3 floats a row) and d2; offsets[0] = 0, offsets[n] = *total, and *total is ALWAYS the full
+ * count.  The rows of one query come in the library's visiting order - deterministic for a given map state, otherwise unspecified -
+ * or, with LII_RADIUS_SORTED in flags, ascending in d2 (equal d2 in unspecified order).
+ * Any finite max_dist >= 0 is accepted: 0 returns the points at d2 == 0, and there is no lower bound of 1 - a ball query has none of
+ * Nearest_Search's dependence on the shape of the tree, the ball itself is the definition.
+ * LII_ERR_INVALID, nothing written: max_dist NaN, infinite or negative; sqrt(max_dist) > 32 map_cell_size (the ball would span more
+ * cells than a query should walk - create the handle with a larger lii_config::map_cell_size); a bad stride; NULL queries with n > 0;
+ * n < 0; unknown flag bits; NULL offsets or total; a negative capacity (where capacity is read).  No map: LII_ERR_STATE.  n == 0:
+ * LII_OK, offsets[0] = 0, total 0.  A query with a NaN coordinate gets an empty segment; one whose ball leaves the addressable grid
+ * is searched over the cells that exist.  From inside lii_scan_job::while_waiting: LII_ERR_STATE.
+ * Both calls are OBSERVERS in the sense of lii_map_nearest: they end a pre-armed launch and join a map update in flight first; scan,
+ * neighbour lists, cached planes, IMU carry and publish order stay as they are; they work with a communicator attached and under
+ * LII_TEST=host_solve.
+ *   lii_map_radius      host queries, host results, synchronous.  With pts_out == NULL && d2_out == NULL offsets and total only are
+ *                       returned and capacity is ignored.  Otherwise capacity (in rows) < *total is LII_ERR_CAPACITY: offsets and
+ *                       total are written and nothing else is (the rule of lii_map_box_search).  The queries are counted 65 536 at a
+ *                       time and filled in chunks of at most 2^20 rows through the staging of lii_map_nearest, grown geometrically; a
+ *                       single query whose ball holds more rows than a chunk gets a chunk to itself, and the staging grows to hold it
+ *                       (16 bytes a row, device and pinned: never more than 16 bytes x the live map points beyond the 17 MiB).
+ *   lii_map_radius_dev  queries and results in device memory of the caller: enqueued on the handle's stream, returns without waiting.
+ *                       offsets_dev (n + 1 words) and total_dev[0] are always complete; rows with index >= capacity are not written -
+ *                       the caller compares the total with its capacity behind lii_synchronize.  pts_dev / d2_dev may be NULL (both:
+ *                       offsets and total only, capacity ignored).
+ * LII_RADIUS_SORTED sorts (query, d2 bits) per row - a non-negative float orders as its uint32 bits - and gathers the points: 24 bytes
+ * a row of temporary device memory that belongs to the handle and is created by the first sorted call (the device form sorts
+ * `capacity` rows, whatever the total turns out to be: give it the capacity it needs, not a generous bound). */
+enum { LII_RADIUS_SORTED = 1 };
+int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
+                   int64_t* offsets_out /* n + 1, required */, float* pts_out /* capacity x 3, may be NULL */,
+                   float* d2_out /* capacity, may be NULL */, int64_t capacity, int64_t* total /* required */);
+int lii_map_radius_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
+                       int64_t* offsets_dev /* n + 1 */, float* pts_dev, float* d2_dev, int64_t capacity,
+                       int64_t* total_dev /* one word */);
 /* ---- edits and queries by point and box: the rest of what a holder of the tree can do (include/ikd-Tree/ikd_Tree.h:165-187).
  * lii_map_delete_points <- ikdtree.Delete_Points(PointToDel)  (include/ikd-Tree/ikd_Tree.cpp:479-498, Delete_by_point :672-719,
  *                       same_point :1269-1271).  Every listed point (float xyz every stride_bytes, as for lii_map_build) takes ONE live

@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("LII_LIB") or os.path.join(_HERE, "lib", "libliinit_hip.so")
 
 STATE_DOUBLES = 36 + 576
+LII_RADIUS_SORTED = 1  # lii_map_radius flags: every segment ascending in d2
 
 
 class LIIError(RuntimeError):
@@ -172,6 +173,8 @@ _DECLS = {
     "lii_map_commit": (C.c_int, [C.c_void_p]),
     "lii_map_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_nearest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_map_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lii_map_radius_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_scan_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_upload_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_advance": (C.c_int, [C.c_void_p]),
@@ -640,6 +643,37 @@ class Registrar:
         (pts_dev / d2_dev may be None).  Enqueued on the handle's stream; synchronize() - or any synchronous call - orders it."""
         self._check(self.L.lii_map_nearest_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), int(k), float(max_dist),
                                                _dev_address(pts_dev), _dev_address(d2_dev), _dev_address(count_dev)))
+
+    def map_radius(self, q, max_dist, sorted=False, points=True):
+        """The ball query (upstream ikd-Tree's Radius_Search) for the points q (n, >= 3) float: EVERY map point with d2 <= max_dist
+        (the SQUARED distance against max_dist, inclusive), however many there are.  Returns (offsets int64 (n + 1,), pts float32
+        (total, 3), d2 float32 (total,)): the points of query i are rows offsets[i] .. offsets[i + 1] - 1, in the library's visiting
+        order, or ascending in d2 with sorted=True.  points=False: the offsets only (pts and d2 come back empty).  A count-only call,
+        then a call sized by its total.  Leaves the handle's scan, neighbour lists and everything else of a registration alone."""
+        q = np.asarray(q, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n = len(q)
+        flags = LII_RADIUS_SORTED if sorted else 0
+        qp, stride = (_ptr(q) if n else None), (q.strides[0] if n else 12)
+        offsets = np.zeros(n + 1, np.int64)
+        total = C.c_int64(0)
+        self._check(self.L.lii_map_radius(self.h, qp, n, stride, float(max_dist), flags, _ptr(offsets), None, None, 0, C.byref(total)))
+        rows = total.value if points else 0
+        pts = np.zeros((rows, 3), np.float32)
+        d2 = np.zeros(rows, np.float32)
+        if rows:
+            self._check(self.L.lii_map_radius(self.h, qp, n, stride, float(max_dist), flags, _ptr(offsets), _ptr(pts), _ptr(d2), rows, C.byref(total)))
+        return offsets, pts, d2
+
+    def map_radius_dev(self, q_dev, n, max_dist, offsets_dev, pts_dev, d2_dev, capacity, total_dev, sorted=False, stride_bytes=12):
+        """map_radius with queries and results in device memory the caller owns - raw addresses, or objects with
+        __cuda_array_interface__ (torch tensors): float xyz every stride_bytes in; (n + 1,) int64 offsets, (capacity, 3) float32,
+        (capacity,) float32 and one int64 total out (pts_dev / d2_dev may be None).  Rows with index >= capacity are not written: compare
+        the total with the capacity behind synchronize().  Enqueued on the handle's stream."""
+        self._check(self.L.lii_map_radius_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), float(max_dist),
+                                              LII_RADIUS_SORTED if sorted else 0, _dev_address(offsets_dev), _dev_address(pts_dev),
+                                              _dev_address(d2_dev), int(capacity), _dev_address(total_dev)))
 
     # ------------------------------------------------------------------ scan
     def scan_upload(self, pts):

@@ -1059,6 +1059,221 @@ int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_byt
   return LII_OK;
 }
 
+// ---- the ball query (kernels: lii_query.hip, k_map_radius; scan and sort: lii_sort.hip)
+namespace {
+// The argument rules both forms share.  Nothing has been touched when this fails.
+int radius_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags, const void* offsets,
+                const void* total, bool want_rows, int64_t capacity, NearestPlan* plan) {
+  if (!h) return LII_ERR_INVALID;
+  if ((!xyz && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4 || !offsets || !total)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments (queries, n >= 0, stride a multiple of 4 and >= 12, offsets, total)");
+  if (flags & ~int32_t(LII_RADIUS_SORTED)) return fail(h, LII_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (want_rows && capacity < 0) return fail(h, LII_ERR_INVALID, std::string(who) + ": negative capacity");
+  if (!(max_dist >= 0.0) || !std::isfinite(max_dist)) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_dist must be finite and >= 0 (it bounds the SQUARED distance)");
+  // sqrt(max_dist) > 32 cells, decided without a rounding: the cell size is a float, so the square of 32 cells is exact in a double
+  const double reach = 32.0 * double(h->cell_size);
+  if (max_dist > reach * reach) {
+    char msg[256];
+    std::snprintf(msg, sizeof(msg), "%s: a ball of radius sqrt(max_dist) = %.3f m spans more than 32 grid cells of %.3f m; create the handle with a larger map_cell_size",
+                  who, std::sqrt(max_dist), double(h->cell_size));
+    return fail(h, LII_ERR_INVALID, msg);
+  }
+  float md = float(max_dist);
+  if (double(md) > max_dist) md = std::nextafterf(md, 0.f);
+  plan->max_d2 = md;
+  plan->r_max = std::min(int(std::ceil(std::sqrt(max_dist) / double(h->cell_size))) + 1, 34);
+  return LII_OK;
+}
+extern "C++" {
+template <class T>
+hipError_t radius_room(DevBuf<T>& b, size_t n) {  // (grown geometrically; grow frees first, and hipFree waits for the device)
+  return b.size() >= n ? hipSuccess : b.grow(std::max(n, 2 * b.size()));
+}
+}
+// the handle's query staging with room for `rows` result rows (and min(rows, kQueriesMax) queries): the buffers of lii_map_nearest
+int radius_staging(lii_handle h, size_t rows) {
+  using MQ = lii_context::MapQuery;
+  if (rows <= h->mq.rows) return LII_OK;
+  rows = std::max(rows, std::min(2 * h->mq.rows, MQ::kRowsMax));
+  const size_t bytes = 16 * std::min(rows, MQ::kQueriesMax) + 16 * rows;
+  h->mq.rows = 0;
+  h->mq.h_buf.reset();
+  HIPCHK(h, h->mq.d_buf.grow(bytes));
+  HIPCHK(h, h->mq.h_buf.alloc(bytes, hipHostMallocDefault));
+  h->mq.rows = rows;
+  return LII_OK;
+}
+struct RadiusView {
+  GridView g;
+  unsigned int entries, pts_cap;
+};
+RadiusView radius_view(lii_handle h) {
+  return {grid_view(h), (unsigned int)std::min<size_t>(h->cells_cap_blocks * 512, 0xFFFFFFFFu), h->pts_cap};
+}
+// LII_RADIUS_SORTED: fill (key, slot) rows, sort them by (query, d2 bits), gather.  `rows`: the rows the launch may write (the sort's size).
+int radius_fill_sorted(lii_handle h, const NearestPlan& plan, const void* q_dev, int n, int stride_bytes, const long long* offsets, long long base,
+                       size_t rows, bool rows_exact, float* pts_dev, float* d2_dev) {
+  lii_context::MapRadius& R = h->mr;
+  hipStream_t s = h->stream;
+  int end_bit = 32;
+  while (end_bit < 63 && (size_t(n) - 1) >> (end_bit - 32)) end_bit++;
+  const size_t temp = sort_u64_bits_temp_bytes(rows, end_bit);
+  HIPCHK(h, radius_room(R.d_key_a, rows));
+  HIPCHK(h, radius_room(R.d_key_b, rows));
+  HIPCHK(h, radius_room(R.d_slot_a, rows));
+  HIPCHK(h, radius_room(R.d_slot_b, rows));
+  HIPCHK(h, radius_room(R.d_temp, temp));
+  // (the device form sorts `capacity` rows whatever the total turns out to be: rows nobody fills sort behind every segment)
+  if (!rows_exact) HIPCHK(h, hipMemsetAsync(R.d_key_a, 0xFF, 8 * rows, s));
+  const RadiusView v = radius_view(h);
+  launch_map_radius_fill(v.g, v.entries, v.pts_cap, q_dev, n, stride_bytes, plan.max_d2, plan.r_max, offsets, base, (long long)rows, nullptr, nullptr,
+                         R.d_key_a, R.d_slot_a, s);
+  HIPCHK(h, hipGetLastError());
+  sort_pairs_u64_bits(R.d_temp, R.d_temp.size(), R.d_key_a, R.d_key_b, R.d_slot_a, R.d_slot_b, rows, end_bit, s);
+  HIPCHK(h, hipGetLastError());
+  launch_map_radius_gather(v.g, v.pts_cap, R.d_key_b, R.d_slot_b, offsets + n, base, (long long)rows, pts_dev, d2_dev, s);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+}  // namespace
+
+int lii_map_radius_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags, int64_t* offsets_dev,
+                       float* pts_dev, float* d2_dev, int64_t capacity, int64_t* total_dev) {
+  if (h && h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_map_radius_dev: a registration is under way (lii_scan_job::while_waiting)");  // (before anything touches the stream)
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  static_assert(sizeof(long long) == sizeof(int64_t), "offsets are 64-bit words");
+  const bool want = pts_dev || d2_dev;
+  NearestPlan plan;
+  int rc = radius_plan(h, "lii_map_radius_dev", xyz_dev, n, stride_bytes, max_dist, flags, offsets_dev, total_dev, want, capacity, &plan);
+  if (rc != LII_OK) return rc;
+  hipStream_t s = h->stream;
+  long long* off = reinterpret_cast<long long*>(offsets_dev);
+  if (n == 0) {
+    HIPCHK(h, hipMemsetAsync(off, 0, 8, s));
+    HIPCHK(h, hipMemsetAsync(total_dev, 0, 8, s));
+    return LII_OK;
+  }
+  rc = nearest_map(h, "lii_map_radius_dev");
+  if (rc != LII_OK) return rc;
+  HIPCHK(h, radius_room(h->mr.d_temp, scan_i64_temp_bytes(size_t(n) + 1)));
+  const RadiusView v = radius_view(h);
+  launch_map_radius_count(v.g, v.entries, v.pts_cap, xyz_dev, n, stride_bytes, plan.max_d2, plan.r_max, off, s);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemsetAsync(off + n, 0, 8, s));
+  exclusive_scan_i64(h->mr.d_temp, h->mr.d_temp.size(), off, size_t(n) + 1, s);  // (n + 1 words: the last one becomes the total)
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(total_dev, off + n, 8, hipMemcpyDeviceToDevice, s));
+  if (!want || capacity == 0) return LII_OK;
+  if (flags & LII_RADIUS_SORTED) return radius_fill_sorted(h, plan, xyz_dev, n, stride_bytes, off, 0, size_t(capacity), false, pts_dev, d2_dev);
+  launch_map_radius_fill(v.g, v.entries, v.pts_cap, xyz_dev, n, stride_bytes, plan.max_d2, plan.r_max, off, 0, capacity, pts_dev, d2_dev, nullptr, nullptr, s);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+
+int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags, int64_t* offsets_out, float* pts_out,
+                   float* d2_out, int64_t capacity, int64_t* total) {
+  if (h && h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_map_radius: a registration is under way (lii_scan_job::while_waiting)");  // (before anything touches the stream)
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  const bool want = pts_out || d2_out;
+  NearestPlan plan;
+  int rc = radius_plan(h, "lii_map_radius", xyz, n, stride_bytes, max_dist, flags, offsets_out, total, want, capacity, &plan);
+  if (rc != LII_OK) return rc;
+  if (n == 0) {
+    offsets_out[0] = 0;
+    *total = 0;
+    return LII_OK;
+  }
+  rc = nearest_map(h, "lii_map_radius");
+  if (rc != LII_OK) return rc;
+  using MQ = lii_context::MapQuery;
+  const size_t block = std::min<size_t>(size_t(n), MQ::kQueriesMax);  // queries counted by one launch
+  rc = radius_staging(h, block + 1);
+  if (rc != LII_OK) return rc;
+  HIPCHK(h, radius_room(h->mr.d_off, block + 1));
+  hipStream_t s = h->stream;
+  const char* src = static_cast<const char*>(xyz);
+  const RadiusView v = radius_view(h);
+  // the queries of one block: packed into the pinned staging and sent to the head of the device staging
+  auto send_queries = [&](size_t at, size_t m) -> hipError_t {
+    float* hq = reinterpret_cast<float*>(h->mq.h_buf.get());
+    for (size_t i = 0; i < m; i++) std::memcpy(hq + 3 * i, src + (at + i) * size_t(stride_bytes), 12);
+    return hipMemcpyAsync(h->mq.d_buf, h->mq.h_buf, 12 * m, hipMemcpyHostToDevice, s);
+  };
+  // ---- the count pass over every block: offsets and total
+  int64_t run = 0;
+  for (size_t at = 0; at < size_t(n); at += block) {
+    const size_t m = std::min(block, size_t(n) - at);
+    unsigned char* hc = h->mq.h_buf + 16 * std::min(h->mq.rows, MQ::kQueriesMax);  // (the rows' area: 8 m bytes of it)
+    HIPCHK(h, send_queries(at, m));
+    launch_map_radius_count(v.g, v.entries, v.pts_cap, h->mq.d_buf, int(m), 12, plan.max_d2, plan.r_max, h->mr.d_off, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hc, h->mr.d_off, 8 * m, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (size_t i = 0; i < m; i++) {
+      long long c = 0;
+      std::memcpy(&c, hc + 8 * i, 8);
+      offsets_out[at + i] = run;
+      run += c;
+    }
+  }
+  offsets_out[n] = run;
+  *total = run;
+  if (!want) return LII_OK;
+  if (capacity < run) return fail(h, LII_ERR_CAPACITY, "lii_map_radius: capacity too small");
+  if (run == 0) return LII_OK;
+  // ---- the fill pass: a chunk is a run of queries of one block with at most kRowsMax rows - or one query with more
+  auto chunk_end = [&](size_t a, size_t end) {
+    size_t b = a + 1;
+    while (b < end && offsets_out[b + 1] - offsets_out[a] <= int64_t(MQ::kRowsMax)) b++;
+    return b;
+  };
+  size_t rows_max = 0;
+  for (size_t at = 0; at < size_t(n); at += block)
+    for (size_t a = at, end = std::min(at + block, size_t(n)); a < end;) {
+      const size_t b = chunk_end(a, end);
+      rows_max = std::max(rows_max, size_t(offsets_out[b] - offsets_out[a]));
+      a = b;
+    }
+  rc = radius_staging(h, std::max(rows_max, block + 1));
+  if (rc != LII_OK) return rc;
+  const size_t q_cap = std::min(h->mq.rows, MQ::kQueriesMax);
+  const size_t off_pts = 16 * q_cap, off_d2 = off_pts + 12 * h->mq.rows;
+  unsigned char *hb = h->mq.h_buf, *db = h->mq.d_buf;
+  float* const d_pts_rows = pts_out ? reinterpret_cast<float*>(db + off_pts) : nullptr;
+  float* const d_d2_rows = d2_out ? reinterpret_cast<float*>(db + off_d2) : nullptr;
+  for (size_t at = 0; at < size_t(n); at += block) {
+    const size_t end = std::min(at + block, size_t(n));
+    if (offsets_out[end] == offsets_out[at]) continue;  // (a block of empty balls)
+    HIPCHK(h, send_queries(at, end - at));
+    for (size_t a = at; a < end;) {
+      const size_t b = chunk_end(a, end), m = b - a;
+      const int64_t first = offsets_out[a];
+      const size_t rows = size_t(offsets_out[b] - first);
+      if (rows > 0) {
+        // the chunk's offsets travel through the head of the rows' area (8 (m + 1) <= 12 (block + 1) bytes; the rows come back behind the launch)
+        std::memcpy(hb + off_pts, offsets_out + a, 8 * (m + 1));
+        HIPCHK(h, hipMemcpyAsync(h->mr.d_off, hb + off_pts, 8 * (m + 1), hipMemcpyHostToDevice, s));
+        const void* q_dev = db + 12 * (a - at);
+        if (flags & LII_RADIUS_SORTED) {
+          rc = radius_fill_sorted(h, plan, q_dev, int(m), 12, h->mr.d_off, first, rows, true, d_pts_rows, d_d2_rows);
+          if (rc != LII_OK) return rc;
+        } else {
+          launch_map_radius_fill(v.g, v.entries, v.pts_cap, q_dev, int(m), 12, plan.max_d2, plan.r_max, h->mr.d_off, first, (long long)rows, d_pts_rows,
+                                 d_d2_rows, nullptr, nullptr, s);
+          HIPCHK(h, hipGetLastError());
+        }
+        if (pts_out) HIPCHK(h, hipMemcpyAsync(hb + off_pts, db + off_pts, 12 * rows, hipMemcpyDeviceToHost, s));
+        if (d2_out) HIPCHK(h, hipMemcpyAsync(hb + off_d2, db + off_d2, 4 * rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (pts_out) std::memcpy(pts_out + 3 * size_t(first), hb + off_pts, 12 * rows);
+        if (d2_out) std::memcpy(d2_out + size_t(first), hb + off_d2, 4 * rows);
+      }
+      a = b;
+    }
+  }
+  return LII_OK;
+}
+
 
 int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, int32_t* n_no_downsample) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)

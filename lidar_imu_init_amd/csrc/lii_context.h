@@ -103,12 +103,21 @@ struct lii_context {
   DevBuf<unsigned char> d_sort_temp;  // temporary storage of the sorts and scans (size(): bytes)
   // lii_map_nearest (host form): staging for one chunk of queries and its results, device and pinned, laid out alike (queries |
   // counts | points | d2).  Created by the first call, grown geometrically up to kRowsMax rows (17 MiB each), kept until the handle goes.
+  // lii_map_radius (host form) stages through the same two buffers and grows them beyond kRowsMax only for a single ball of more rows.
   struct MapQuery {
     static constexpr size_t kQueriesMax = 65536, kRowsMax = size_t(1) << 20;  // per chunk: queries, and rows (queries x k)
     DevBuf<unsigned char> d_buf;
     PinnedBuf<unsigned char> h_buf;
     size_t rows = 0;  // both hold min(rows, kQueriesMax) queries and `rows` result rows
   } mq;
+  // lii_map_radius / lii_map_radius_dev: what the ball query needs beyond mq.  Nothing here exists before the first such call; every
+  // buffer grows geometrically and goes with the handle.
+  struct MapRadius {
+    DevBuf<long long> d_off;             // host form: the offsets of one chunk of queries (kQueriesMax + 1)
+    DevBuf<unsigned char> d_temp;        // temporary storage of the scan and of the sort
+    DevBuf<unsigned long long> d_key_a, d_key_b;  // LII_RADIUS_SORTED: (query << 32 | d2 bits) per row, before and behind the sort
+    DevBuf<unsigned int> d_slot_a, d_slot_b;      // ... and the row's slot in the point array
+  } mr;
 
   // ---- scan
   DevBuf<float4> d_scan;   // raw / undistorted (x,y,z,t_ms)

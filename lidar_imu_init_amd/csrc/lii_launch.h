@@ -51,6 +51,25 @@ void launch_cells_fill(const unsigned long long* keys, const unsigned int* ranks
 // / d2_out: neighbour j of query i, zeros from count_out[i] on; pts_out / d2_out may be nullptr.
 void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, int k,
                         float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s);
+// ... and the ball query (lii_map_radius): every point with d2 <= max_d2, in two walks of the same cells.  _count: count_out[i] = points in
+// the ball of query i (64 bits, so that the scan below turns them into offsets in place).  _fill: the points of query i into rows
+// offsets[i] - base .. offsets[i + 1] - base - 1, only rows < capacity; per row 3 floats of pts_out, d2_out, and - for LII_RADIUS_SORTED -
+// key_out (query << 32 | d2 bits) and slot_out (the point's slot in the array); each of the four may be nullptr.  _gather: behind the sort
+// of (key, slot), rows < min(total[0] - base, capacity): the key's d2 and the slot's point.
+void launch_map_radius_count(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2,
+                             int r_max, long long* count_out, hipStream_t s);
+void launch_map_radius_fill(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2,
+                            int r_max, const long long* offsets, long long base, long long capacity, float* pts_out, float* d2_out,
+                            unsigned long long* key_out, unsigned int* slot_out, hipStream_t s);
+void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const unsigned long long* keys, const unsigned int* slots, const long long* total,
+                              long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s);
+// (lii_sort.hip) counts -> offsets in place: io[i] = io[0] + ... + io[i - 1] over n words; and the sort of the sorted form: bits [0, end_bit)
+// of 64-bit keys with 32-bit values, stable.  *_temp_bytes: the temporary storage either needs for that size.
+size_t scan_i64_temp_bytes(size_t n);
+void exclusive_scan_i64(void* temp, size_t temp_bytes, long long* io, size_t n, hipStream_t s);
+size_t sort_u64_bits_temp_bytes(size_t n, int end_bit);
+void sort_pairs_u64_bits(void* temp, size_t temp_bytes, const unsigned long long* kin, unsigned long long* kout, const unsigned int* vin,
+                         unsigned int* vout, size_t n, int end_bit, hipStream_t s);
 // registration: the search launch (lii_knn.hip)
 // (`pose`: device memory on every path - a host-driven pass uploads it first)
 // epoch: the number of this search launch (> 0, RegistrationBuffers::flag_*) and of the fit launch behind it; 0: no list of unfinished queries

@@ -37,6 +37,27 @@ void sort_pairs_u32(void* temp, size_t temp_bytes, const unsigned int* kin, unsi
   if (n <= 0) return;
   (void)rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, vin, vout, (size_t)n, 0, 32, s);
 }
+// the ball query (lii_map_radius): counts -> offsets, and the sort behind LII_RADIUS_SORTED
+size_t scan_i64_temp_bytes(size_t n) {
+  size_t b = 0;
+  (void)rocprim::exclusive_scan(nullptr, b, (const long long*)nullptr, (long long*)nullptr, 0ll, n, rocprim::plus<long long>(), 0);
+  return b + 256;
+}
+void exclusive_scan_i64(void* temp, size_t temp_bytes, long long* io, size_t n, hipStream_t s) {
+  if (n == 0) return;
+  (void)rocprim::exclusive_scan(temp, temp_bytes, (const long long*)io, io, 0ll, n, rocprim::plus<long long>(), s);
+}
+size_t sort_u64_bits_temp_bytes(size_t n, int end_bit) {
+  size_t b = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, b, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned int*)nullptr,
+                                  (unsigned int*)nullptr, n, 0, (unsigned int)end_bit, 0);
+  return b + 256;
+}
+void sort_pairs_u64_bits(void* temp, size_t temp_bytes, const unsigned long long* kin, unsigned long long* kout, const unsigned int* vin,
+                         unsigned int* vout, size_t n, int end_bit, hipStream_t s) {
+  if (n == 0) return;
+  (void)rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, vin, vout, n, 0, (unsigned int)end_bit, s);
+}
 void inclusive_scan_u32(void* temp, size_t temp_bytes, const unsigned int* in, unsigned int* out, int n, hipStream_t s) {
   if (n <= 0) return;
   (void)rocprim::inclusive_scan(temp, temp_bytes, in, out, (size_t)n, rocprim::plus<unsigned int>(), s);
