@@ -103,10 +103,9 @@ bool fuse_filter(lii_handle h, float leaf) {
 // Fetches the exact size of the down-sampled cloud from the device (one small synchronising copy).
 int resolve_n_body(lii_handle h) {
   if (!h->n_body_pending) return LII_OK;
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 2048, h->d_nbody, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  int* v = h->h_small->n_body;
+  HIPCHK(h, hipMemcpyAsync(v, h->d_nbody, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  int v[2];
-  std::memcpy(v, h->h_small + 2048, sizeof(v));
   h->n_body = v[0];
   h->last_filtered = v[1];
   h->n_body_pending = false;
@@ -391,7 +390,6 @@ static int create_resources(lii_handle h) {
   h->d_counts = h->d_mapctr + kMapCtrWords;
   HIPCHK(h, h->d_keys_a.alloc(M));
   HIPCHK(h, h->d_keys_b.alloc(M));
-  HIPCHK(h, h->d_keys_c.alloc(M));
   HIPCHK(h, h->d_idx_a.alloc(M));
   HIPCHK(h, h->d_idx_b.alloc(M));
   HIPCHK(h, h->d_blocks.alloc(4096));
@@ -407,7 +405,6 @@ static int create_resources(lii_handle h) {
   HIPCHK(h, hipMemset(h->d_cells, 0, sizeof(uint2) * h->cells_cap_blocks * 512));
   HIPCHK(h, hipMemset(h->d_cell_cap, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
   HIPCHK(h, hipMemset(h->d_tp, 0, sizeof(unsigned int) * h->cells_cap_blocks * 512));
-  HIPCHK(h, h->d_counter.alloc(4));
   // (whole 32-bit words: k_point_tomb claims a tombstone byte with an atomic on the aligned word that holds it)
   HIPCHK(h, h->d_tomb.alloc((size_t(h->pts_cap) + 3) & ~size_t(3)));
   HIPCHK(h, hipMemset(h->d_tomb, 0, h->d_tomb.size()));
@@ -415,11 +412,9 @@ static int create_resources(lii_handle h) {
   HIPCHK(h, h->d_batch.alloc(M));
   HIPCHK(h, h->d_dropped.alloc(NM));
   h->drop_cap = (unsigned int)h->d_dropped.size();
-  HIPCHK(h, h->d_ins_c.alloc(M));
   HIPCHK(h, h->d_u32_a.alloc(NM));
   HIPCHK(h, h->d_u32_b.alloc(NM));
   HIPCHK(h, hipMemset(h->d_u32_b, 0, sizeof(unsigned int) * NM));  // (k_map_decide's block words: run number 0 is never used)
-  HIPCHK(h, h->d_u32_c.alloc(NM));
   {
     const size_t slots = add_hash_slots(int(N));
     HIPCHK(h, h->d_ah_key.alloc(slots)); HIPCHK(h, h->d_ah_best.alloc(slots)); HIPCHK(h, h->d_ah_slot.alloc(N));
@@ -427,8 +422,6 @@ static int create_resources(lii_handle h) {
   }
   HIPCHK(h, h->d_list_add.alloc(N));
   HIPCHK(h, h->d_list_nodown.alloc(N));
-  HIPCHK(h, h->n_map_pinned.alloc(16, hipHostMallocDefault));
-  h->n_map_pinned[0] = 0;
   HIPCHK(h, h->d_sort_temp.alloc(sort_temp_bytes(int(std::max<size_t>(NM, h->cells_cap_blocks * 512)))));
   HIPCHK(h, h->d_scan.alloc(N));
   HIPCHK(h, h->d_body.alloc(N));
@@ -469,7 +462,6 @@ static int create_resources(lii_handle h) {
   HIPCHK(h, h->h_mapflag.alloc(64, hipHostMallocMapped));  // (written by k_map_publish)
   std::memset(h->h_mapflag, 0, 256);
   HIPCHK(h, h->ev_lists.create(hipEventDisableTiming));
-  HIPCHK(h, hipMemset(h->d_counter, 0, 16));
   h->partial_stride = register_blocks(int(N)) + std::max(lii::kCompletionBlocks, lii::kCompletionBlocksPre) + 8;  // (+ the columns of the fit launches' completion workgroups)
   HIPCHK(h, h->d_flags.alloc(4 + 16 * lii::kListCap));  // 2 counters (+ 2 pad), 2 x kListCap entries of two float4
   HIPCHK(h, hipMemset(h->d_flags, 0, sizeof(int) * (4 + 16 * lii::kListCap)));
@@ -513,7 +505,7 @@ static int create_resources(lii_handle h) {
   HIPCHK(h, h->cal.d_cal_params.alloc(64));
   HIPCHK(h, h->cal.d_cal_out.alloc(128));
   HIPCHK(h, h->h_stage.alloc(NM * kMatch, hipHostMallocDefault));  // large enough for the neighbour download too
-  HIPCHK(h, h->h_small.alloc(32768, hipHostMallocDefault));
+  HIPCHK(h, h->h_small.alloc(1, hipHostMallocDefault));
   for (int i = 0; i < 4; i++) HIPCHK(h, h->prof.ev[i].create(kProfEventFlags));
   for (int i = 0; i < 32; i++) HIPCHK(h, h->prof.ev_it[i].create(kProfEventFlags));
   launch_table_clear(h->d_blocks, (unsigned int)h->d_blocks.size(), h->stream);

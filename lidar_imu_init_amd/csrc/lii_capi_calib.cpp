@@ -30,13 +30,14 @@ int lii_calib_eval(lii_handle h, int32_t stage, const double* params, double* Jt
   if (h->cal.n_cal <= 0) return fail(h, LII_ERR_STATE, "lii_calib_eval: no buffers uploaded");
   const int np = stage == 1 ? 9 : (stage == 2 ? 13 : 24);
   const int dof = stage == 1 ? 3 : (stage == 2 ? 7 : 9);
-  std::memcpy(h->h_small, params, sizeof(double) * np);
-  HIPCHK(h, hipMemcpyAsync(h->cal.d_cal_params, h->h_small, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+  static_assert(kCalibEvalParams == 24 && kCalibEvalOut == 9 * 9 + 9 + 1, "stage 3: the most parameters and outputs");
+  std::memcpy(h->h_small->calib_params, params, sizeof(double) * np);
+  HIPCHK(h, hipMemcpyAsync(h->cal.d_cal_params, h->h_small->calib_params, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
   launch_calib_eval(stage, h->cal.d_cal_imu, h->cal.d_cal_lidar, h->cal.n_cal, h->cal.d_cal_params, h->cal.d_cal_out, h->stream);
   const int n_out = dof * dof + dof + 1;
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 64, h->cal.d_cal_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
+  const double* o = h->h_small->calib_out;
+  HIPCHK(h, hipMemcpyAsync(h->h_small->calib_out, h->cal.d_cal_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const double* o = h->h_small + 64;
   if (JtJ) std::memcpy(JtJ, o, sizeof(double) * dof * dof);
   if (Jtr) std::memcpy(Jtr, o + dof * dof, sizeof(double) * dof);
   if (cost) *cost = o[dof * dof + dof];

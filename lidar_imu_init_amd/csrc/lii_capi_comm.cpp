@@ -41,6 +41,8 @@ struct GxLayout {
   size_t block;
 };
 int gx_prepare(lii_handle h, int N, GxLayout* L) {
+  // (the headers of all ranks come to the host in PinnedScratch::gx_headers)
+  if (N > kGxRanksMax) return fail(h, LII_ERR_CAPACITY, "list exchange over RCCL: more than " + std::to_string(kGxRanksMax) + " ranks in the job");
   const size_t block = size_t(kGatherHeaderBytes) + sizeof(float4) * size_t(h->cfg.max_scan_points);
   if (!h->net.d_gx || h->net.gx_block != block || h->net.gx_ranks != N) {
     const size_t bytes = block * (size_t(N) + 1) + size_t(N) * kGatherHeaderBytes + sizeof(void*) * (size_t(N) + 1);
@@ -75,7 +77,7 @@ template <class Gather>
 int gx_gather_collect(lii_handle h, const GxLayout& L, int N, int rank, unsigned long long seq, hipStream_t s, Gather&& gather) {
   std::string e = gather(L.send, L.hdrs, size_t(kGatherHeaderBytes));
   if (!e.empty()) return fail(h, LII_ERR_COMM, "list headers: " + e);
-  unsigned char* host_hdrs = reinterpret_cast<unsigned char*>(h->h_small + 3200);
+  unsigned char* host_hdrs = h->h_small->gx_headers;
   HIPCHK(h, hipMemcpyAsync(host_hdrs, L.hdrs, size_t(N) * kGatherHeaderBytes, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   long long longest = 0;

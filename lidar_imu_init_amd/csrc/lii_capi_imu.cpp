@@ -24,7 +24,8 @@ namespace {
 // what every entry point that propagates checks first (include/liinit_hip.h, "Rules")
 int check_feed(lii_handle h, const char* who, const lii_imu_sample* imu, int32_t n_imu) {
   if (!imu || n_imu < 1) return fail(h, LII_ERR_INVALID, std::string(who) + ": no IMU samples (the reference returns untouched when meas.imu is empty)");
-  if (n_imu > 63) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": more than 63 IMU samples (64 poses) in one scan");
+  static_assert(kImuSamplesMax == 63, "the message names the limit");
+  if (n_imu > kImuSamplesMax) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": more than 63 IMU samples (64 poses) in one scan");
   if (!h->imu.have_noise) return fail(h, LII_ERR_STATE, std::string(who) + ": no noise block (lii_imu_set_noise)");
   if (!h->imu.have_carry) return fail(h, LII_ERR_STATE, std::string(who) + ": no carry (lii_imu_set_carry)");
   if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, std::string(who) + ": single rank only for now (a communicator is attached)");
@@ -113,7 +114,7 @@ int lii_imu_propagate(lii_handle h, const lii_imu_sample* imu, int32_t n_imu, do
   launch_imu_propagate(a, h->stream);
   HIPCHK(h, hipGetLastError());
   h->imu.carry_sel ^= 1;  // (only behind a launch that went out: a failed one leaves the current carry the current one)
-  double* stage = h->h_small + 4096;  // (pinned, 32 768 doubles; lii_map_delete_boxes stages here too - both calls end with a synchronisation before they return)
+  lii_pose6d* stage = h->h_small->imu_poses;  // (pinned, kImuSamplesMax + 1 poses: check_feed; this call ends with a synchronisation)
   HIPCHK(h, hipMemcpyAsync(stage, h->d_poses, sizeof(lii_pose6d) * size_t(n_imu + 1), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const int K = int(h->imu.h_out[kStateDoubles + 15]);

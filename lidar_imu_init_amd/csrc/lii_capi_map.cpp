@@ -7,7 +7,43 @@
 using namespace lii_impl;
 
 namespace lii_impl {
-
+namespace {
+// One block of kMapCtrWords device counters - from the pinned scratch or from h_mapflag - becomes the host's copies.
+void adopt_counters(lii_handle h, const int* c) {
+  if (c[kMapCtrWinStale] && h->win_valid) { h->win_valid = false; h->win_dropped++; }  // (an update touched a cell outside the window's box)
+  h->n_used = c[kMapCtrUsed];
+  h->n_map = c[kMapCtrValid];
+  h->n_blocks = int(std::min<size_t>(size_t(std::max(c[kMapCtrBlocks], 0)), h->cells_cap_blocks));  // (the counter runs past the pool when it is exhausted)
+  h->map_dirty = false;
+}
+// d_mapctr -> PinnedScratch::map_ctr: one copy on the handle's stream and the wait for it
+int read_counters(lii_handle h) {
+  HIPCHK(h, hipMemcpyAsync(h->h_small->map_ctr, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return LII_OK;
+}
+// The work list with room for `need` cell entries; where it has to grow, to `entries` (nothing in flight uses the list).  work_cap and
+// the buffer agree across a failed allocation.
+int work_reserve(lii_handle h, size_t need, size_t entries) {
+  if (need <= size_t(h->work_cap)) return LII_OK;
+  h->work_cap = 0;
+  HIPCHK(h, h->d_work.grow(entries));
+  h->work_cap = (unsigned int)h->d_work.size();
+  return LII_OK;
+}
+// The window as the launches that change cell entries keep it current (win == nullptr: nothing to keep); a window that is not kept goes.
+lii::WinKeep win_keep_or_drop(lii_handle h) {
+  lii::WinKeep wk = {};
+  if (h->win_valid && h->win_keep && h->d_win && h->d_block_key) {
+    wk.win = h->d_win; wk.key_of_id = h->d_block_key;
+    wk.x0 = h->win_org[0]; wk.y0 = h->win_org[1]; wk.z0 = h->win_org[2];
+    wk.nx = h->win_dim[0]; wk.ny = h->win_dim[1]; wk.nz = h->win_dim[2];
+  } else if (h->win_valid) { h->win_valid = false; h->win_dropped++; }
+  return wk;
+}
+// map_seq / lm.seq: the number after `seq` (never 0, never negative)
+int next_seq(int seq) { return seq == 0x7FFFFFFF ? 1 : seq + 1; }
+}  // namespace
 
 // Builds the device map from n float4 points in d_map_unsorted:
 // key (block | local cell) -> radix sort -> gather (d_map: cell-sorted, compact) -> block ids by scan -> per-block cell tables +
@@ -29,9 +65,9 @@ int build_index(lii_handle h, int n, int extra_blocks) {
     unsigned int* flags = h->d_idx_a;  // free after the sort
     launch_block_flags(h->d_keys_b, n, flags, s);
     inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), flags, ranks, n, s);
-    HIPCHK(h, hipMemcpyAsync(h->h_small, ranks + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&h->h_small->index_blocks, ranks + (n - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    std::memcpy(&n_blocks, h->h_small, sizeof(unsigned int));
+    n_blocks = h->h_small->index_blocks;
   }
   const size_t want_blocks = size_t(n_blocks) + size_t(std::max(extra_blocks, 0));
   if (want_blocks + 1 > h->cells_cap_blocks) {
@@ -78,14 +114,13 @@ int build_index(lii_handle h, int n, int extra_blocks) {
     // the dense cell window: the box of the occupied blocks, one block of margin on every side (queries at the map's edge look one
     // cell out), if it fits 64 MiB of entries
     unsigned int* box = h->d_cs_a;  // (free again)
+    unsigned int* bxx = h->h_small->win_box;
     const unsigned int init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    std::memcpy(h->h_small + 2100, init, sizeof(init));
-    HIPCHK(h, hipMemcpyAsync(box, h->h_small + 2100, sizeof(init), hipMemcpyHostToDevice, s));
+    std::memcpy(bxx, init, sizeof(init));
+    HIPCHK(h, hipMemcpyAsync(box, bxx, sizeof(init), hipMemcpyHostToDevice, s));
     launch_win_bbox(h->d_blocks, bcap, box, s);
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 2100, box, sizeof(init), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(bxx, box, sizeof(init), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    unsigned int bxx[6];
-    std::memcpy(bxx, h->h_small + 2100, sizeof(bxx));
     const int bb = kCellBias >> kCoarseShift;
     size_t entries_w = 1;
     for (int a = 0; a < 3; a++) {
@@ -101,16 +136,12 @@ int build_index(lii_handle h, int n, int extra_blocks) {
       h->win_valid = true;
     }
   }
-  int rc = LII_OK;
-  {  // the slots in use (sum of the capacities) - and a first capacity check
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 3072, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    int c[kMapCtrWords];
-    std::memcpy(c, h->h_small + 3072, sizeof(c));
-    h->n_used = c[kMapCtrUsed];
-    if ((unsigned int)h->n_used > h->pts_cap) rc = fail(h, LII_ERR_CAPACITY, "local map with its per-cell slack exceeds the point array");
-    h->pts_cap_eff = h->map_tight ? std::min<unsigned int>(h->pts_cap, (unsigned int)h->n_used + 256u) : h->pts_cap;
-  }
+  // the slots in use (sum of the capacities) - and a first capacity check
+  int rc = read_counters(h);
+  if (rc != LII_OK) return rc;
+  adopt_counters(h, h->h_small->map_ctr);  // (k_spread left n and n_blocks beside them, nothing has made the window stale: only n_used is news)
+  if ((unsigned int)h->n_used > h->pts_cap) rc = fail(h, LII_ERR_CAPACITY, "local map with its per-cell slack exceeds the point array");
+  h->pts_cap_eff = h->map_tight ? std::min<unsigned int>(h->pts_cap, (unsigned int)h->n_used + 256u) : h->pts_cap;
   return rc;
 }
 
@@ -186,11 +217,7 @@ int commit_map(lii_handle h) {
     const int rc = map_counters(h, false);
     if (rc != LII_OK) return rc;
   } else {  // the counters came along: the host's copies are current again without a read of their own
-    if (h->h_mapflag[kMapCtrWinStale] && h->win_valid) { h->win_valid = false; h->win_dropped++; }  // (the update touched a cell outside the window's box)
-    h->n_used = h->h_mapflag[kMapCtrUsed];
-    h->n_map = h->h_mapflag[kMapCtrValid];
-    h->n_blocks = int(std::min<size_t>(size_t(std::max(h->h_mapflag[kMapCtrBlocks], 0)), h->cells_cap_blocks));
-    h->map_dirty = false;
+    adopt_counters(h, h->h_mapflag);
     h->lm.counts_pending = false;  // (the update ran behind every local-map call enqueued so far: its counters hold their deletes)
   }
   return LII_OK;
@@ -208,17 +235,10 @@ int map_counters(lii_handle h, bool already_synced) {
   h->map_flag_pending = false;
   if (!h->map_dirty && !h->lm.counts_pending) return LII_OK;  // (counts_pending: a local-map call deleted on the device since the last read)
   h->lm.counts_pending = false;
-  if (!already_synced) {
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 3072, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  int c[kMapCtrWords];
-  std::memcpy(c, h->h_small + 3072, sizeof(c));
-  if (c[kMapCtrWinStale] && h->win_valid) { h->win_valid = false; h->win_dropped++; }
-  h->n_used = c[kMapCtrUsed];
-  h->n_map = c[kMapCtrValid];
-  h->n_blocks = int(std::min<size_t>(size_t(std::max(c[kMapCtrBlocks], 0)), h->cells_cap_blocks));  // (the counter runs past the pool when it is exhausted)
-  h->map_dirty = false;
+  int rc = already_synced ? LII_OK : read_counters(h);
+  if (rc != LII_OK) return rc;
+  const int* c = h->h_small->map_ctr;
+  adopt_counters(h, c);
   if (c[kMapCtrOverflow]) {
     const int n_drop = c[kMapCtrDropped];
     if (n_drop < 0 || (unsigned int)n_drop > h->drop_cap || (size_t)n_drop > size_t(h->cfg.max_map_points)) {
@@ -228,7 +248,7 @@ int map_counters(lii_handle h, bool already_synced) {
     h->map_recoveries++;
     if (n_drop > 0)  // (the rebuild leaves d_dropped alone; the batch buffer is free: its Add_Points call has returned)
       HIPCHK(h, hipMemcpyAsync(h->d_batch, h->d_dropped, sizeof(float4) * size_t(n_drop), hipMemcpyDeviceToDevice, h->stream));
-    int rc = map_rebuild(h, std::max(4096, 2 * n_drop));
+    rc = map_rebuild(h, std::max(4096, 2 * n_drop));
     if (rc != LII_OK) return rc;
     if (n_drop > 0) {
       const bool tight = h->map_tight;
@@ -237,13 +257,9 @@ int map_counters(lii_handle h, bool already_synced) {
       h->map_tight = tight;
       if (rc != LII_OK) return rc;
       // settle it now: the caller of map_counters goes on with counters that include the re-inserted points
-      HIPCHK(h, hipMemcpyAsync(h->h_small + 3072, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      std::memcpy(c, h->h_small + 3072, sizeof(c));
-      h->n_used = c[kMapCtrUsed];
-      h->n_map = c[kMapCtrValid];
-      h->n_blocks = int(std::min<size_t>(size_t(std::max(c[kMapCtrBlocks], 0)), h->cells_cap_blocks));
-      h->map_dirty = false;
+      rc = read_counters(h);
+      if (rc != LII_OK) return rc;
+      adopt_counters(h, c);
       if (c[kMapCtrOverflow]) return fail(h, LII_ERR_CAPACITY, "local map: the re-insertion after a rebuild ran out of room again");
     }
   }
@@ -258,10 +274,9 @@ int map_gather(lii_handle h, int* n_out) {
   launch_cell_counts(h->d_cells, ne, h->d_cs_a, s);
   inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), h->d_cs_a, h->d_cs_b, ne, s);
   launch_gather_live(h->d_pts, h->d_cells, h->d_cs_b, ne, h->d_map_unsorted, h->cfg.max_map_points, s);
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 3000, h->d_cs_b + (ne - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&h->h_small->gather_count, h->d_cs_b + (ne - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  unsigned int n = 0;
-  std::memcpy(&n, h->h_small + 3000, sizeof(n));
+  const unsigned int n = h->h_small->gather_count;
   *n_out = int(std::min<unsigned int>(n, (unsigned int)h->cfg.max_map_points));
   return LII_OK;
 }
@@ -282,15 +297,6 @@ int map_rebuild(lii_handle h, int extra_blocks) {
 // bounds of them (lii_map_incremental's predicted sizes); the launches are made for the bounds.
 // count_events = false (lii_map_incremental): Add_Points' event counter is not needed - the down-sampled list is folded through
 // the hash table instead of the batch sort (lii_map.hip: AddHash).
-lii::WinKeep win_keep_view(lii_handle h) {
-  lii::WinKeep wk = {};
-  if (h->win_valid && h->win_keep && h->d_win && h->d_block_key) {
-    wk.win = h->d_win; wk.key_of_id = h->d_block_key;
-    wk.x0 = h->win_org[0]; wk.y0 = h->win_org[1]; wk.z0 = h->win_org[2];
-    wk.nx = h->win_dim[0]; wk.ny = h->win_dim[1]; wk.nz = h->win_dim[2];
-  }
-  return wk;
-}
 lii::RemovedSink removed_sink(lii_handle h) {
   lii::RemovedSink rs = {};
   if (h->rm.on && h->rm.d_buf && h->rm.d_ctr && h->rm.cap > 0) {
@@ -372,11 +378,10 @@ int map_apply(lii_handle h, const float4* list, int n_list, bool downsample, con
     launch_ins_cells(list_a, flags_a, n_list, flags_a ? nullptr : n_list_dev, extra, n_extra, n_extra_dev, h->d_ins_e2, h->d_blocks, h->block_mask, g.inv_cs, tables_cap, h->d_ins_e, h->d_tp,
                      h->d_work, h->d_mapctr, h->work_cap, h->d_dropped, h->drop_cap, h->d_block_key, s);
   // (cell entries change: the dense window is kept current by the two launches that change them - WinKeep - or dropped)
-  const lii::WinKeep wk = win_keep_view(h);
+  const lii::WinKeep wk = win_keep_or_drop(h);
   if (wk.win) h->win_kept++;
-  else if (h->win_valid) { h->win_valid = false; h->win_dropped++; }
   launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, (int)work_need, wk, s);
-  h->map_seq = h->map_seq == 0x7FFFFFFF ? 1 : h->map_seq + 1;
+  h->map_seq = next_seq(h->map_seq);
   launch_ins_write(list_a, h->d_ins_e, n_list, flags_a ? nullptr : n_list_dev, extra, h->d_ins_e2, n_extra, n_extra_dev, h->d_cells, h->d_cell_cap, h->d_pts, h->d_mapctr, h->d_dropped,
                    h->drop_cap, s, h->h_mapflag, kMapCtrWords + 8, kMapFlagSeqAt, h->map_seq, wk);
   HIPCHK(h, hipGetLastError());
@@ -431,17 +436,12 @@ int local_map_enqueue(lii_handle h, const double* pos_dev, const double* pos, bo
   // the work list holds every cell entry of the map if it must: made here, on the host, in front of the launches (a rebuild may have
   // changed the number of blocks since the setting was made; nothing is in flight that uses the list)
   const size_t ne = size_t(std::max(h->n_blocks, 0)) * 512;
-  if (ne > size_t(h->work_cap)) {
-    h->work_cap = 0;
-    HIPCHK(h, h->d_work.grow(ne + ne / 2 + 4096));
-    h->work_cap = (unsigned int)h->d_work.size();
-  }
-  L.seq = L.seq == 0x7FFFFFFF ? 1 : L.seq + 1;
+  { const int r = work_reserve(h, ne, ne + ne / 2 + 4096); if (r != LII_OK) return r; }
+  L.seq = next_seq(L.seq);
   if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
   launch_local_map_tomb(L.d_state + L.cur, L.d_state + (L.cur ^ 1), L.P, pos_dev, pos, h->d_pts, h->d_cells, h->d_block_key, std::max(h->n_blocks, 0), h->cell_size,
                         h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
-  const lii::WinKeep wk = win_keep_view(h);
-  if (!wk.win && h->win_valid) { h->win_valid = false; h->win_dropped++; }  // (cell entries may change: a window that is not kept current goes)
+  const lii::WinKeep wk = win_keep_or_drop(h);  // (cell entries may change: a window that is not kept current goes)
   if (mark) { const int r = kp_mark(h, LII_KP_VOXEL); if (r != LII_OK) return r; }
   const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
   launch_cell_apply_listed(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, h->work_cap, wk, s, &rs);
@@ -509,6 +509,28 @@ int upload_xyz(lii_handle h, const void* xyz, int n, int stride_bytes, float4* d
   }
   return LII_OK;
 }
+// the boxes of a call -> pinned scratch -> the scratch of the index build (d_keys_b: max_map_points * 8 bytes, free between calls)
+int upload_boxes(lii_handle h, const char* who, const float* boxes, int n_boxes, float** d_boxes) {
+  static_assert(kMapBoxesMax == 4096, "the callers' messages name the limit");
+  *d_boxes = reinterpret_cast<float*>(h->d_keys_b.get());
+  if (size_t(n_boxes) * 24 > size_t(h->cfg.max_map_points) * 8)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": more boxes than the handle's scratch holds (max_map_points / 3)");
+  std::memcpy(h->h_small->boxes, boxes, sizeof(float) * 6 * size_t(n_boxes));
+  HIPCHK(h, hipMemcpyAsync(*d_boxes, h->h_small->boxes, sizeof(float) * 6 * size_t(n_boxes), hipMemcpyHostToDevice, h->stream));
+  return LII_OK;
+}
+// cnt float4 rows in device memory -> the caller's packed xyz, through the pinned staging buffer a piece of it at a time
+int download_xyz(lii_handle h, const float4* rows, size_t cnt, float* xyz_out) {
+  const size_t piece = std::max<size_t>(h->h_stage.size(), 1);
+  if (cnt > 0) HIPCHK(h, hipEventSynchronize(h->ev_stage));  // an asynchronous scan upload may still be reading the staging buffer
+  for (size_t at = 0; at < cnt; at += piece) {
+    const size_t m = std::min(piece, cnt - at);
+    HIPCHK(h, hipMemcpyAsync(h->h_stage, rows + at, sizeof(float4) * m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < m; i++) std::memcpy(xyz_out + 3 * (at + i), &h->h_stage[i], 12);  // (x, y, z: the head of the float4)
+  }
+  return LII_OK;
+}
 }  // namespace
 int lii_map_build(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
@@ -562,39 +584,32 @@ int lii_map_add_points(lii_handle h, const void* xyz, int32_t n, int32_t stride_
   h->have_search = false;
   rc = map_apply(h, h->d_batch, n, downsample_on != 0, nullptr, 0);
   if (rc != LII_OK) return rc;
-  int ev = 0;  // this entry point reports Add_Points' counter: one synchronising read (lii_map_incremental does not)
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 3090, h->d_mapctr + kMapCtrEvents, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  // this entry point reports Add_Points' counter: one synchronising read (lii_map_incremental does not)
+  HIPCHK(h, hipMemcpyAsync(&h->h_small->add_events, h->d_mapctr + kMapCtrEvents, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   rc = map_counters(h);  // synchronises; reports a capacity problem of this very update
   if (rc != LII_OK) return rc;
-  std::memcpy(&ev, h->h_small + 3090, sizeof(int));
-  if (n_added) *n_added = downsample_on ? ev : 0;
+  if (n_added) *n_added = downsample_on ? h->h_small->add_events : 0;
   return LII_OK;
 }
 int lii_map_delete_boxes(lii_handle h, const float* boxes, int32_t n_boxes, int32_t* n_deleted) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
-  if (!h || (!boxes && n_boxes > 0) || n_boxes < 0 || n_boxes > 4096) return fail(h, LII_ERR_INVALID, "lii_map_delete_boxes: bad arguments (<= 4096 boxes)");
+  if (!h || (!boxes && n_boxes > 0) || n_boxes < 0 || n_boxes > kMapBoxesMax) return fail(h, LII_ERR_INVALID, "lii_map_delete_boxes: bad arguments (<= 4096 boxes)");
   if (n_deleted) *n_deleted = 0;
   int rc = map_counters(h);
   if (rc != LII_OK) return rc;
   const int n_old = h->n_map;
   if (n_boxes == 0 || n_old == 0) return LII_OK;
   hipStream_t s = h->stream;
-  float* d_boxes = reinterpret_cast<float*>(h->d_keys_b.get());  // scratch of the index build (max_map_points * 8 bytes), free between calls
-  if (size_t(n_boxes) * 24 > size_t(h->cfg.max_map_points) * 8)
-    return fail(h, LII_ERR_INVALID, "lii_map_delete_boxes: more boxes than the handle's scratch holds (max_map_points / 3)");
-  std::memcpy(h->h_small + 4096, boxes, sizeof(float) * 6 * size_t(n_boxes));
-  HIPCHK(h, hipMemcpyAsync(d_boxes, h->h_small + 4096, sizeof(float) * 6 * size_t(n_boxes), hipMemcpyHostToDevice, s));
+  float* d_boxes = nullptr;
+  rc = upload_boxes(h, "lii_map_delete_boxes", boxes, n_boxes, &d_boxes);
+  if (rc != LII_OK) return rc;
   // in place: every cell walks its live points, the cells that lose points squeeze them out (k_cell_apply)
   const int ne = h->n_blocks * 512;
-  if ((unsigned int)ne > h->work_cap) {  // more cells than the work list holds: rebuild-free fallback is not worth it - grow the list
-    h->work_cap = 0;
-    HIPCHK(h, h->d_work.grow(size_t(ne) + 4096));
-    h->work_cap = (unsigned int)h->d_work.size();
-  }
+  rc = work_reserve(h, size_t(ne), size_t(ne) + 4096);  // more cells than the work list holds: rebuild-free fallback is not worth it - grow the list
+  if (rc != LII_OK) return rc;
   h->map_dirty = true;
   launch_box_tomb_cells(h->d_pts, h->d_cells, ne, d_boxes, n_boxes, h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
-  const lii::WinKeep wk = win_keep_view(h);
-  if (!wk.win) h->win_valid = false;
+  const lii::WinKeep wk = win_keep_or_drop(h);
   const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
   launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, ne, wk, s, &rs);
   launch_ins_write(h->d_pts, h->d_ins_e, 0, nullptr, nullptr, nullptr, 0, nullptr, h->d_cells, h->d_cell_cap, h->d_pts, h->d_mapctr, h->d_dropped, h->drop_cap,
@@ -616,18 +631,13 @@ int delete_points_enqueue(lii_handle h, const void* list_dev, int n, int stride_
   const long long ne = (long long)std::max(h->n_blocks, 0) * 512;
   const long long bound = std::min<long long>(8ll * n, ne);
   if (bound <= 0) return LII_OK;
-  if ((unsigned long long)bound > (unsigned long long)h->work_cap) {  // (nothing is in flight that uses the list: the counters have just been read)
-    h->work_cap = 0;
-    HIPCHK(h, h->d_work.grow(size_t(bound) + 4096));
-    h->work_cap = (unsigned int)h->d_work.size();
-  }
+  { const int r = work_reserve(h, size_t(bound), size_t(bound) + 4096); if (r != LII_OK) return r; }  // (nothing in flight uses the list: the counters have just been read)
   h->map_dirty = true;
   launch_point_tomb(grid_view(h), list_dev, n, stride_bytes, h->d_tomb, h->d_tp, h->d_work, h->d_mapctr, h->work_cap, s);
-  const lii::WinKeep wk = win_keep_view(h);
-  if (!wk.win) h->win_valid = false;
+  const lii::WinKeep wk = win_keep_or_drop(h);
   const lii::RemovedSink rs = removed_sink(h);  // (lii_map_removed_set: the squeeze hands what it drops to the history buffer - the same launch)
   launch_cell_apply(h->d_work, h->d_cells, h->d_cell_cap, h->d_pts, h->d_tomb, h->d_tp, h->d_mapctr, h->pts_cap_eff, int(bound), wk, s, &rs);
-  if (publish) h->map_seq = h->map_seq == 0x7FFFFFFF ? 1 : h->map_seq + 1;
+  if (publish) h->map_seq = next_seq(h->map_seq);
   launch_ins_write(h->d_pts, h->d_ins_e, 0, nullptr, nullptr, nullptr, 0, nullptr, h->d_cells, h->d_cell_cap, h->d_pts, h->d_mapctr, h->d_dropped, h->drop_cap,
                    s, publish ? h->h_mapflag.get() : nullptr, publish ? kMapCtrWords + 8 : 0, publish ? kMapFlagSeqAt : 0, publish ? h->map_seq : 0,
                    wk);  // (re-arms the work list)
@@ -688,36 +698,33 @@ int lii_map_range(lii_handle h, float range6[6]) {
     float* d_range = reinterpret_cast<float*>(partial + 256 * 6);
     launch_map_range(h->d_pts, h->d_cells, h->n_blocks * 512, partial, d_range, s);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->h_small + 3100, d_range, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->h_small->map_range, d_range, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
   }
   HIPCHK(h, hipStreamSynchronize(s));
-  if (h->n_map > 0) std::memcpy(range6, h->h_small + 3100, 6 * sizeof(float));
+  if (h->n_map > 0) std::memcpy(range6, h->h_small->map_range, 6 * sizeof(float));
   return LII_OK;
 }
 int lii_map_box_search(lii_handle h, const float* boxes, int32_t n_boxes, float* xyz_out, int32_t capacity, int32_t* n) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   if (!h) return LII_ERR_INVALID;
-  if (!n || (!boxes && n_boxes > 0) || n_boxes < 0 || n_boxes > 4096) return fail(h, LII_ERR_INVALID, "lii_map_box_search: bad arguments (<= 4096 boxes, n)");
+  if (!n || (!boxes && n_boxes > 0) || n_boxes < 0 || n_boxes > kMapBoxesMax) return fail(h, LII_ERR_INVALID, "lii_map_box_search: bad arguments (<= 4096 boxes, n)");
   *n = 0;
   int rc = map_counters(h);
   if (rc != LII_OK) return rc;
   if (n_boxes == 0 || h->n_map == 0) return LII_OK;
   hipStream_t s = h->stream;
-  float* d_boxes = reinterpret_cast<float*>(h->d_keys_b.get());  // scratch of the index build (max_map_points * 8 bytes), free between calls
-  if (size_t(n_boxes) * 24 > size_t(h->cfg.max_map_points) * 8)
-    return fail(h, LII_ERR_INVALID, "lii_map_box_search: more boxes than the handle's scratch holds (max_map_points / 3)");
-  std::memcpy(h->h_small + 4096, boxes, sizeof(float) * 6 * size_t(n_boxes));
-  HIPCHK(h, hipMemcpyAsync(d_boxes, h->h_small + 4096, sizeof(float) * 6 * size_t(n_boxes), hipMemcpyHostToDevice, s));
+  float* d_boxes = nullptr;
+  rc = upload_boxes(h, "lii_map_box_search", boxes, n_boxes, &d_boxes);
+  if (rc != LII_OK) return rc;
   unsigned long long* d_hits = reinterpret_cast<unsigned long long*>(h->d_cs_a.get());
   HIPCHK(h, hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), s));
   // (the hits land in the staging of gathers and rebuilds: it holds max_map_points, and a box holds no more than the map)
   const unsigned int room = xyz_out ? (unsigned int)std::min<size_t>(h->d_map_unsorted.size(), 0x7FFFFFFFu) : 0u;
   launch_box_gather(h->d_pts, h->d_cells, h->d_block_key, std::max(h->n_blocks, 0), h->cell_size, d_boxes, n_boxes, h->d_map_unsorted, room, d_hits, s);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 3110, d_hits, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&h->h_small->box_hits, d_hits, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  unsigned long long hits = 0;
-  std::memcpy(&hits, h->h_small + 3110, sizeof(hits));
+  const unsigned long long hits = h->h_small->box_hits;
   if (hits > (unsigned long long)0x7FFFFFFF) return fail(h, LII_ERR_HIP, "lii_map_box_search: counter out of range");
   const int cnt = int(hits);
   *n = cnt;
@@ -725,15 +732,7 @@ int lii_map_box_search(lii_handle h, const float* boxes, int32_t n_boxes, float*
   if (capacity < cnt) return fail(h, LII_ERR_CAPACITY, "lii_map_box_search: capacity too small");
   if (cnt == 0) return LII_OK;
   if ((unsigned int)cnt > room || size_t(cnt) > h->h_stage.size()) return fail(h, LII_ERR_CAPACITY, "lii_map_box_search: more hits than the handle's staging holds");
-  HIPCHK(h, hipEventSynchronize(h->ev_stage));  // an asynchronous scan upload may still be reading the staging buffer
-  HIPCHK(h, hipMemcpyAsync(h->h_stage, h->d_map_unsorted, sizeof(float4) * size_t(cnt), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  for (int i = 0; i < cnt; i++) {
-    xyz_out[3 * size_t(i)] = h->h_stage[i].x;
-    xyz_out[3 * size_t(i) + 1] = h->h_stage[i].y;
-    xyz_out[3 * size_t(i) + 2] = h->h_stage[i].z;
-  }
-  return LII_OK;
+  return download_xyz(h, h->d_map_unsorted, size_t(cnt), xyz_out);
 }
 int lii_local_map_set(lii_handle h, const lii_local_map_opts* opts) {
   if (!h) return LII_ERR_INVALID;
@@ -882,19 +881,8 @@ int lii_map_removed_acquire(lii_handle h, float* xyz_out, int32_t capacity, int3
   const char* const overflowed = "lii_map_removed_acquire: the history buffer overflowed - points were removed that it could not store (what it held is intact)";
   if (!xyz_out) return reserved > held ? fail(h, LII_ERR_CAPACITY, overflowed) : LII_OK;  // (the count only: nothing is delivered, so nothing is cleared either)
   if (capacity < held) return fail(h, LII_ERR_CAPACITY, "lii_map_removed_acquire: capacity too small");
-  // through the pinned staging buffer, a piece of it at a time (the history may be larger than the map)
-  const size_t piece = std::max<size_t>(h->h_stage.size(), 1);
-  if (held > 0) HIPCHK(h, hipEventSynchronize(h->ev_stage));  // an asynchronous scan upload may still be reading the staging buffer
-  for (size_t at = 0; at < size_t(held); at += piece) {
-    const size_t m = std::min(piece, size_t(held) - at);
-    HIPCHK(h, hipMemcpyAsync(h->h_stage, R.d_buf + at, sizeof(float4) * m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < m; i++) {
-      xyz_out[3 * (at + i)] = h->h_stage[i].x;
-      xyz_out[3 * (at + i) + 1] = h->h_stage[i].y;
-      xyz_out[3 * (at + i) + 2] = h->h_stage[i].z;
-    }
-  }
+  rc = download_xyz(h, R.d_buf, size_t(held), xyz_out);  // (in pieces: the history may be larger than the map)
+  if (rc != LII_OK) return rc;
   if (clear) {
     R.collected_base += held;
     R.lost_base += reserved - held;
@@ -939,14 +927,7 @@ int lii_map_download(lii_handle h, float* xyz_out, int32_t capacity, int32_t* n)
   rc = map_gather(h, &cnt);  // the live points, cell by cell (the array itself has slack between the cells)
   if (rc != LII_OK) return rc;
   *n = cnt;
-  HIPCHK(h, hipMemcpyAsync(h->h_stage, h->d_map_unsorted, sizeof(float4) * size_t(cnt), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (int i = 0; i < cnt; i++) {
-    xyz_out[3 * size_t(i)] = h->h_stage[i].x;
-    xyz_out[3 * size_t(i) + 1] = h->h_stage[i].y;
-    xyz_out[3 * size_t(i) + 2] = h->h_stage[i].z;
-  }
-  return LII_OK;
+  return download_xyz(h, h->d_map_unsorted, size_t(cnt), xyz_out);
 }
 int lii_map_commit(lii_handle h) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
@@ -965,6 +946,18 @@ struct NearestPlan {
   float max_d2;  // the largest float <= max_dist: `float d2 <= double max_dist` (Search, :842) in float
   int r_max;     // rings of cells that cover the ball of radius sqrt(max_dist)
 };
+// max_dist bounds the squared distance of a float comparison: the largest float not above it
+float max_d2_of(double max_dist) {
+  const float md = float(max_dist);
+  return double(md) > max_dist ? std::nextafterf(md, 0.f) : md;
+}
+// ... and the refusal of a ball that reaches further than the search walks (each query decides by its own rule whether it does)
+int refuse_reach(lii_handle h, const char* who, double max_dist) {
+  char msg[256];
+  std::snprintf(msg, sizeof(msg), "%s: a ball of radius sqrt(max_dist) = %.3f m spans more than 32 grid cells of %.3f m; create the handle with a larger map_cell_size",
+                who, std::sqrt(max_dist), double(h->cell_size));
+  return fail(h, LII_ERR_INVALID, msg);
+}
 // The argument rules both forms share; LII_OK with n == 0 means "nothing to do".  Nothing has been touched when this fails.
 int nearest_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int32_t stride_bytes, int32_t k, double max_dist, const void* count_out,
                  NearestPlan* plan) {
@@ -976,15 +969,8 @@ int nearest_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int3
   // depends on the shape of its tree, and there is no rule to reproduce
   if (!(max_dist >= 1.0) || !std::isfinite(max_dist)) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_dist must be finite and >= 1 (it bounds the SQUARED distance)");
   const double cells = std::sqrt(max_dist) / double(h->cell_size);
-  if (cells > 32.0) {
-    char msg[256];
-    std::snprintf(msg, sizeof(msg), "%s: a ball of radius sqrt(max_dist) = %.3f m spans more than 32 grid cells of %.3f m; create the handle with a larger map_cell_size",
-                  who, std::sqrt(max_dist), double(h->cell_size));
-    return fail(h, LII_ERR_INVALID, msg);
-  }
-  float md = float(max_dist);
-  if (double(md) > max_dist) md = std::nextafterf(md, 0.f);
-  plan->max_d2 = md;
+  if (cells > 32.0) return refuse_reach(h, who, max_dist);
+  plan->max_d2 = max_d2_of(max_dist);
   plan->r_max = int(std::ceil(cells)) + 1;
   return LII_OK;
 }
@@ -993,6 +979,20 @@ int nearest_map(lii_handle h, const char* who) {
   const int rc = commit_map(h);
   if (rc != LII_OK) return rc;
   if (h->n_map <= 0 && !h->map_dirty) return fail(h, LII_ERR_STATE, std::string(who) + ": no map");
+  return LII_OK;
+}
+// The handle's query staging with room for `rows` result rows (and min(rows, kQueriesMax) queries), grown geometrically up to kRowsMax -
+// a host whose batches creep upwards frees (hipFree waits for the device) a handful of times at most - and beyond it only as far as asked.
+int query_staging(lii_handle h, size_t rows) {
+  using MQ = lii_context::MapQuery;
+  if (rows <= h->mq.rows) return LII_OK;
+  rows = std::max(rows, std::min(2 * h->mq.rows, MQ::kRowsMax));
+  const size_t bytes = 16 * std::min(rows, MQ::kQueriesMax) + 16 * rows;
+  h->mq.rows = 0;
+  h->mq.h_buf.reset();
+  HIPCHK(h, h->mq.d_buf.grow(bytes));
+  HIPCHK(h, h->mq.h_buf.alloc(bytes, hipHostMallocDefault));
+  h->mq.rows = rows;
   return LII_OK;
 }
 void nearest_launch(lii_handle h, const NearestPlan& plan, const void* q_dev, int n, int stride_bytes, int k, float* pts_dev, float* d2_dev, int* count_dev) {
@@ -1025,16 +1025,8 @@ int lii_map_nearest(lii_handle h, const void* xyz, int32_t n, int32_t stride_byt
   using MQ = lii_context::MapQuery;
   // a chunk: at most kQueriesMax queries and kRowsMax rows - the staging stays bounded whatever n is
   const size_t chunk = std::min<size_t>(std::min<size_t>(size_t(n), MQ::kQueriesMax), MQ::kRowsMax / size_t(k));
-  if (chunk * size_t(k) > h->mq.rows) {
-    // (grown geometrically, so that a host whose batches creep upwards frees - hipFree waits for the device - a handful of times at most)
-    const size_t rows = std::min(std::max(chunk * size_t(k), 2 * h->mq.rows), MQ::kRowsMax);
-    const size_t bytes = 16 * std::min(rows, MQ::kQueriesMax) + 16 * rows;
-    h->mq.rows = 0;
-    h->mq.h_buf.reset();
-    HIPCHK(h, h->mq.d_buf.grow(bytes));
-    HIPCHK(h, h->mq.h_buf.alloc(bytes, hipHostMallocDefault));
-    h->mq.rows = rows;
-  }
+  rc = query_staging(h, chunk * size_t(k));  // (chunk * k <= kRowsMax, so max(rows, min(2 old, kRowsMax)) = min(max(rows, 2 old), kRowsMax): doubling, capped at kRowsMax)
+  if (rc != LII_OK) return rc;
   const size_t q_cap = std::min(h->mq.rows, MQ::kQueriesMax);
   const size_t off_cnt = 12 * q_cap, off_pts = 16 * q_cap, off_d2 = off_pts + 12 * h->mq.rows;
   unsigned char *hb = h->mq.h_buf, *db = h->mq.d_buf;
@@ -1072,15 +1064,8 @@ int radius_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int32
   if (!(max_dist >= 0.0) || !std::isfinite(max_dist)) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_dist must be finite and >= 0 (it bounds the SQUARED distance)");
   // sqrt(max_dist) > 32 cells, decided without a rounding: the cell size is a float, so the square of 32 cells is exact in a double
   const double reach = 32.0 * double(h->cell_size);
-  if (max_dist > reach * reach) {
-    char msg[256];
-    std::snprintf(msg, sizeof(msg), "%s: a ball of radius sqrt(max_dist) = %.3f m spans more than 32 grid cells of %.3f m; create the handle with a larger map_cell_size",
-                  who, std::sqrt(max_dist), double(h->cell_size));
-    return fail(h, LII_ERR_INVALID, msg);
-  }
-  float md = float(max_dist);
-  if (double(md) > max_dist) md = std::nextafterf(md, 0.f);
-  plan->max_d2 = md;
+  if (max_dist > reach * reach) return refuse_reach(h, who, max_dist);
+  plan->max_d2 = max_d2_of(max_dist);
   plan->r_max = std::min(int(std::ceil(std::sqrt(max_dist) / double(h->cell_size))) + 1, 34);
   return LII_OK;
 }
@@ -1089,19 +1074,6 @@ template <class T>
 hipError_t radius_room(DevBuf<T>& b, size_t n) {  // (grown geometrically; grow frees first, and hipFree waits for the device)
   return b.size() >= n ? hipSuccess : b.grow(std::max(n, 2 * b.size()));
 }
-}
-// the handle's query staging with room for `rows` result rows (and min(rows, kQueriesMax) queries): the buffers of lii_map_nearest
-int radius_staging(lii_handle h, size_t rows) {
-  using MQ = lii_context::MapQuery;
-  if (rows <= h->mq.rows) return LII_OK;
-  rows = std::max(rows, std::min(2 * h->mq.rows, MQ::kRowsMax));
-  const size_t bytes = 16 * std::min(rows, MQ::kQueriesMax) + 16 * rows;
-  h->mq.rows = 0;
-  h->mq.h_buf.reset();
-  HIPCHK(h, h->mq.d_buf.grow(bytes));
-  HIPCHK(h, h->mq.h_buf.alloc(bytes, hipHostMallocDefault));
-  h->mq.rows = rows;
-  return LII_OK;
 }
 struct RadiusView {
   GridView g;
@@ -1187,7 +1159,7 @@ int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_byte
   if (rc != LII_OK) return rc;
   using MQ = lii_context::MapQuery;
   const size_t block = std::min<size_t>(size_t(n), MQ::kQueriesMax);  // queries counted by one launch
-  rc = radius_staging(h, block + 1);
+  rc = query_staging(h, block + 1);
   if (rc != LII_OK) return rc;
   HIPCHK(h, radius_room(h->mr.d_off, block + 1));
   hipStream_t s = h->stream;
@@ -1234,7 +1206,7 @@ int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_byte
       rows_max = std::max(rows_max, size_t(offsets_out[b] - offsets_out[a]));
       a = b;
     }
-  rc = radius_staging(h, std::max(rows_max, block + 1));
+  rc = query_staging(h, std::max(rows_max, block + 1));
   if (rc != LII_OK) return rc;
   const size_t q_cap = std::min(h->mq.rows, MQ::kQueriesMax);
   const size_t off_pts = 16 * q_cap, off_d2 = off_pts + 12 * h->mq.rows;
@@ -1343,11 +1315,10 @@ int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, in
   // (voxel keys, the batch sort, the per-voxel fold, the insert compaction) is launched for the exact count instead of the
   // scan-sized bound - one small host round trip (~15 us) against ~80 us of kernels working on padding.
   // (the same round trip brings the map's counters up to date: the previous update ran without a synchronisation)
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 3090, h->d_counts, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(h->h_small + 3072, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, s));
+  const int* n_lists = h->h_small->list_counts;
+  HIPCHK(h, hipMemcpyAsync(h->h_small->list_counts, h->d_counts, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(h->h_small->map_ctr, h->d_mapctr, sizeof(int) * kMapCtrWords, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
-  int n_lists[6];
-  std::memcpy(n_lists, h->h_small + 3090, sizeof(n_lists));
   if (exchange && n_lists[5])
     return fail(h, LII_ERR_COMM, "list exchange timed out (a rank of the job did not reach this map update); re-create the communicator");
   {

@@ -34,7 +34,7 @@ int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double*
   if (prof) HIPCHK(h, hipEventRecord(h->prof.ev[0], h->stream));
   // the pose of a host-driven pass travels to the handle's pose slot first: the kernels read it from device memory on every path
   {
-    PoseArg* stage = reinterpret_cast<PoseArg*>(h->h_small + 20000);  // (pinned, a stretch nothing else uses; this call ends with a synchronisation)
+    PoseArg* stage = &h->h_small->pose;  // (pinned, a member of its own; this call ends with a synchronisation)
     *stage = pose_of(*st);
     HIPCHK(h, hipMemcpyAsync(h->d_pose, stage, sizeof(PoseArg), hipMemcpyHostToDevice, h->stream));
   }
@@ -54,9 +54,9 @@ int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double*
   } else if (h->net.mailbox.dev_slots) {
     launch_mailbox_allreduce(h->d_out91, mailbox_view(h), h->stream);
   }
-  HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_out91, sizeof(double) * kNormalEq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->h_small->normal_eq, h->d_out91, sizeof(double) * kNormalEq, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  std::memcpy(out91, h->h_small, sizeof(double) * kNormalEq);
+  std::memcpy(out91, h->h_small->normal_eq, sizeof(double) * kNormalEq);
   if (h->net.mailbox.dev_slots && out91[kNormalEq - 1] != out91[kNormalEq - 1])
     return fail(h, LII_ERR_COMM, "mailbox exchange timed out (a rank of the job did not reach this pass)");
   if (prof) {

@@ -28,6 +28,35 @@ using lii::BlockEntry; using lii::IekfCtrl; using lii::IekfResult; using lii::Po
 using lii::DevBuf; using lii::PinnedBuf;
 constexpr size_t kCtrlBytes = (sizeof(lii::IekfCtrl) + 255) / 256 * 256;
 
+// ---- the handle's small pinned scratch (lii_context::h_small): where a few words travel between the host and the device.  One member
+// per use, free again when the call that used it has returned (each ends with a synchronisation of its stream); what an argument check
+// enforces is the member's extent.
+constexpr int kMapBoxesMax = 4096;  // boxes of one lii_map_delete_boxes / lii_map_box_search
+constexpr int kImuSamplesMax = 63;  // IMU samples of one scan (lii_capi_imu.cpp: check_feed); the pose table holds one pose more
+constexpr int kGxRanksMax = 128;    // ranks of a job whose map lists travel over RCCL (lii_capi_comm.cpp: gx_prepare)
+constexpr int kCalibEvalParams = 24, kCalibEvalOut = 9 * 9 + 9 + 1;  // lii_calib_eval: stage 3 has the most parameters and outputs
+constexpr int kLiInitBackDoubles = 128;  // lii_li_init_resident: its control and result block (kSmallDoubles, lii_li_init_resident.hip)
+struct PinnedScratch {
+  double normal_eq[lii::kNormalEq];        // iterate: the sums of a host-driven pass
+  double calib_params[kCalibEvalParams];   // lii_calib_eval: in,
+  double calib_out[kCalibEvalOut];         // ... out: JtJ | Jtr | cost
+  double li_init_back[kLiInitBackDoubles]; // lii_li_init_resident: ResCtl | ResOut
+  lii_calib_result calib_stage;            // lii_calib_solve_stage_dev: in and out
+  lii::PoseArg pose;                       // iterate: the pose on its way to d_pose
+  lii_pose6d imu_poses[kImuSamplesMax + 1];  // lii_imu_propagate: the pose table
+  unsigned long long box_hits;             // lii_map_box_search: the hit counter
+  unsigned char gx_headers[kGxRanksMax * lii::kGatherHeaderBytes];  // gx_gather_collect: every rank's list header
+  float boxes[kMapBoxesMax * 6];           // lii_map_delete_boxes / lii_map_box_search: the boxes on their way to the device
+  float map_range[6];                      // lii_map_range
+  unsigned int index_blocks;               // build_index: blocks of the new index
+  unsigned int win_box[6];                 // build_index: the box of the occupied blocks
+  unsigned int gather_count;               // map_gather: live points
+  int n_body[2];                           // resolve_n_body: d_nbody
+  int map_ctr[lii::kMapCtrWords];          // read_counters / lii_map_incremental: d_mapctr
+  int list_counts[6];                      // lii_map_incremental: d_counts
+  int add_events;                          // lii_map_add_points: kMapCtrEvents
+};
+
 // A resource of the handle is a member of an owning type (lii_owned.h) and goes with the handle; a raw pointer here is an alias
 // into one of them, or memory of somebody else, and its comment says which.
 struct lii_context {
@@ -55,8 +84,8 @@ struct lii_context {
   DevBuf<unsigned long long> d_block_key;  // packed block coordinates by block id (WinKeep::key_of_id), cells_cap_blocks entries
   bool map_tight = false;       // LII_TEST=map_tight: no spare room is provisioned (tests: forces the recovery path)
   long long map_recoveries = 0;
-  DevBuf<float4> d_ins, d_ins_c;         // fold output / compacted inserts or host batches (M each)
-  DevBuf<unsigned int> d_u32_a, d_u32_b, d_u32_c;  // flags / ranks (max(N, M) each)
+  DevBuf<float4> d_ins;         // fold output (M)
+  DevBuf<unsigned int> d_u32_a, d_u32_b;  // flags / ranks (max(N, M) each)
   DevBuf<float4> d_list_add, d_list_nodown;  // map_incremental lists (N each)
   int* d_counts = nullptr;      // inside d_mapctr, behind the kMapCtrWords counters: [0] add list, [1] no-downsample list, [2] alive, [3] inserted, [4] total, [5] events
   DevBuf<float4> d_map_unsorted;
@@ -88,17 +117,15 @@ struct lii_context {
   DevBuf<int> d_mapctr;            // kMapCtr* counters
   int n_used = 0;                     // host copy of kMapCtrUsed as of the last map_counters()
   bool map_dirty = false;             // an update has been enqueued since the last map_counters(): n_map / n_used / n_blocks are stale
-  DevBuf<unsigned long long> d_keys_a, d_keys_b, d_keys_c;
+  DevBuf<unsigned long long> d_keys_a, d_keys_b;
   DevBuf<unsigned int> d_idx_a, d_idx_b;
   DevBuf<BlockEntry> d_blocks;   // capacity-managed (grows on demand)
   unsigned int block_mask = 0;      // d_blocks.size() - 1
   DevBuf<uint2> d_cells;         // capacity-managed: 512 entries per occupied block
   size_t cells_cap_blocks = 0;      // = d_block_key.size(): blocks the six cell tables hold (build_index)
   int n_blocks = 0;
-  DevBuf<unsigned int> d_counter;
   int partial_stride = 0;
   int n_map = 0;
-  PinnedBuf<int> n_map_pinned;  // small pinned scratch for H2D of counters
   float cell_size = 0.3f;
   DevBuf<unsigned char> d_sort_temp;  // temporary storage of the sorts and scans (size(): bytes)
   // lii_map_nearest (host form): staging for one chunk of queries and its results, device and pinned, laid out alike (queries |
@@ -276,7 +303,7 @@ struct lii_context {
 
   // ---- pinned staging
   PinnedBuf<float4> h_stage;     // max(max_scan, max_map) float4
-  PinnedBuf<double> h_small;     // 32 768 doubles
+  PinnedBuf<PinnedScratch> h_small;  // one record: the small scratch, member by member (above)
 
   // ---- calibration
   struct CalibState {  // lii_capi_calib.cpp: the LI_init evaluators' buffers
@@ -460,7 +487,6 @@ int map_update_early(lii_handle h);  // 1: enqueued behind the passes of the upd
 int commit_map(lii_handle h);
 int map_counters(lii_handle h, bool already_synced = false);
 lii::RemovedSink removed_sink(lii_handle h);  // the history buffer as the launches of a box delete take it (buf == nullptr: nothing is collected)
-lii::WinKeep win_keep_view(lii_handle h);  // the window as the update's launches keep it current (win == nullptr: nothing to keep)
 // one lasermap_fov_segment + Delete_Point_Boxes on the handle's stream (three launches); pos_dev: state.pos_end in device memory, else pos by
 // value.  The caller has joined the map update in flight.  mark: lii_set_profiling(h, 3) brackets the launches (LII_KP_VOXEL)
 int local_map_enqueue(lii_handle h, const double* pos_dev, const double* pos, bool mark);

@@ -905,7 +905,8 @@ int lii_li_init_resident(lii_handle h, const lii_li_init_job* job, lii_calib_res
   hipLaunchKernelGGL(k_res_stage3_prep, one, wg, 0, s, ctl, ro, L.imu, L.lid, L.imu3, L.lid3, h->cal.d_cal_imu.get(), h->cal.d_cal_lidar.get()); launches++;
   launch_calib_lm(3, ctl, 2, L.imu3, L.lid3, 0, ro, s); launches++;
   static_assert(sizeof(ResCtl) % 8 == 0, "the result block follows the control block");
-  double* back = h->h_small + 1024;
+  static_assert(kSmallDoubles <= kLiInitBackDoubles, "PinnedScratch::li_init_back holds the control and the result block");
+  double* back = h->h_small->li_init_back;
   HIPCHK(h, hipMemcpyAsync(back, r.d_small, sizeof(double) * kSmallDoubles, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));  // the one wait
   HIPCHK(h, hipGetLastError());
@@ -965,7 +966,7 @@ int lii_calib_solve_stage_dev(lii_handle h, int32_t stage, lii_calib_result* io)
   const int rc = ensure_small(h);
   if (rc != LII_OK) return rc;
   ResOut* ro = out_of(h);
-  lii_calib_result* stage_io = reinterpret_cast<lii_calib_result*>(h->h_small + 1024);
+  lii_calib_result* stage_io = &h->h_small->calib_stage;
   *stage_io = *io;
   HIPCHK(h, hipMemcpyAsync(&ro->res, stage_io, sizeof(lii_calib_result), hipMemcpyHostToDevice, h->stream));
   launch_calib_lm(stage, nullptr, 0, h->cal.d_cal_imu, h->cal.d_cal_lidar, h->cal.n_cal, ro, h->stream);

@@ -453,6 +453,84 @@ def test_refusals():
     reg.map_delete_points_dev(d, len(p))
     assert reg.map_size() == 0
     reg.close()
+    # ... and the largest requests the argument checks let through, next to each other in one handle
+    _largest_requests_side_by_side()
+
+
+def _canon(a):
+    """The rows of a (n, 3) float32 array in the order of their bits, as bytes: equal for equal multisets of rows."""
+    v = np.ascontiguousarray(a, np.float32).reshape(-1, 3).view(np.uint32)
+    return v[np.lexsort(v.T[::-1])].tobytes()
+
+
+def _largest_requests_side_by_side():
+    """4096 boxes into lii_map_delete_boxes and lii_map_box_search (lii_map_size and lii_map_range between them) and 63 IMU samples into
+    lii_imu_propagate, on ONE handle, the delete in front of the others and behind them: every call gives the bits it gives alone on a
+    fresh handle, and those are numpy's (min <= p < max; the recorded reference run of the n63 case is held in test_gpu_imu_propagate.py)."""
+    import lidar_imu_init_amd as lii
+    rng = np.random.default_rng(42)
+    base = _unique_points(rng, 2_000)
+    outside = lambda n: _one_ulp_boxes(rng.uniform(20, 30, (n, 3)).astype(np.float32))
+    del_boxes = np.concatenate([_one_ulp_boxes(base[rng.choice(len(base), 300, replace=False)]), outside(4096 - 300)])
+    del_boxes = np.ascontiguousarray(del_boxes[rng.permutation(4096)])
+    lo = rng.uniform(-10, 8, (96, 3)).astype(np.float32)
+    find_boxes = np.concatenate([_one_ulp_boxes(base[rng.choice(len(base), 500, replace=False)]), np.c_[lo, lo + np.float32(2.0)], outside(3500)])
+    find_boxes = np.ascontiguousarray(find_boxes[rng.permutation(4096)], np.float32)
+    assert del_boxes.shape == find_boxes.shape == (4096, 6)
+    dead = MC.in_boxes(base, del_boxes)
+    left = base[~dead]
+    assert int(dead.sum()) == 300
+    F = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "imu", "reference_propagation.npz"))
+    c = {k: F[f"lio/n63/in/{k}"] for k in ("state", "imu", "last_imu", "last_end", "acc_s_last", "angvel_last", "beg", "pts", "cov_gyr", "cov_acc")}
+    assert len(c["imu"]) == 63
+
+    def fresh(map_pts=None):
+        reg = _registrar(max_scan_points=1_000, max_map_points=16_000)
+        if map_pts is not None:
+            reg.map_build(map_pts)
+        return reg
+
+    def delete(reg):
+        return reg.map_delete_boxes(del_boxes), _canon(reg.map_download())
+
+    def imu(reg):
+        reg.set_imu_noise(cov_gyr=c["cov_gyr"], cov_acc=c["cov_acc"], mean_acc_norm=9.805)
+        reg.imu_carry = dict(last_imu=c["last_imu"], acc_s_last=c["acc_s_last"], angvel_last=c["angvel_last"], last_lidar_end_time=float(c["last_end"]))
+        beg = float(c["beg"])
+        st, poses = reg.propagate_imu(c["imu"], beg, beg + float(c["pts"][-1, 3]) / 1000.0, lii.State(c["state"]))
+        carry = reg.imu_carry
+        assert len(poses) == 64
+        return st.pod.tobytes(), poses.tobytes(), np.r_[carry["last_imu"], carry["acc_s_last"], carry["angvel_last"], carry["last_lidar_end_time"]].tobytes()
+
+    queries = (("size", lambda reg: reg.map_size()), ("range", lambda reg: reg.map_range().tobytes()),
+               ("search", lambda reg: _canon(reg.map_box_search(find_boxes))))
+
+    def alone(call, map_pts=None):
+        reg = fresh(map_pts)
+        out = call(reg)
+        reg.close()
+        return out
+
+    solo = {"delete": alone(delete, base), "imu": alone(imu)}
+    assert solo["delete"] == (300, _canon(left))
+    for tag, m in (("whole", base), ("left", left)):
+        for name, call in queries:
+            solo[tag, name] = alone(call, m)
+        assert solo[tag, "size"] == len(m) and solo[tag, "range"] == _range_of(m).tobytes()
+        assert solo[tag, "search"] == _canon(m[MC.in_boxes(m, find_boxes)])
+    print(f"4096 boxes delete {solo['delete'][0]} of {len(base)} points; 4096 boxes hold {len(solo['whole', 'search']) // 12} / {len(solo['left', 'search']) // 12} points")
+    assert 500 < len(solo["whole", "search"]) // 12 > len(solo["left", "search"]) // 12
+    for delete_first in (True, False):
+        reg = fresh(base)
+        if delete_first:
+            assert delete(reg) == solo["delete"]
+        tag = "left" if delete_first else "whole"
+        for name, call in queries:
+            assert call(reg) == solo[tag, name], (delete_first, name)
+        assert imu(reg) == solo["imu"], delete_first
+        if not delete_first:
+            assert delete(reg) == solo["delete"]
+        reg.close()
 
 
 def test_under_host_solve():
