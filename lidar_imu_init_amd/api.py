@@ -405,6 +405,36 @@ def scan_sorted_value(scan_sorted) -> int:
     return 1 if scan_sorted else 0
 
 
+def _scan_job(undistort, imu_poses, leaf, max_iterations, imu_en, scan_dev, scan_sorted, map_update, next_scan, while_waiting):
+    """A lii_scan_job of the current ABI, and the objects that must stay alive with it (the pose array, the WAIT_HOOK thunk)."""
+    job = lii_scan_job()
+    job.struct_size = C.sizeof(lii_scan_job)
+    job.undistort = int(undistort)
+    job.scan_sorted = scan_sorted_value(scan_sorted)
+    job.map_update = 1 if map_update else 0
+    if scan_dev is not None:
+        job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
+    if next_scan is not None:  # a device_scan() handle: the scan the NEXT call will bring (lii_scan_job::next_scan_dev - its prologue is pre-armed)
+        job.next_scan_dev, job.next_n_scan = next_scan[0], next_scan[1]
+    hook = None
+    if while_waiting is not None:  # a Python callable: runs once inside the call, when every launch is enqueued (lii_scan_job::while_waiting)
+        hook = WAIT_HOOK(lambda _arg: while_waiting())
+        job.while_waiting = C.cast(hook, C.c_void_p)
+    poses = None
+    if imu_poses is not None:
+        poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
+        job.imu_poses, job.n_imu_poses = _ptr(poses), len(poses)
+    job.leaf = float(leaf)
+    job.opts = lii_iekf_opts(int(max_iterations), int(imu_en))
+    return job, (poses, hook)
+
+
+def _report(rep):
+    """The report dict of a lii_iekf_report."""
+    return dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
+                converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+
+
 def pose6d_array(n):
     """n x 22 doubles: offset_time, acc[3], gyr[3], vel[3], pos[3], rot[9] (msg/Pose6D.msg)."""
     return np.zeros((n, 22))
@@ -861,8 +891,7 @@ class Registrar:
         opts = lii_iekf_opts(int(max_iterations), int(imu_en))
         rep = lii_iekf_report()
         self._check(self.L.lii_iekf_update(self.h, _ptr(state.pod), _ptr(state_prop.pod), C.byref(opts), C.byref(rep)))
-        return dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
-                    converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+        return _report(rep)
 
     def scan_register(self, state: State, state_prop: State, *, imu_poses=None, cv=False, leaf=0.0, max_iterations=4,
                       imu_en=False, scan_dev=None, scan_sorted=False, map_update=False, next_scan=None, while_waiting=None):
@@ -871,30 +900,11 @@ class Registrar:
         points are in ascending time order; 2 / "sort" - the library sorts them by time on the device first
         (lii_scan_job::scan_sorted; register_imu and register_cv take the same values).  map_update: map_incremental with the final state
         follows inside the call (lii_scan_job::map_update) - do not call map_incremental() for this scan."""
-        job = lii_scan_job()
-        job.struct_size = C.sizeof(lii_scan_job)
-        job.scan_sorted = scan_sorted_value(scan_sorted)
-        job.map_update = 1 if map_update else 0
-        if scan_dev is not None:
-            job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
-        if next_scan is not None:  # a device_scan() handle: the scan the NEXT call will bring (lii_scan_job::next_scan_dev - its prologue is pre-armed)
-            job.next_scan_dev, job.next_n_scan = next_scan[0], next_scan[1]
-        hook = None
-        if while_waiting is not None:  # a Python callable: runs once inside the call, when every launch is enqueued (lii_scan_job::while_waiting)
-            hook = WAIT_HOOK(lambda _arg: while_waiting())
-            job.while_waiting = C.cast(hook, C.c_void_p)
-        poses = None
-        if imu_poses is not None:
-            poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
-            job.undistort, job.imu_poses, job.n_imu_poses = 1, _ptr(poses), len(poses)
-        elif cv:
-            job.undistort = 2
-        job.leaf = float(leaf)
-        job.opts = lii_iekf_opts(int(max_iterations), int(imu_en))
+        job, _alive = _scan_job(1 if imu_poses is not None else (2 if cv else 0), imu_poses, leaf, max_iterations, imu_en, scan_dev, scan_sorted,
+                                map_update, next_scan, while_waiting)
         rep = lii_iekf_report()
         self._check(self.L.lii_scan_register(self.h, C.byref(job), _ptr(state.pod), _ptr(state_prop.pod), C.byref(rep)))
-        return dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
-                    converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+        return _report(rep)
 
     # ------------------------------------------------------------------ IMU processing (ImuProcess::Process on the device)
     def set_imu_noise(self, cov_gyr=None, cov_acc=None, cov_bias_gyr=None, cov_bias_acc=None, cov_R_LI=None, cov_T_LI=None,
@@ -956,31 +966,12 @@ class Registrar:
         state after the previous update and is updated in place.  Returns (state, propagated state or None, report dict).  The
         keywords are scan_register's; imu_poses must stay None (the table is formed on the device)."""
         imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
-        job = lii_scan_job()
-        job.struct_size = C.sizeof(lii_scan_job)
-        job.undistort = 1
-        job.scan_sorted = scan_sorted_value(scan_sorted)
-        job.map_update = 1 if map_update else 0
-        if scan_dev is not None:
-            job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
-        if next_scan is not None:
-            job.next_scan_dev, job.next_n_scan = next_scan[0], next_scan[1]
-        hook = None
-        if while_waiting is not None:
-            hook = WAIT_HOOK(lambda _arg: while_waiting())
-            job.while_waiting = C.cast(hook, C.c_void_p)
-        poses = None
-        if imu_poses is not None:
-            poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
-            job.imu_poses, job.n_imu_poses = _ptr(poses), len(poses)
-        job.leaf = float(leaf)
-        job.opts = lii_iekf_opts(int(max_iterations), int(imu_en))
+        job, _alive = _scan_job(1, imu_poses, leaf, max_iterations, imu_en, scan_dev, scan_sorted, map_update, next_scan, while_waiting)
         rep = lii_iekf_report()
         prop = State() if want_propagated else None
         self._check(self.L.lii_scan_register_imu(self.h, C.byref(job), _ptr(imu) if len(imu) else None, len(imu), float(pcl_beg_time),
                                                  _ptr(state.pod), _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
-        return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
-                                 converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+        return state, prop, _report(rep)
 
     def register_cv(self, dt, cov_gyr_scale, cov_acc_scale, state: State, *, leaf=0.0, max_iterations=4, scan_dev=None, scan_sorted=False,
                     map_update=False, while_waiting=None, imu_poses=None, want_propagated=True, undistort=2):
@@ -989,30 +980,13 @@ class Registrar:
         (state, propagated state or None, report dict).  imu_poses must stay None and undistort 2 (the rules' tests pass others)."""
         cg = None if cov_gyr_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cov_gyr_scale, np.float64), (3,)))
         ca = None if cov_acc_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cov_acc_scale, np.float64), (3,)))
-        job = lii_scan_job()
-        job.struct_size = C.sizeof(lii_scan_job)
-        job.undistort = int(undistort)
-        job.scan_sorted = scan_sorted_value(scan_sorted)
-        job.map_update = 1 if map_update else 0
-        if scan_dev is not None:
-            job.scan_dev, job.n_scan_dev = scan_dev[0], scan_dev[1]
-        hook = None
-        if while_waiting is not None:
-            hook = WAIT_HOOK(lambda _arg: while_waiting())
-            job.while_waiting = C.cast(hook, C.c_void_p)
-        poses = None
-        if imu_poses is not None:
-            poses = np.ascontiguousarray(imu_poses, np.float64).reshape(-1, 22)
-            job.imu_poses, job.n_imu_poses = _ptr(poses), len(poses)
-        job.leaf = float(leaf)
-        job.opts = lii_iekf_opts(int(max_iterations), 0)
+        job, _alive = _scan_job(undistort, imu_poses, leaf, max_iterations, 0, scan_dev, scan_sorted, map_update, None, while_waiting)
         rep = lii_iekf_report()
         prop = State() if want_propagated else None
         self._check(self.L.lii_scan_register_cv(self.h, C.byref(job), float(dt), _ptr(cg) if cg is not None else None,
                                                 _ptr(ca) if ca is not None else None, _ptr(state.pod),
                                                 _ptr(prop.pod) if prop is not None else None, C.byref(rep)))
-        return state, prop, dict(iterations=rep.iterations, searches=rep.searches, effect_num=rep.effect_num,
-                                 converged=bool(rep.converged), normal_eq=np.array(rep.normal_eq[:]))
+        return state, prop, _report(rep)
 
     # ------------------------------------------------------------------ the registered clouds (publish_frame_world / pcd_save)
     def publish_set(self, clouds=0, to_host=False, save_capacity=0):

@@ -100,6 +100,17 @@ bool fuse_filter(lii_handle h, float leaf) {
   if (h->vh.part_world > 1) return true;
   return h->vh_mode == 1 && (h->vh_pinned || leaf == h->vh_leaf);
 }
+DeskewPlan deskew_plan(lii_handle h, const float4* in, float4* out, int n, bool sorted, const unsigned long long* extent, float leaf, bool fused,
+                       DeskewCtrl ctrl) {
+  DeskewPlan dp = {};
+  dp.in = in; dp.out = out; dp.n = n; dp.sorted = sorted ? 1 : 0; dp.extent = extent; dp.bbox_rows = h->d_bbox_rows;
+  dp.leaf = leaf; dp.vh = fused ? &h->vh : nullptr;
+  if (ctrl == DeskewCtrl::pulled) { dp.ctrl_src = h->h_ctrl; dp.ctrl_dst = h->d_ctrl; dp.ctrl_bytes = (sizeof(IekfCtrl) + 15) / 16 * 16; }
+#ifdef LII_GAP_TRACE
+  if (ctrl != DeskewCtrl::none) dp.gap = h->d_gran;
+#endif
+  return dp;
+}
 // Fetches the exact size of the down-sampled cloud from the device (one small synchronising copy).
 int resolve_n_body(lii_handle h) {
   if (!h->n_body_pending) return LII_OK;
@@ -156,6 +167,66 @@ void prearm_cancel(lii_handle h) {
   h->pre.armed = false;
   if (gate_move(h->pre.state, h->pre.seq, lii::kGateCancel)) h->pre.n_cancelled++;
   else h->pre.n_expired++;  // (the launch had given up already)
+}
+// THE NEXT SCAN'S PROLOGUE, pre-armed (lii_launch.h: DeskewGate): the job announced the scan the next call will bring (prearm_wanted,
+// lii_capi_register.cpp) - its de-skew + filter-insert launch goes out now, behind this update's passes (and its map update), and waits
+// on the device for the record the next lii_scan_register writes (prearm_go).
+void prearm_arm(lii_handle h) {
+  // (poll_result: a caller that ends its updates with a stream synchronise - LII_TEST=sync_result - would wait for the waiting launch)
+  // (mode 3 puts an event in front of every launch: not in front of one that waits)
+  const bool arm = h->pre.want_dev && !h->net.comm && h->net.n_ranks <= 1 && h->prof.prof_mode != 3 && !h->map_async && h->poll_result;
+  if (arm) {
+    lii::GateState* gst = h->pre.state;
+    h->pre.seq = (h->pre.seq + 1) & 0x003FFFFFFFFFFFFFull;  // (seq << 2 stays below the tag's top byte)
+    __atomic_store_n(&gst->word, (h->pre.seq << 2) | lii::kGateArmed, __ATOMIC_RELEASE);
+    h->pre.scan_dev = h->pre.want_dev; h->pre.n = h->pre.want_n; h->pre.leaf = h->pre.want_leaf; h->pre.late = h->pre.want_late;
+    h->pre.fuse = fuse_filter(h, h->pre.leaf);
+    const float4* in = static_cast<const float4*>(h->pre.scan_dev);
+    // (late: the buffer becomes the handle's scan buffer with lii_scan_advance)
+    const DeskewPlan dp = deskew_plan(h, in, h->pre.late ? const_cast<float4*>(in) : h->d_scan.get(), h->pre.n, true, nullptr, h->pre.leaf, h->pre.fuse,
+                                      DeskewCtrl::pulled);
+    lii::DeskewGate gate = {gst, h->pre.d_ring + size_t(h->pre.seq % lii::kGateRing) * lii::kGateLines * 8, h->pre.d_flag, h->pre.seq, h->pre.timeout_ticks, h->pre.late ? 1 : 0};
+    launch_deskew_imu_gated(dp, gate, h->stream);
+    h->pre.armed = hipGetLastError() == hipSuccess;
+    if (!h->pre.armed) __atomic_store_n(&gst->word, (h->pre.seq << 2) | lii::kGateCancel, __ATOMIC_RELEASE);
+  }
+  h->pre.want_dev = nullptr;
+}
+// GO - unless the launch gave up in this very moment (false: the scan is launched like any other) - and the record: straight into
+// device memory (large BAR), payload, then the tags, line 0's last, a store fence between the three
+bool prearm_go(lii_handle h, const lii_state* state, const lii_pose6d* poses, int K) {
+  h->pre.armed = false;
+  if (!gate_move(h->pre.state, h->pre.seq, lii::kGateGo)) {
+    h->pre.n_expired++;
+    return false;
+  }
+  h->pre.n_used++;
+  const int n_pay = 25 + 22 * K, n_lines = (n_pay + 6) / 7;
+  double pay[7 * lii::kGateLines];
+  pay[0] = double(K);
+  std::memcpy(pay + 1, state->rot_end, 72);
+  std::memcpy(pay + 10, state->pos_end, 24);
+  std::memcpy(pay + 13, state->offset_R_L_I, 72);
+  std::memcpy(pay + 22, state->offset_T_L_I, 24);
+  std::memcpy(pay + 25, poses, sizeof(lii_pose6d) * size_t(K));
+  for (int e = n_pay; e < 7 * n_lines; e++) pay[e] = 0.0;
+  volatile double* rec = h->pre.d_ring + size_t(h->pre.seq % lii::kGateRing) * lii::kGateLines * 8;
+  double tag;
+  const unsigned long long tagw = (h->pre.seq << 2) | lii::kGateGo;
+  std::memcpy(&tag, &tagw, 8);
+  for (int l = 0; l < n_lines; l++)
+    for (int c = 0; c < 7; c++) rec[8 * l + c] = pay[7 * l + c];
+  __builtin_ia32_sfence();
+  for (int l = 1; l < n_lines; l++) rec[8 * l + 7] = tag;
+  __builtin_ia32_sfence();
+  {  // (line 0's tag carries K in its top byte: lii_scan.hip, k_deskew_imu_gated)
+    const unsigned long long tag0 = tagw | ((unsigned long long)K << 56);
+    double t0d;
+    std::memcpy(&t0d, &tag0, 8);
+    rec[7] = t0d;
+  }
+  __builtin_ia32_sfence();
+  return true;
 }
 // The intensity channel: whatever replaces the current scan detaches its intensities (those of the down-sampled cloud go with them).
 void intensity_detach(lii_handle h) {
@@ -810,9 +881,7 @@ int lii_undistort_imu(lii_handle h, const lii_pose6d* poses, int32_t n_poses, co
   // (one launch less per scan; lii_downsample goes on with the emit)
   h->vh_inserted = fuse_filter(h, h->fuse_leaf);
   if (h->vh_inserted) h->vh_inserted_leaf = h->fuse_leaf;
-  DeskewPlan dp = {};
-  dp.in = dp.out = h->d_scan; dp.n = h->n_scan; dp.sorted = 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
-  dp.leaf = h->fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
+  const DeskewPlan dp = deskew_plan(h, h->d_scan, h->d_scan, h->n_scan, false, ext, h->fuse_leaf, h->vh_inserted, DeskewCtrl::none);
   launch_deskew_imu(dp, nullptr, h->d_poses, n_poses, u, h->stream);
   h->bbox_rows = (h->n_scan + 255) / 256;
   HIPCHK(h, hipGetLastError());
@@ -831,9 +900,7 @@ int lii_undistort_cv(lii_handle h, const double omega[3], const double vel[3], c
   unsigned long long* ext = extent_of_scan(h);
   h->vh_inserted = fuse_filter(h, h->fuse_leaf);
   if (h->vh_inserted) h->vh_inserted_leaf = h->fuse_leaf;
-  DeskewPlan dp = {};
-  dp.in = dp.out = h->d_scan; dp.n = h->n_scan; dp.sorted = 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
-  dp.leaf = h->fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
+  const DeskewPlan dp = deskew_plan(h, h->d_scan, h->d_scan, h->n_scan, false, ext, h->fuse_leaf, h->vh_inserted, DeskewCtrl::none);
   launch_deskew_cv(dp, a, h->stream);
   h->bbox_rows = (h->n_scan + 255) / 256;
   HIPCHK(h, hipGetLastError());

@@ -10,7 +10,6 @@ using namespace lii_impl;
 
 namespace {
 
-
 // (every enqueued search launch has a number, which the fit launch behind it shares: the list of unfinished queries the one leaves
 // and the other consumes - RegistrationBuffers::flag_*)
 int next_knn_epoch(lii_handle h) {
@@ -21,7 +20,6 @@ void launch_knn(lii_handle h, const GridView& g, const RegistrationBuffers& rb, 
                 hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
   lii::launch_knn(g, rb, pose, h->d_ctrl, forced, h->d_ctrl->search_pose, h->stream, epoch, ev_start, ev_stop);
 }
-
 
 int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double* out91) {
   if (h->n_body <= 0) return fail(h, LII_ERR_STATE, "no down-sampled scan (call lii_downsample / lii_downsample_skip)");
@@ -99,47 +97,77 @@ void fill_ctrl(lii_handle h, const lii_state* state, const lii_state* state_prop
   h->plan_cur = plan;
 }
 
-int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop, const lii_iekf_opts* opts,
-                     lii_iekf_report* report) {
-  static_assert(sizeof(lii_state) == sizeof(double) * kStateDoubles, "lii_state layout");
-  if (h->n_body <= 0) return fail(h, LII_ERR_STATE, "no down-sampled scan (call lii_downsample / lii_downsample_skip)");
-  const auto t_map0 = std::chrono::steady_clock::now();
-  int rc = commit_map(h);
-  if (rc != LII_OK) return rc;
-  if (h->diag) h->prof.host_map_us[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_map0).count();
-  hipStream_t s = h->stream;
-  // The stream lii_map_incremental leaves its update on is created with the first update of a handle that is NOT a rank of a
-  // sharded job (those never update beside a scan).  Not in lii_create: a second compute queue per process - even one whose
-  // stream has been destroyed again: the runtime keeps the hardware queue - makes several processes on one device oversubscribe
-  // the hardware queues, and a kernel that waits for a peer's kernel (the mailbox) then waits for a time slice: the one-device
-  // rehearsal of a 2-rank job fell from 4 000 to 1 350 scans/s.
-  if (!h->map_stream && h->net.n_ranks <= 1) HIPCHK(h, h->map_stream.create(hipStreamNonBlocking));
-  if (!h->ctrl_preloaded) {
-    if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(s));  // a lii_scan_register that failed half way left the buffer in use
-    fill_ctrl(h, state, state_prop, opts);
-    HIPCHK(h, hipMemcpyAsync(h->d_ctrl, h->h_ctrl, sizeof(IekfCtrl), hipMemcpyHostToDevice, s));
+// ------------------------------------------------------------------------------------------------ the job
+// lii_scan_job as the call uses it, read once: a field the caller's ABI does not have reads as zero / null.
+// struct_size 88: ABI 9; 72: ABI 8, without while_waiting; 56: ABI 6 - 7, without next_scan_dev; 48: ABI 5, without scan_sorted / map_update.
+static_assert(sizeof(lii_scan_job) == 88, "lii_scan_job: the sizes of the earlier ABIs are accepted by number");
+constexpr uint32_t kJobAbi5 = 48u, kJobAbi6 = 56u, kJobAbi8 = 72u, kJobAbi9 = 88u;
+struct JobView {
+  bool sorted;      // ascending time order, as it arrived or (sort_first) once scan_sort_into has run
+  bool sort_first;  // scan_sorted == 2: the scan is put into ascending time order on the device first, and the call goes on as for a
+                    // scan_sorted == 1 job on the handle's own scan buffer
+  bool map_update;
+  float leaf;       // 0 when not positive
+  int undistort;
+  const lii_pose6d* poses; int n_poses;
+  const void* scan_dev; int n_scan_dev;
+  const void* next_scan_dev; int next_n_scan;
+  void (*while_waiting)(void*); void* while_waiting_arg;
+};
+bool job_size_ok(uint32_t size) { return size == kJobAbi9 || size == kJobAbi8 || size == kJobAbi6 || size == kJobAbi5; }
+JobView job_view(const lii_scan_job* job) {
+  const uint32_t size = job->struct_size;
+  JobView jv = {};
+  jv.sort_first = size >= kJobAbi6 && job->scan_sorted == 2;
+  jv.sorted = size >= kJobAbi6 && (job->scan_sorted == 1 || jv.sort_first);
+  jv.map_update = size >= kJobAbi6 && job->map_update == 1;
+  jv.leaf = job->leaf > 0 ? job->leaf : 0.f;
+  jv.undistort = job->undistort;
+  jv.poses = job->imu_poses; jv.n_poses = job->n_imu_poses;
+  jv.scan_dev = job->scan_dev; jv.n_scan_dev = job->n_scan_dev;
+  if (size >= kJobAbi8) { jv.next_scan_dev = job->next_scan_dev; jv.next_n_scan = job->next_n_scan; }
+  if (size >= kJobAbi9) { jv.while_waiting = job->while_waiting; jv.while_waiting_arg = job->while_waiting_arg; }
+  return jv;
+}
+
+// The pre-armed prologue (lii_launch.h: DeskewGate; prearm_arm / prearm_go / prearm_cancel: lii_capi.cpp): what this job announces for
+// the next call - update_on_device arms it behind the passes.  may_announce: a plain lii_scan_register that neither sorts nor runs the
+// local map; every other form announces nothing - next_scan_dev is ignored.
+void prearm_wanted(lii_handle h, const JobView& jv, bool may_announce, bool from_job) {
+  h->pre.want_dev = nullptr;
+  if (!may_announce || !h->pre.enabled || !jv.sorted || jv.undistort != 1) return;
+  if (jv.next_scan_dev && jv.next_n_scan > 0 && jv.next_n_scan <= h->cfg.max_scan_points) {
+    h->pre.want_dev = jv.next_scan_dev; h->pre.want_n = jv.next_n_scan; h->pre.want_leaf = jv.leaf; h->pre.want_late = false;
+  } else if (h->n_scan_next > 0 && h->d_scan_next && !from_job) {
+    // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
+    h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = jv.leaf; h->pre.want_late = true;
   }
-  h->ctrl_preloaded = false;
-  h->h_res->singular = 0;
-  h->h_res->it = -1;  // overwritten by the stopping iteration
-  // lii_local_map_set(enabled): lasermap_fov_segment + the box delete at the reference's place - behind the propagation (state.pos_end of
-  // the control block, which every prologue has put on the stream by now) and the map update that commit_map joined, in front of the
-  // first search.  Three launches of fixed size.
-  if (h->lm.in_job) {
-    rc = local_map_enqueue(h, h->d_ctrl->st + 9, nullptr, h->prof.kp_active);
-    if (rc != LII_OK) return rc;
-  }
-  GridView g = grid_view(h);
-  RegistrationBuffers rb = reg_buffers(h);
-  const PoseArg* pose = reinterpret_cast<const PoseArg*>(h->d_ctrl);  // first 24 doubles of IekfCtrl::st
-  const bool prof = h->prof.profiling && h->prof.prof_mode != 3;  // (mode 3 brackets every launch itself: kp_mark)
-  if (prof) harvest_knn_events(h);  // (the events are about to be used again)
-  const double* ne = h->net.comm ? h->d_out91 + 128 : h->d_out91;
-  unsigned int plan = h->plan_cur;  // fill_ctrl chose it (the control block on the device carries the same mask)
-  const unsigned int plan0 = plan;
+}
+
+// ------------------------------------------------------------------------------------------------ the update on the device
+// lii_scan_job::while_waiting (ABI 9), once per call that got as far as its update.  inside: from update_on_device - everything is
+// enqueued, the thread would only wait now, the caller's hook runs first (entry points that change which frames are current refuse
+// meanwhile: in_wait_hook); an arrangement without that wait (LII_TEST=host_solve) calls it behind the update, never otherwise.
+void run_wait_hook(lii_handle h, bool inside) {
+  if (!h->wait_hook) return;
+  void (*hook)(void*) = h->wait_hook;
+  h->wait_hook = nullptr;
+  if (inside) h->in_wait_hook = true;
+  hook(h->wait_hook_arg);
+  if (inside) h->in_wait_hook = false;
+}
+
+// The passes of one update on the stream: what enqueueing one, waiting for the result and continuing a parked loop share.
+struct DevicePasses {
+  lii_handle h; const lii_iekf_opts* opts; hipStream_t s;
+  GridView g; RegistrationBuffers rb;
+  const PoseArg* pose;  // first 24 doubles of IekfCtrl::st
   // (profiling = HIP events around the k-NN launches only - the dominant kernel, lii_last_timings [5] / [7]; every event is a
   // barrier packet on the stream, so the rest of the loop is left alone: launch plan and result polling work as always)
-  auto enqueue_pass = [&](int it) -> int {
+  bool prof;
+  unsigned int plan;  // fill_ctrl chose it (the control block on the device carries the same mask)
+
+  int enqueue(int it) {
     const bool knn = it >= 16 || ((plan >> it) & 1u);
     // (a fit launch that is not behind a search launch never runs as a search pass - the plan parks the loop instead - and needs no number)
     const int epoch = knn ? next_knn_epoch(h) : 0;
@@ -166,31 +194,26 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     // unchanged local buffer on all ranks alike, so the ranks stay in lock-step without a host decision
     ncclResult_t r = ncclAllReduce(h->d_out91, h->d_out91 + 128, kNormalEq, ncclDouble, ncclSum, h->net.comm, s);
     if (r != ncclSuccess) return fail(h, LII_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-    launch_iekf_solve(h->d_ctrl, ne, h->h_res, s);
+    launch_iekf_solve(h->d_ctrl, h->d_out91 + 128, h->h_res, s);
     return LII_OK;
-  };
-  const auto t_loop0 = std::chrono::steady_clock::now();
-  for (int it = 0; it < opts->max_iterations; it++) {
-    if (it < 16 && !((plan >> (16 + it)) & 1u)) break;  // the plan ends here
-    rc = enqueue_pass(it);
-    if (rc != LII_OK) return rc;
   }
+
   // The iteration that stops the loop writes the result block (mapped host memory) and then its sequence number.  Polling
   // that word instead of synchronising the stream returns as soon as the result exists: the passes enqueued behind the
   // stopping one (they only read `stop` and return) drain while the caller already prepares the next scan.
   // The plan also ends the enqueued loop after as many passes as the last updates ran: the launches behind the stopping pass
   // only drain (3 x 4.5 us on stream100k, about what the host needs to come back with the next scan: + 0 .. 3 % scans/s,
   // gpurun_out/r3x4).  A loop that parked itself (the next pass is not there, or needs a search the plan did not hold - the
-  // pattern changed against the previous scans) is continued from here (below): one host round trip, on those scans.
-  auto wait_result = [&](bool first) -> int {
-    const int parked_word = first ? (h->update_seq | kLoopParked) : h->update_seq;
+  // pattern changed against the previous scans) is continued by continue_parked: one host round trip, on those scans.
+  int wait() {
+    const int parked_word = h->update_seq | kLoopParked;
     if (h->poll_result && !h->net.comm) {
       volatile int* done = &h->h_res->done;
       unsigned int spins = 0;
       while (*done != h->update_seq && *done != parked_word) {
         if ((++spins & 0x3FFF) == 0) {  // every ~50 us: is the stream still alive?
           const hipError_t q = hipStreamQuery(s);
-          if (q == hipSuccess) break;  // everything ran; `done` is final (a loop that never stopped is reported below)
+          if (q == hipSuccess) break;  // everything ran; `done` is final (a loop that never stopped is reported by result_code)
           if (q != hipErrorNotReady) return fail(h, LII_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
         }
         __builtin_ia32_pause();
@@ -201,7 +224,169 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
       HIPCHK(h, hipStreamSynchronize(s));  // the stopping iteration's solve has written h_res (mapped host memory)
     }
     return LII_OK;
+  }
+
+  // A parked loop is continued with what it is known to need: the pass it parked in front of - behind a k-NN launch if that pass
+  // searches - and as many passes behind it as the longer of the last two updates ran; should that not be enough (the next search
+  // comes at another pass as well, or the update runs longer) it parks again and is continued again.  (Round 3 enqueued every
+  // remaining pass with every k-NN launch: up to nine launches that only read a flag, ~ 20 us on a scan that parks.)
+  int continue_parked(bool* parked_once) {
+    for (int round = 0; h->h_res->done == (h->update_seq | kLoopParked); round++) {
+      if (round > 2 * opts->max_iterations) return fail(h, LII_ERR_HIP, "device loop parked again and again");
+      *parked_once = true;
+      const int from = h->h_res->parked_it;
+      const bool search = h->h_res->parked_search != 0;
+      h->plan_parked++;
+      prearm_cancel(h);  // (the launches that continue the loop would queue up behind a launch that waits for this call to return)
+      h->map_enqueued_early = false;  // (that launch saw a parked loop and did nothing: the caller makes the map update when the loop has ended)
+      g = grid_view(h);  // (never a view older than the last thing that may have rebuilt the index: update_on_device, map_update_early)
+      const int last = std::min(opts->max_iterations, std::max(h->plan_passes_prev, from + 1));  // (exclusive; from < max_iterations: the last pass never parks)
+      unsigned int rplan = 0u;
+      for (int q = from; q < last && q < 16; q++) rplan |= 1u << (16 + q);
+      if (search && from < 16) rplan |= 1u << from;
+      plan = rplan;
+      h->h_res->done = 0;  // (the parked word of this round must not be taken for the next one's)
+      std::atomic_thread_fence(std::memory_order_release);
+      launch_loop_resume(h->d_ctrl, rplan, s);
+      for (int it = from; it < last; it++) {
+        const int rc = enqueue(it);
+        if (rc != LII_OK) return rc;
+      }
+      if (h->prof.kp_active) { const int rc = kp_mark(h, LII_KP_KINDS); if (rc != LII_OK) return rc; }
+      const int rc = wait();
+      if (rc != LII_OK) return rc;
+    }
+    return LII_OK;
+  }
+};
+
+#ifdef LII_SOLVE_TRACE
+void solve_trace(const IekfResult* hr) {
+  static int cnt = 0;
+  if (++cnt % 100 != 0) return;
+  auto row = [&](const long long* t) {
+    fprintf(stderr, " loads+sums %lld | A %lld | elimination %lld (its own %lld) | solution %lld | state %lld (rotations %lld, pose stores %lld) | barrier + cov %lld | all %lld | clock %.2f GHz ;",
+            t[1] - t[0], t[2] - t[1], t[4] - t[3], t[5] - t[3], t[8] - t[4], t[9] - t[8], t[7] - t[8], t[9] - t[7], t[10] - t[9], t[10] - t[0],
+            t[5] > t[3] ? (double)(t[12] - t[11]) / (10.0 * (double)(t[5] - t[3])) : 0.0);
   };
+  fprintf(stderr, "[solve trace, 10 ns ticks] stopping pass:");
+  row(hr->ts);
+  fprintf(stderr, "  pass 0:");
+  row(hr->ts0);
+  fprintf(stderr, "\n");
+}
+#endif
+
+// (the launch plan of the completions, see DevicePasses::enqueue)
+void note_unfinished(lii_handle h) {
+  h->unfinished_known = !h->net.comm;
+  if (h->net.comm || !h->wide_enabled) return;
+  // (two scans in a row decide: a stream on which one scan in eight crosses the capacity - bench --edge - would pay for a launch that
+  // finds nothing behind every such scan and never have it where it is needed)
+  const bool wide = h->h_res->unfinished > lii::kFlagCap;
+  if (wide == h->wide_prev && wide != h->wide_listed) { h->wide_listed = wide; h->wide_switches++; }
+  h->wide_prev = wide;
+  if (wide) h->wide_scans++;
+}
+
+// per-launch brackets (lii_set_profiling(h, 3)): the time from the event in front of a launch to the next event, for the
+// launches that executed (a pass the loop did not reach, or a k-NN launch whose pass did not search, only read a flag)
+int account_brackets(lii_handle h, const IekfResult* hr) {
+  if (!(h->prof.kp_active && h->prof.kp_n > 1 && hr->it > 0)) return LII_OK;
+  HIPCHK(h, hipEventSynchronize(h->prof.kp_ev[size_t(h->prof.kp_n - 1)]));
+  for (int i = 0; i + 1 < h->prof.kp_n; i++) {
+    int kind = h->prof.kp_kind[size_t(i)] / 64;
+    const int it = h->prof.kp_kind[size_t(i)] % 64;
+    if (kind >= LII_KP_KINDS) continue;
+    const bool loop_kind = kind == LII_KP_KNN || kind == LII_KP_FIT || kind == LII_KP_SOLVE;
+    if (loop_kind && (it >= hr->it || it >= 16)) continue;
+    if (kind == LII_KP_KNN && !(hr->search_log[it] & 1)) continue;
+    if (kind == LII_KP_FIT && (hr->search_log[it] & 1)) kind = LII_KP_FIT_SEARCH;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->prof.kp_ev[size_t(i)], h->prof.kp_ev[size_t(i + 1)]) != hipSuccess) continue;
+    h->prof.kprof.ms[kind] += ms;
+    h->prof.kprof.launches[kind] += 1;
+  }
+  h->prof.kprof.scans += 1;
+  return LII_OK;
+}
+
+// what the result block says about the update, as the call's return code
+int result_code(lii_handle h, const IekfResult* hr) {
+  if (hr->part_overflow) {
+    h->h_res->part_overflow = 0;
+    return fail(h, LII_ERR_CAPACITY, "voxel-partitioned job: this rank's share of the down-sampled cloud exceeds its bound (mean share + 25 % + 2048 points); use lii_comm_set_partition(h, 1)");
+  }
+  if (hr->singular == 3)
+    return fail(h, LII_ERR_COMM, "mailbox exchange timed out (a rank of the job did not reach this pass); re-create the communicator");
+  if (hr->singular == 4)
+    return fail(h, LII_ERR_COMM, "the sums of a pass did not reach the solver within 2 s (a summing workgroup of the launch was not scheduled: is the device shared?)");
+  if (hr->singular) return fail(h, LII_ERR_INVALID, "singular covariance / normal matrix in the device solve");
+  if (hr->it < 0) return fail(h, LII_ERR_HIP, "device loop ended without a result");
+  return LII_OK;
+}
+
+// the next update's plan: this one's pattern; passes it did not reach keep their launch
+void plan_from_result(lii_handle h, const IekfResult* hr) {
+  h->last_pivoted_passes = 0;
+  for (int q = 0; q < 16 && q < hr->it; q++) h->last_pivoted_passes += (hr->search_log[q] >> 1) & 1;
+  unsigned int next = 0xFFFFFFFFu;
+  for (int q = 0; q < 16 && q < hr->it; q++)
+    if (!(hr->search_log[q] & 1)) next &= ~(1u << q);
+  // ... and as many passes as the longer of the last two updates ran (a scan that needs more parks and is continued)
+  for (int q = std::max(hr->it, h->plan_passes_prev); q < 16; q++) next &= ~(1u << (16 + q));
+  h->plan_passes_prev = hr->it;
+  h->plan_next = next;
+}
+
+void fill_report(lii_iekf_report* report, int iterations, int searches, int effect_num, int converged, const double* normal_eq) {
+  if (!report) return;
+  report->iterations = iterations;
+  report->searches = searches;
+  report->effect_num = effect_num;
+  report->converged = converged;
+  std::memcpy(report->normal_eq, normal_eq, sizeof(double) * kNormalEq);
+}
+
+int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop, const lii_iekf_opts* opts,
+                     lii_iekf_report* report) {
+  static_assert(sizeof(lii_state) == sizeof(double) * kStateDoubles, "lii_state layout");
+  if (h->n_body <= 0) return fail(h, LII_ERR_STATE, "no down-sampled scan (call lii_downsample / lii_downsample_skip)");
+  const auto t_map0 = std::chrono::steady_clock::now();
+  int rc = commit_map(h);
+  if (rc != LII_OK) return rc;
+  if (h->diag) h->prof.host_map_us[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_map0).count();
+  hipStream_t s = h->stream;
+  // The stream lii_map_incremental leaves its update on is created with the first update of a handle that is NOT a rank of a
+  // sharded job (those never update beside a scan).  Not in lii_create: a second compute queue per process - even one whose
+  // stream has been destroyed again: the runtime keeps the hardware queue - makes several processes on one device oversubscribe
+  // the hardware queues, and a kernel that waits for a peer's kernel (the mailbox) then waits for a time slice: the one-device
+  // rehearsal of a 2-rank job fell from 4 000 to 1 350 scans/s.
+  if (!h->map_stream && h->net.n_ranks <= 1) HIPCHK(h, h->map_stream.create(hipStreamNonBlocking));
+  if (!h->ctrl_preloaded) {
+    if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(s));  // a lii_scan_register that failed half way left the buffer in use
+    fill_ctrl(h, state, state_prop, opts);
+    HIPCHK(h, hipMemcpyAsync(h->d_ctrl, h->h_ctrl, sizeof(IekfCtrl), hipMemcpyHostToDevice, s));
+  }
+  h->ctrl_preloaded = false;
+  h->h_res->singular = 0; h->h_res->it = -1;  // (it: overwritten by the stopping iteration)
+  // lii_local_map_set(enabled): lasermap_fov_segment + the box delete at the reference's place - behind the propagation (state.pos_end of
+  // the control block, which every prologue has put on the stream by now) and the map update that commit_map joined, in front of the
+  // first search.  Three launches of fixed size.
+  if (h->lm.in_job) {
+    rc = local_map_enqueue(h, h->d_ctrl->st + 9, nullptr, h->prof.kp_active);
+    if (rc != LII_OK) return rc;
+  }
+  const bool prof = h->prof.profiling && h->prof.prof_mode != 3;  // (mode 3 brackets every launch itself: kp_mark)
+  DevicePasses p = {h, opts, s, grid_view(h), reg_buffers(h), reinterpret_cast<const PoseArg*>(h->d_ctrl), prof, h->plan_cur};
+  if (prof) harvest_knn_events(h);  // (the events are about to be used again)
+  const unsigned int plan0 = p.plan;
+  const auto t_loop0 = std::chrono::steady_clock::now();
+  for (int it = 0; it < opts->max_iterations; it++) {
+    if (it < 16 && !((p.plan >> (16 + it)) & 1u)) break;  // the plan ends here
+    rc = p.enqueue(it);
+    if (rc != LII_OK) return rc;
+  }
   if (h->diag) h->prof.host_loop_enq_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_loop0).count();
   if (h->prof.kp_active) { rc = kp_mark(h, LII_KP_KINDS); if (rc != LII_OK) return rc; }  // (end mark of the planned passes)
   h->map_enqueued_early = false;
@@ -214,161 +399,39 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
     // (map_apply rebuilds the index when the map is short of room - build_index may free and reallocate the block table, the cell
     // tables and their side arrays and change the mask: a loop that parks is continued below with launches that must see the map
     // as it is NOW, not the view taken before the passes went out - ADVICE r4)
-    g = grid_view(h);
+    p.g = grid_view(h);
     if (h->diag) h->prof.host_map_us[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_me0).count();
   }
   // lii_publish_set: the registered clouds go out now as well - behind the passes and the map update, in front of a pre-armed prologue.
   // The launch reads the final state from the control block and does nothing if the loop has parked (then it is enqueued again below).
   if (h->pub.any()) { rc = publish_enqueue(h, h->d_ctrl, nullptr, true); if (rc != LII_OK) return rc; }
-  // THE NEXT SCAN'S PROLOGUE, pre-armed (lii_launch.h: DeskewGate): the job announced the scan the next call will bring - its de-skew +
-  // filter-insert launch goes out now, behind this update's passes (and its map update), and waits on the device for the record
-  // the next lii_scan_register writes.
-  if (h->pre.want_dev && !h->net.comm && h->net.n_ranks <= 1 && h->prof.prof_mode != 3 && !h->map_async && h->poll_result) {  // (poll_result: a caller that ends its updates with a stream synchronise - LII_TEST=sync_result - would wait for the waiting launch)  // (mode 3 puts an event in front of every launch: not in front of one that waits)
-    lii::GateState* gst = h->pre.state;
-    h->pre.seq = (h->pre.seq + 1) & 0x003FFFFFFFFFFFFFull;  // (seq << 2 stays below the tag's top byte)
-    __atomic_store_n(&gst->word, (h->pre.seq << 2) | lii::kGateArmed, __ATOMIC_RELEASE);
-    h->pre.scan_dev = h->pre.want_dev; h->pre.n = h->pre.want_n; h->pre.leaf = h->pre.want_leaf; h->pre.late = h->pre.want_late;
-    h->pre.fuse = fuse_filter(h, h->pre.leaf);
-    DeskewPlan dp = {};
-    dp.in = static_cast<const float4*>(h->pre.scan_dev);
-    dp.out = h->pre.late ? const_cast<float4*>(dp.in) : h->d_scan;  // (late: the buffer becomes the handle's scan buffer with lii_scan_advance)
-    dp.n = h->pre.n; dp.sorted = 1; dp.extent = nullptr; dp.bbox_rows = h->d_bbox_rows;
-    dp.leaf = h->pre.leaf; dp.vh = h->pre.fuse ? &h->vh : nullptr;
-    dp.ctrl_src = h->h_ctrl; dp.ctrl_dst = h->d_ctrl; dp.ctrl_bytes = (sizeof(IekfCtrl) + 15) / 16 * 16;
-#ifdef LII_GAP_TRACE
-    dp.gap = h->d_gran;
-#endif
-    lii::DeskewGate gate = {gst, h->pre.d_ring + size_t(h->pre.seq % lii::kGateRing) * lii::kGateLines * 8, h->pre.d_flag, h->pre.seq, h->pre.timeout_ticks, h->pre.late ? 1 : 0};
-    launch_deskew_imu_gated(dp, gate, s);
-    h->pre.armed = hipGetLastError() == hipSuccess;
-    if (!h->pre.armed) __atomic_store_n(&gst->word, (h->pre.seq << 2) | lii::kGateCancel, __ATOMIC_RELEASE);
-  }
-  h->pre.want_dev = nullptr;
-  // lii_scan_job::while_waiting (ABI 9): everything is enqueued, the thread would only wait now - the caller's hook runs first
-  if (h->wait_hook) {
-    void (*hook)(void*) = h->wait_hook;
-    h->wait_hook = nullptr;
-    h->in_wait_hook = true;
-    hook(h->wait_hook_arg);
-    h->in_wait_hook = false;
-  }
-  rc = wait_result(true);
-  if (rc != LII_OK) return rc;
-  // A parked loop is continued with what it is known to need: the pass it parked in front of - behind a k-NN launch if that pass
-  // searches - and as many passes behind it as the longer of the last two updates ran; should that not be enough (the next search
-  // comes at another pass as well, or the update runs longer) it parks again and is continued again.  (Round 3 enqueued every
-  // remaining pass with every k-NN launch: up to nine launches that only read a flag, ~ 20 us on a scan that parks.)
+  prearm_arm(h);
+  run_wait_hook(h, true);
   bool parked_once = false;
-  for (int round = 0; h->h_res->done == (h->update_seq | kLoopParked); round++) {
-    if (round > 2 * opts->max_iterations) return fail(h, LII_ERR_HIP, "device loop parked again and again");
-    parked_once = true;
-    const int from = h->h_res->parked_it;
-    const bool search = h->h_res->parked_search != 0;
-    h->plan_parked++;
-    prearm_cancel(h);  // (the launches that continue the loop would queue up behind a launch that waits for this call to return)
-    h->map_enqueued_early = false;  // (that launch saw a parked loop and did nothing: the caller makes the map update when the loop has ended)
-    g = grid_view(h);  // (see above: never a view older than the last thing that may have rebuilt the index)
-    const int last = std::min(opts->max_iterations, std::max(h->plan_passes_prev, from + 1));  // (exclusive; from < max_iterations: the last pass never parks)
-    unsigned int rplan = 0u;
-    for (int q = from; q < last && q < 16; q++) rplan |= 1u << (16 + q);
-    if (search && from < 16) rplan |= 1u << from;
-    plan = rplan;
-    h->h_res->done = 0;  // (the parked word of this round must not be taken for the next one's)
-    std::atomic_thread_fence(std::memory_order_release);
-    launch_loop_resume(h->d_ctrl, rplan, s);
-    for (int it = from; it < last; it++) {
-      rc = enqueue_pass(it);
-      if (rc != LII_OK) return rc;
-    }
-    if (h->prof.kp_active) { rc = kp_mark(h, LII_KP_KINDS); if (rc != LII_OK) return rc; }
-    rc = wait_result(true);
-    if (rc != LII_OK) return rc;
-  }
+  rc = p.wait();
+  if (rc == LII_OK) rc = p.continue_parked(&parked_once);
+  if (rc != LII_OK) return rc;
   if (h->pub.any() && parked_once) {  // (the launch behind the planned passes saw a parked loop and did nothing: once more, behind the passes that ended it)
     if (h->pub.kp_idx >= 0) h->prof.kp_kind[size_t(h->pub.kp_idx)] = LII_KP_KINDS * 64;  // (lii_set_profiling(h, 3): that launch did not execute)
     rc = publish_enqueue(h, h->d_ctrl, nullptr, false);
     if (rc != LII_OK) return rc;
   }
-  h->unfinished_known = !h->net.comm;
-  if (!h->net.comm && h->wide_enabled) {  // (the launch plan of the completions, see enqueue_pass)
-    // (two scans in a row decide: a stream on which one scan in eight crosses the capacity - bench --edge - would pay for a launch that
-    // finds nothing behind every such scan and never have it where it is needed)
-    const bool wide = h->h_res->unfinished > lii::kFlagCap;
-    if (wide == h->wide_prev && wide != h->wide_listed) { h->wide_listed = wide; h->wide_switches++; }
-    h->wide_prev = wide;
-    if (wide) h->wide_scans++;
-  }
+  note_unfinished(h);
   h->staging_busy = false;  // the wait above covers everything enqueued before the stopping pass
   h->scan_buf_idle = !h->pub.any();  // ... every launch that read or wrote the current scan buffer among it (what was enqueued behind - drained passes, the map update, a pre-armed launch on the OTHER buffer - does not touch it;
                                    // the launch and the body copy of a standing lii_publish_set order DO read it behind the stopping pass: with one, lii_scan_upload_next puts its event pair between the streams)
   const IekfResult* hr = h->h_res;
   h->have_search = true;
 #ifdef LII_SOLVE_TRACE
-  {
-    static int cnt = 0;
-    if (++cnt % 100 == 0) {
-      auto row = [&](const long long* t) {
-        fprintf(stderr, " loads+sums %lld | A %lld | elimination %lld (its own %lld) | solution %lld | state %lld (rotations %lld, pose stores %lld) | barrier + cov %lld | all %lld | clock %.2f GHz ;",
-                t[1] - t[0], t[2] - t[1], t[4] - t[3], t[5] - t[3], t[8] - t[4], t[9] - t[8], t[7] - t[8], t[9] - t[7], t[10] - t[9], t[10] - t[0],
-                t[5] > t[3] ? (double)(t[12] - t[11]) / (10.0 * (double)(t[5] - t[3])) : 0.0);
-      };
-      fprintf(stderr, "[solve trace, 10 ns ticks] stopping pass:");
-      row(hr->ts);
-      fprintf(stderr, "  pass 0:");
-      row(hr->ts0);
-      fprintf(stderr, "\n");
-    }
-  }
+  solve_trace(hr);
 #endif
-  if (h->prof.kp_active && h->prof.kp_n > 1 && hr->it > 0) {
-    // per-launch brackets (lii_set_profiling(h, 3)): the time from the event in front of a launch to the next event, for the
-    // launches that executed (a pass the loop did not reach, or a k-NN launch whose pass did not search, only read a flag)
-    HIPCHK(h, hipEventSynchronize(h->prof.kp_ev[size_t(h->prof.kp_n - 1)]));
-    for (int i = 0; i + 1 < h->prof.kp_n; i++) {
-      int kind = h->prof.kp_kind[size_t(i)] / 64;
-      const int it = h->prof.kp_kind[size_t(i)] % 64;
-      if (kind >= LII_KP_KINDS) continue;
-      const bool loop_kind = kind == LII_KP_KNN || kind == LII_KP_FIT || kind == LII_KP_SOLVE;
-      if (loop_kind && (it >= hr->it || it >= 16)) continue;
-      if (kind == LII_KP_KNN && !(hr->search_log[it] & 1)) continue;
-      if (kind == LII_KP_FIT && (hr->search_log[it] & 1)) kind = LII_KP_FIT_SEARCH;
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, h->prof.kp_ev[size_t(i)], h->prof.kp_ev[size_t(i + 1)]) != hipSuccess) continue;
-      h->prof.kprof.ms[kind] += ms;
-      h->prof.kprof.launches[kind] += 1;
-    }
-    h->prof.kprof.scans += 1;
-  }
-  if (hr->part_overflow) {
-    h->h_res->part_overflow = 0;
-    return fail(h, LII_ERR_CAPACITY, "voxel-partitioned job: this rank's share of the down-sampled cloud exceeds its bound (mean share + 25 % + 2048 points); use lii_comm_set_partition(h, 1)");
-  }
-  if (hr->singular == 3)
-    return fail(h, LII_ERR_COMM, "mailbox exchange timed out (a rank of the job did not reach this pass); re-create the communicator");
-  if (hr->singular == 4)
-    return fail(h, LII_ERR_COMM, "the sums of a pass did not reach the solver within 2 s (a summing workgroup of the launch was not scheduled: is the device shared?)");
-  if (hr->singular) return fail(h, LII_ERR_INVALID, "singular covariance / normal matrix in the device solve");
-  if (hr->it < 0) return fail(h, LII_ERR_HIP, "device loop ended without a result");
+  rc = account_brackets(h, hr);
+  if (rc == LII_OK) rc = result_code(h, hr);
+  if (rc != LII_OK) return rc;
   std::memcpy(state, hr->st, sizeof(lii_state));
   publish_finish(h);  // (the clouds of this registration are the ones lii_publish_fetch serves from here on)
-  h->last_pivoted_passes = 0;
-  for (int q = 0; q < 16 && q < hr->it; q++) h->last_pivoted_passes += (hr->search_log[q] >> 1) & 1;
-  {  // the next update's plan: this one's pattern; passes it did not reach keep their launch
-    unsigned int next = 0xFFFFFFFFu;
-    for (int q = 0; q < 16 && q < hr->it; q++)
-      if (!(hr->search_log[q] & 1)) next &= ~(1u << q);
-    // ... and as many passes as the longer of the last two updates ran (a scan that needs more parks and is continued)
-    for (int q = std::max(hr->it, h->plan_passes_prev); q < 16; q++) next &= ~(1u << (16 + q));
-    h->plan_passes_prev = hr->it;
-    h->plan_next = next;
-  }
-  if (report) {
-    report->iterations = hr->it;
-    report->searches = hr->searches;
-    report->effect_num = hr->effect_num;
-    report->converged = hr->converged;
-    std::memcpy(report->normal_eq, hr->ne, sizeof(double) * kNormalEq);
-  }
+  plan_from_result(h, hr);
+  fill_report(report, hr->it, hr->searches, hr->effect_num, hr->converged, hr->ne);
   if (prof) {
     // the k-NN kernel alone, over EVERY pass that actually searched (the device logs which iterations did).  The events are READ
     // LATER (harvest_knn_events: in front of the next profiled update, or when the timings are asked for): asking the runtime for
@@ -384,38 +447,70 @@ int update_on_device(lii_handle h, lii_state* state, const lii_state* state_prop
   return LII_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ the prologues
+// The 16-byte words [from, vec) of IekfCtrl are what a launch that propagates pulls from pinned memory: the two states in front of them
+// are written on the device.
+struct CtrlWords { int from, vec; };
+CtrlWords ctrl_words() {
+  static_assert(offsetof(IekfCtrl, solution) % 16 == 0 && offsetof(IekfCtrl, prop) + sizeof(IekfCtrl::prop) == offsetof(IekfCtrl, solution), "IekfCtrl: the two states come first");
+  return {int(offsetof(IekfCtrl, solution) / 16), int((sizeof(IekfCtrl) + 15) / 16)};
+}
 
-
-// The prologue of lii_scan_register_imu: IMU forward propagation and de-skew, back to back on the stream.  The host's part is what it
-// knows BEFORE the previous update has ended - the samples - and the state that update left; everything that depends on them (the
-// propagated state, the IMUpose table, the update's control block with state and state_propagat filled in) is formed on the device.
-int imu_prologue(lii_handle h, const lii_scan_job* job, const ImuFeed* feed, const lii_state* state, bool adopt, const float4* src_dev, int n_next,
-                 bool sorted) {
-  if (n_next <= 0) return fail(h, LII_ERR_STATE, "lii_scan_register_imu: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
-  int rc = imu_buffers(h);
-  if (rc != LII_OK) return rc;
+// The staging buffer (control block + pose table) is this call's from here on.  poses_too: the table's half is written as well - a
+// pose table uploaded by a stand-alone lii_undistort_imu (long done) must have left it.
+int claim_staging(lii_handle h, bool poses_too) {
   if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
-  HIPCHK(h, hipEventSynchronize(h->ev_poses));  // a pose table uploaded by a stand-alone lii_undistort_imu (long done): the samples take its staging area
+  if (poses_too) HIPCHK(h, hipEventSynchronize(h->ev_poses));
   h->staging_busy = true;
-  fill_ctrl(h, state, state, &job->opts);  // (st / prop of the block on the device are written by k_imu_propagate, not pulled)
-  std::memcpy(h->h_poses, feed->imu, sizeof(lii_imu_sample) * size_t(feed->n_imu));
+  return LII_OK;
+}
+// Scan admission: the handle's book-keeping of the scan a prologue launch is about to de-skew.  Returns whether the insert of the
+// hashed voxel filter rides in that launch.
+bool admit_scan(lii_handle h, int n_next, float leaf) {
   extent_discard(h);
   h->n_scan = n_next;
   h->n_body = 0;
   h->n_body_pending = false;
   h->have_search = false;
-  const float fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
-  h->vh_inserted = fuse_filter(h, fuse_leaf);
-  if (h->vh_inserted) h->vh_inserted_leaf = fuse_leaf;
+  h->vh_inserted = fuse_filter(h, leaf);
+  if (h->vh_inserted) h->vh_inserted_leaf = leaf;
+  return h->vh_inserted;
+}
+// A scan in any order: the time-extent reduction in front - the sweep's end and the time-earliest point - adopting the scan on the
+// way; the de-skew then reads the handle's buffer.  Returns the accumulator that holds the extent.
+const unsigned long long* extent_for_unsorted(lii_handle h, const float4*& in, int n, bool adopt) {
+  unsigned long long* e = h->d_extent + 2 * h->extent_sel;
+  launch_time_extent(in, n, e, h->d_extent + 2 * (h->extent_sel ^ 1), adopt ? h->d_scan.get() : nullptr, nullptr, nullptr, 0, h->stream);
+  h->extent_sel ^= 1;
+  in = h->d_scan;
+  return e;
+}
+
+// Behind the de-skew launch of a prologue that pre-loads the control block: the box rows it leaves - or its failure.
+int deskew_launched(lii_handle h, int n_next, const char* what) {
+  h->bbox_rows = (n_next + 255) / 256;
+  h->ctrl_preloaded = true;
+  const hipError_t e_launch = hipGetLastError();
+  if (e_launch == hipSuccess) return LII_OK;
+  h->vh_inserted = false; h->ctrl_preloaded = false;
+  return fail(h, LII_ERR_HIP, std::string(what) + hipGetErrorString(e_launch));
+}
+
+// The prologue of lii_scan_register_imu: IMU forward propagation and de-skew, back to back on the stream.  The host's part is what it
+// knows BEFORE the previous update has ended - the samples - and the state that update left; everything that depends on them (the
+// propagated state, the IMUpose table, the update's control block with state and state_propagat filled in) is formed on the device.
+int imu_prologue(lii_handle h, const JobView& jv, const lii_iekf_opts* opts, const ImuFeed* feed, const lii_state* state, bool adopt, const float4* src_dev,
+                 int n_next) {
+  if (n_next <= 0) return fail(h, LII_ERR_STATE, "lii_scan_register_imu: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
+  int rc = imu_buffers(h);
+  if (rc != LII_OK) return rc;
+  rc = claim_staging(h, true);  // (the samples take the pose table's staging area)
+  if (rc != LII_OK) return rc;
+  fill_ctrl(h, state, state, opts);  // (st / prop of the block on the device are written by k_imu_propagate, not pulled)
+  std::memcpy(h->h_poses, feed->imu, sizeof(lii_imu_sample) * size_t(feed->n_imu));
+  const bool fused = admit_scan(h, n_next, jv.leaf);
   const float4* in = adopt ? src_dev : h->d_scan.get();
-  const unsigned long long* ext = nullptr;
-  if (!sorted) {  // the sweep's end and the time-earliest point of a scan in any order: the time-extent reduction (adopting the scan on the way)
-    unsigned long long* e = h->d_extent + 2 * h->extent_sel;
-    launch_time_extent(in, n_next, e, h->d_extent + 2 * (h->extent_sel ^ 1), adopt ? h->d_scan.get() : nullptr, nullptr, nullptr, 0, h->stream);
-    h->extent_sel ^= 1;
-    ext = e;
-    in = h->d_scan;
-  }
+  const unsigned long long* ext = jv.sorted ? nullptr : extent_for_unsorted(h, in, n_next, adopt);
   ImuPropArgs a = {};
   a.st_in = h->h_ctrl->st;
   a.samples = reinterpret_cast<const double*>(h->h_poses);
@@ -423,7 +518,7 @@ int imu_prologue(lii_handle h, const lii_scan_job* job, const ImuFeed* feed, con
   static_assert(sizeof(lii_imu_noise) == 8 + 19 * sizeof(double), "lii_imu_noise layout");
   std::memcpy(a.noise, h->imu.noise.cov_gyr, sizeof(a.noise));
   a.pcl_beg_time = feed->pcl_beg_time;
-  a.scan = in; a.n_scan = n_next; a.sorted = sorted ? 1 : 0; a.extent = ext;
+  a.scan = in; a.n_scan = n_next; a.sorted = jv.sorted ? 1 : 0; a.extent = ext;
   a.carry_in = h->imu.d_carry(h->imu.carry_sel);
   a.carry_out = h->imu.d_carry(h->imu.carry_sel ^ 1);
   a.poses = h->d_poses;
@@ -433,64 +528,34 @@ int imu_prologue(lii_handle h, const lii_scan_job* job, const ImuFeed* feed, con
   a.host_out = feed->prop_out ? h->imu.h_out.get() : nullptr;
   a.ctrl_src = reinterpret_cast<const uint4*>(h->h_ctrl);
   a.ctrl_dst = reinterpret_cast<uint4*>(h->d_ctrl);
-  static_assert(offsetof(IekfCtrl, solution) % 16 == 0 && offsetof(IekfCtrl, prop) + sizeof(IekfCtrl::prop) == offsetof(IekfCtrl, solution), "IekfCtrl: the two states come first");
-  a.ctrl_from = int(offsetof(IekfCtrl, solution) / 16);
-  a.ctrl_vec = int((sizeof(IekfCtrl) + 15) / 16);
+  a.ctrl_from = ctrl_words().from;
+  a.ctrl_vec = ctrl_words().vec;
   launch_imu_propagate(a, h->stream);
-  {
-    const hipError_t e_prop = hipGetLastError();
-    if (e_prop != hipSuccess) { h->vh_inserted = false; return fail(h, LII_ERR_HIP, std::string("IMU propagation launch: ") + hipGetErrorString(e_prop)); }
-  }
+  const hipError_t e_prop = hipGetLastError();
+  if (e_prop != hipSuccess) { h->vh_inserted = false; return fail(h, LII_ERR_HIP, std::string("IMU propagation launch: ") + hipGetErrorString(e_prop)); }
   h->imu.carry_sel ^= 1;  // the launch is on the stream: the carry it writes is the current one from here on, whatever becomes of the rest of the call
   if (h->prof.kp_active) { rc = kp_mark(h, LII_KP_DESKEW); if (rc != LII_OK) return rc; }
-  DeskewPlan dp = {};
-  dp.in = in; dp.out = h->d_scan; dp.n = n_next; dp.sorted = sorted ? 1 : 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
-  dp.leaf = fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
-#ifdef LII_GAP_TRACE
-  dp.gap = h->d_gran;
-#endif
+  const DeskewPlan dp = deskew_plan(h, in, h->d_scan, n_next, jv.sorted, ext, jv.leaf, fused, DeskewCtrl::ahead);
   launch_deskew_imu_dev(dp, h->d_ctrl->st, h->imu.d_n_poses(), h->d_poses, h->stream);
-  h->bbox_rows = (n_next + 255) / 256;
-  h->ctrl_preloaded = true;
-  const hipError_t e_launch = hipGetLastError();
-  if (e_launch != hipSuccess) { h->vh_inserted = false; h->ctrl_preloaded = false; return fail(h, LII_ERR_HIP, std::string("de-skew launch behind the IMU propagation: ") + hipGetErrorString(e_launch)); }
-  return LII_OK;
+  return deskew_launched(h, n_next, "de-skew launch behind the IMU propagation: ");
 }
 
 // The prologue of lii_scan_register_cv: ONE launch, the CV de-skew whose extra workgroup propagates (k_deskew_cv_prop).  The host hands
 // over the state the previous update left - inside the control block in pinned memory for the extra workgroup, rot_end / bias_g /
 // vel_end by value for the scan workgroups - and never sees the propagated one unless it asks for it.
-int cv_prologue(lii_handle h, const lii_scan_job* job, const CvFeed* cv, const lii_state* state, bool adopt, const float4* src_dev, int n_next, bool sorted) {
+int cv_prologue(lii_handle h, const JobView& jv, const lii_iekf_opts* opts, const CvFeed* cv, const lii_state* state, bool adopt, const float4* src_dev,
+                int n_next) {
   if (n_next <= 0) return fail(h, LII_ERR_STATE, "lii_scan_register_cv: no scan (lii_scan_upload / lii_frame_select / lii_scan_job::scan_dev)");
   int rc = LII_OK;
   if (cv->prop_out) { rc = imu_buffers(h); if (rc != LII_OK) return rc; }
-  if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
-  h->staging_busy = true;
-  fill_ctrl(h, state, state, &job->opts);  // (st / prop of the block on the device are written by the extra workgroup, not pulled; st is what it reads)
-  extent_discard(h);
-  h->n_scan = n_next;
-  h->n_body = 0;
-  h->n_body_pending = false;
-  h->have_search = false;
-  const float fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
-  h->vh_inserted = fuse_filter(h, fuse_leaf);
-  if (h->vh_inserted) h->vh_inserted_leaf = fuse_leaf;
+  rc = claim_staging(h, false);
+  if (rc != LII_OK) return rc;
+  fill_ctrl(h, state, state, opts);  // (st / prop of the block on the device are written by the extra workgroup, not pulled; st is what it reads)
+  const bool fused = admit_scan(h, n_next, jv.leaf);
   const float4* in = adopt ? src_dev : h->d_scan.get();
-  const unsigned long long* ext = nullptr;
-  if (!sorted) {  // a scan in any order: the time-extent reduction in front (adopting the scan on the way), as on lii_scan_register's general path
-    unsigned long long* e = h->d_extent + 2 * h->extent_sel;
-    launch_time_extent(in, n_next, e, h->d_extent + 2 * (h->extent_sel ^ 1), adopt ? h->d_scan.get() : nullptr, nullptr, nullptr, 0, h->stream);
-    h->extent_sel ^= 1;
-    ext = e;
-    in = h->d_scan;
-  }
-  DeskewPlan dp = {};
-  dp.in = in; dp.out = h->d_scan; dp.n = n_next; dp.sorted = sorted ? 1 : 0; dp.extent = ext; dp.bbox_rows = h->d_bbox_rows;
-  dp.leaf = fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
-  dp.ctrl_src = h->h_ctrl; dp.ctrl_dst = h->d_ctrl; dp.ctrl_bytes = (sizeof(IekfCtrl) + 15) / 16 * 16;
-#ifdef LII_GAP_TRACE
-  dp.gap = h->d_gran;
-#endif
+  // (a scan in any order: as on lii_scan_register's general path)
+  const unsigned long long* ext = jv.sorted ? nullptr : extent_for_unsorted(h, in, n_next, adopt);
+  const DeskewPlan dp = deskew_plan(h, in, h->d_scan, n_next, jv.sorted, ext, jv.leaf, fused, DeskewCtrl::pulled);
   CvFuseH f = {};
   std::memcpy(f.rot, state->rot_end, 72);
   std::memcpy(f.bias_g, state->bias_g, 24);
@@ -502,188 +567,59 @@ int cv_prologue(lii_handle h, const lii_scan_job* job, const CvFeed* cv, const l
   f.st_out = h->d_ctrl->st;
   f.prop_out = h->d_ctrl->prop;
   f.host_out = cv->prop_out ? h->imu.h_out.get() : nullptr;
-  static_assert(offsetof(IekfCtrl, solution) % 16 == 0 && offsetof(IekfCtrl, prop) + sizeof(IekfCtrl::prop) == offsetof(IekfCtrl, solution), "IekfCtrl: the two states come first");
-  f.ctrl_from = int(offsetof(IekfCtrl, solution) / 16);
+  f.ctrl_from = ctrl_words().from;
   launch_deskew_cv_prop(dp, f, h->stream);
-  h->bbox_rows = (n_next + 255) / 256;
+  return deskew_launched(h, n_next, "de-skew launch with the CV propagation: ");
+}
+
+// The prologue of a lii_scan_register job whose scan is in ascending time order: ONE launch takes it from wherever it arrived (the
+// caller's device buffer is read in place) to the de-skewed scan with the voxel filter's table filled, and one extra workgroup of it
+// pulls the update's control block over PCIe; the IMU pose table (<= 64 poses) travels in the kernel arguments.  Round 3 needed
+// k_time_extent in front (copy + time extent + pull: 8.9 us per scan).  use_pre: that launch waits on the stream already (prearm_go).
+// A failed launch is reported through *rc and the call goes on to its clean-up; the return value ends the call at once.
+int fast_prologue(lii_handle h, const JobView& jv, const lii_iekf_opts* opts, const lii_state* state, const lii_state* state_prop, bool adopt,
+                  const float4* src_dev, int n_next, bool use_pre, int* rc) {
+  const int rc_claim = claim_staging(h, false);
+  if (rc_claim != LII_OK) return rc_claim;
+  fill_ctrl(h, state, state_prop, opts);
   h->ctrl_preloaded = true;
-  const hipError_t e_launch = hipGetLastError();
-  if (e_launch != hipSuccess) { h->vh_inserted = false; h->ctrl_preloaded = false; return fail(h, LII_ERR_HIP, std::string("de-skew launch with the CV propagation: ") + hipGetErrorString(e_launch)); }
+  const bool fused = admit_scan(h, n_next, jv.leaf);
+  if (use_pre) use_pre = prearm_go(h, state, jv.poses, jv.n_poses);
+  const DeskewPlan dp = deskew_plan(h, adopt ? src_dev : h->d_scan.get(), h->d_scan, n_next, true, nullptr, jv.leaf, fused, DeskewCtrl::pulled);
+  if (use_pre) {
+    // (the launch is on the stream already and has its go)
+  } else if (jv.undistort == 1) {
+    UndistArgH u;
+    std::memcpy(u.endR, state->rot_end, 72);
+    std::memcpy(u.endp, state->pos_end, 24);
+    std::memcpy(u.RLI, state->offset_R_L_I, 72);
+    std::memcpy(u.TLI, state->offset_T_L_I, 24);
+    launch_deskew_imu(dp, reinterpret_cast<const double*>(jv.poses), nullptr, jv.n_poses, u, h->stream);
+  } else {
+    CvArgH a;  // CV model: bias_g = omega, vel_end = v
+    std::memcpy(a.omega, state->bias_g, 24);
+    std::memcpy(a.vel, state->vel_end, 24);
+    std::memcpy(a.endR, state->rot_end, 72);
+    launch_deskew_cv(dp, a, h->stream);
+  }
+  *rc = deskew_launched(h, n_next, "de-skew launch: ");
   return LII_OK;
 }
 
-}  // namespace
-
-// lii_scan_register, and - feed != nullptr - lii_scan_register_imu, - cv != nullptr - lii_scan_register_cv (lii_capi_imu.cpp: their checks
-// are made there; state_prop is not used)
-int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report,
-                                const ImuFeed* feed, const CvFeed* cv) {
-  const char* const who = feed ? "lii_scan_register_imu" : (cv ? "lii_scan_register_cv" : "lii_scan_register");
-  // (struct_size 48: a job of ABI 5, without scan_sorted)
-  // (struct_size 88: ABI 9; 72: ABI 8, without while_waiting; 56: ABI 6 - 7, without next_scan_dev; 48: ABI 5, without scan_sorted)
-  static_assert(sizeof(lii_scan_job) == 88, "lii_scan_job: the sizes of the earlier ABIs are accepted by number");
-  if (!h || !job || (job->struct_size != sizeof(lii_scan_job) && job->struct_size != 72u && job->struct_size != 56u && job->struct_size != 48u) || !state || (!state_prop && !feed && !cv) || job->opts.max_iterations < 1)
-    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
-  // scan_sorted == 2: the scan is put into ascending time order on the device first (scan_sort_into, below), and the call goes on as for
-  // a scan_sorted == 1 job on the handle's own scan buffer
-  const bool sort_first = job->struct_size >= 56u && job->scan_sorted == 2;
-  if (sort_first && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": scan_sorted = 2 is single rank only for now (a communicator is attached)");
-  const bool sorted = job->struct_size >= 56u && (job->scan_sorted == 1 || sort_first);
-  // lii_local_map_set(enabled): this call segments by itself (update_on_device).  Single rank, and not under LII_TEST=host_solve: the
-  // decision reads the device-resident control block, which the host-driven loop does not have.
-  const bool local_map = h->lm.enabled;
-  if (local_map && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is single rank only for now (a communicator is attached)");
-  if (local_map && h->host_solve) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is not available under LII_TEST=host_solve; call lii_local_map_segment");
-  h->scan_buf_idle = false;
-  int rc = LII_OK;
-  const auto t_entry = std::chrono::steady_clock::now();
-  if (h->diag && h->prof.host_us[4] > 0) h->prof.host_us[5] += std::chrono::duration<double, std::micro>(t_entry - h->prof.host_last_return).count();
-  // the scan to adopt: the caller's device buffer (lii_scan_job::scan_dev), or the frame lii_frame_select left where the ingest put it
-  const bool from_job = job->scan_dev != nullptr && job->n_scan_dev > 0;
-  const void* src_dev = from_job ? job->scan_dev : static_cast<const void*>(h->scan_pending);
-  const int src_n = from_job ? job->n_scan_dev : h->scan_pending_n;
-  bool adopt = src_dev != nullptr && src_n > 0;
-  if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": n_scan_dev > max_scan_points");
-  if (from_job) intensity_detach(h);  // (the job's scan_dev replaces the current scan: a scan with intensities is handed over by lii_scan_set_device + lii_scan_intensity_set_device)
-  const int n_next = adopt ? src_n : h->n_scan;
-  // A gated de-skew launch waits on the stream (the previous call enqueued it for the scan its job announced): it is used when THIS
-  // call asks for exactly that, and told to end otherwise - before anything here could wait for the stream.
-  const float leaf_now = job->leaf > 0 ? job->leaf : 0.f;
-  // (the announced scan: the job's own device buffer, or - announced while lii_scan_upload_next was bringing it - the handle's current
-  // scan after lii_scan_advance, de-skewed in place)
-  const void* const cur_dev = from_job ? job->scan_dev : (adopt ? nullptr : static_cast<const void*>(h->d_scan));
-  const int cur_n = from_job ? job->n_scan_dev : h->n_scan;
-  bool use_pre = h->pre.armed && sorted && job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= lii::kGateMaxPoses &&
-                 cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && leaf_now == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
-                 h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, leaf_now) == h->pre.fuse;
-  if (feed || cv || sort_first || local_map) use_pre = false;  // (lii_scan_register_imu / _cv, a job that sorts, a handle with the local map enabled: a waiting launch is ended, and nothing is announced - next_scan_dev is ignored)
-  if (!use_pre) prearm_cancel(h);
-  // ... and what this job announces for the next call (update_on_device arms it behind the passes)
-  h->pre.want_dev = nullptr;
-  if (!feed && !cv && !sort_first && !local_map && job->struct_size >= 72u && job->next_scan_dev && job->next_n_scan > 0 && job->next_n_scan <= h->cfg.max_scan_points && h->pre.enabled &&
-      sorted && job->undistort == 1) {
-    h->pre.want_dev = job->next_scan_dev; h->pre.want_n = job->next_n_scan; h->pre.want_leaf = leaf_now; h->pre.want_late = false;
-  } else if (!feed && !cv && !sort_first && !local_map && h->n_scan_next > 0 && h->d_scan_next && h->pre.enabled && sorted && job->undistort == 1 && !from_job) {
-    // a scan is on its way through lii_scan_upload_next: it is the next call's (after lii_scan_advance), de-skewed where it lands
-    h->pre.want_dev = h->d_scan_next; h->pre.want_n = h->n_scan_next; h->pre.want_leaf = leaf_now; h->pre.want_late = true;
-  }
-  // A scan in ascending time order: ONE launch takes it from wherever it arrived (the caller's device buffer is read in place)
-  // to the de-skewed scan with the voxel filter's table filled, and one extra workgroup of it pulls the update's control block
-  // over PCIe; the IMU pose table (<= 64 poses) travels in the kernel arguments.  Round 3 needed k_time_extent in front (copy +
-  // time extent + pull: 8.9 us per scan).
-  h->prof.kp_active = h->prof.prof_mode == 3 && !h->host_solve;
-  h->prof.kp_n = 0;
-  if (h->prof.kp_active) { rc = kp_mark(h, feed ? LII_KP_PROPAGATE : LII_KP_DESKEW); if (rc != LII_OK) { h->prof.kp_active = false; return rc; } }
-  const bool fast = sorted && !h->host_solve && n_next > 0 && !h->no_fast_prologue &&
-                    ((job->undistort == 1 && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= 64) || job->undistort == 2);
-  if (use_pre && !fast) { prearm_cancel(h); use_pre = false; }  // (cannot happen with the conditions above; a waiting launch must never be left behind a call that will not feed it)
-  if (job->undistort != 0 && job->undistort != 1 && job->undistort != 2) return fail(h, LII_ERR_INVALID, std::string(who) + ": undistort must be 0, 1 or 2");
-  const auto t_first = std::chrono::steady_clock::now();
-  if (sort_first && n_next > 0) {
-    // (behind the first profiling mark: lii_set_profiling(h, 3) counts these launches where it counts the time-extent launch of a scan in any order)
-    rc = scan_sort_into(h, adopt ? static_cast<const float4*>(src_dev) : h->d_scan.get(), n_next);
-    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
-    extent_discard(h);  // (the sorted scan in d_scan is the current one: a selected frame has been read, an extent of the old order is void)
-    h->n_scan = n_next;
-    h->bbox_rows = 0;
-    adopt = false;
-    src_dev = nullptr;
-  }
-  if (feed) {
-    rc = imu_prologue(h, job, feed, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
-    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
-  } else if (cv) {
-    rc = cv_prologue(h, job, cv, state, adopt, static_cast<const float4*>(src_dev), n_next, sorted);
-    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
-  } else if (fast) {
-    if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));  // (a call that failed half way left the buffer in use)
-    h->staging_busy = true;
-    fill_ctrl(h, state, state_prop, &job->opts);
-    h->ctrl_preloaded = true;
-    extent_discard(h);
-    h->n_scan = n_next;
-    h->n_body = 0;
-    h->n_body_pending = false;
-    h->have_search = false;
-    const float fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
-    h->vh_inserted = fuse_filter(h, fuse_leaf);
-    if (h->vh_inserted) h->vh_inserted_leaf = fuse_leaf;
-    if (use_pre) {
-      // GO - unless the launch gave up in this very moment (then the scan is launched below like any other) - and the record: straight
-      // into device memory (large BAR), payload, then the tags, line 0's last, a store fence between the three
-      h->pre.armed = false;
-      if (gate_move(h->pre.state, h->pre.seq, lii::kGateGo)) {
-        h->pre.n_used++;
-        const int K = job->n_imu_poses;
-        const int n_pay = 25 + 22 * K, n_lines = (n_pay + 6) / 7;
-        double pay[7 * lii::kGateLines];
-        pay[0] = double(K);
-        std::memcpy(pay + 1, state->rot_end, 72);
-        std::memcpy(pay + 10, state->pos_end, 24);
-        std::memcpy(pay + 13, state->offset_R_L_I, 72);
-        std::memcpy(pay + 22, state->offset_T_L_I, 24);
-        std::memcpy(pay + 25, job->imu_poses, sizeof(lii_pose6d) * size_t(K));
-        for (int e = n_pay; e < 7 * n_lines; e++) pay[e] = 0.0;
-        volatile double* rec = h->pre.d_ring + size_t(h->pre.seq % lii::kGateRing) * lii::kGateLines * 8;
-        double tag;
-        const unsigned long long tagw = (h->pre.seq << 2) | lii::kGateGo;
-        std::memcpy(&tag, &tagw, 8);
-        for (int l = 0; l < n_lines; l++)
-          for (int c = 0; c < 7; c++) rec[8 * l + c] = pay[7 * l + c];
-        __builtin_ia32_sfence();
-        for (int l = 1; l < n_lines; l++) rec[8 * l + 7] = tag;
-        __builtin_ia32_sfence();
-        {  // (line 0's tag carries K in its top byte: lii_scan.hip, k_deskew_imu_gated)
-          const unsigned long long tag0 = tagw | ((unsigned long long)K << 56);
-          double t0d;
-          std::memcpy(&t0d, &tag0, 8);
-          rec[7] = t0d;
-        }
-        __builtin_ia32_sfence();
-      } else {
-        use_pre = false;
-        h->pre.n_expired++;
-      }
-    }
-    DeskewPlan dp = {};
-    dp.in = adopt ? static_cast<const float4*>(src_dev) : h->d_scan;
-    dp.out = h->d_scan; dp.n = n_next; dp.sorted = 1; dp.extent = nullptr; dp.bbox_rows = h->d_bbox_rows;
-    dp.leaf = fuse_leaf; dp.vh = h->vh_inserted ? &h->vh : nullptr;
-    dp.ctrl_src = h->h_ctrl; dp.ctrl_dst = h->d_ctrl; dp.ctrl_bytes = (sizeof(IekfCtrl) + 15) / 16 * 16;
-#ifdef LII_GAP_TRACE
-    dp.gap = h->d_gran;
-#endif
-    if (use_pre) {
-      // (the launch is on the stream already and has its go)
-    } else if (job->undistort == 1) {
-      UndistArgH u;
-      std::memcpy(u.endR, state->rot_end, 72);
-      std::memcpy(u.endp, state->pos_end, 24);
-      std::memcpy(u.RLI, state->offset_R_L_I, 72);
-      std::memcpy(u.TLI, state->offset_T_L_I, 24);
-      launch_deskew_imu(dp, reinterpret_cast<const double*>(job->imu_poses), nullptr, job->n_imu_poses, u, h->stream);
-    } else {
-      CvArgH a;  // CV model: bias_g = omega, vel_end = v
-      std::memcpy(a.omega, state->bias_g, 24);
-      std::memcpy(a.vel, state->vel_end, 24);
-      std::memcpy(a.endR, state->rot_end, 72);
-      launch_deskew_cv(dp, a, h->stream);
-    }
-    h->bbox_rows = (n_next + 255) / 256;
-    const hipError_t e_launch = hipGetLastError();
-    if (e_launch != hipSuccess) { h->vh_inserted = false; h->ctrl_preloaded = false; rc = fail(h, LII_ERR_HIP, std::string("de-skew launch: ") + hipGetErrorString(e_launch)); }
-  } else {
-  if (job->undistort == 1 && !h->host_solve && job->imu_poses && job->n_imu_poses >= 2 && job->n_imu_poses <= 1024 && n_next > 0) {
+// The prologue of every other lii_scan_register job (a scan in any order, LII_TEST=host_solve / no_fast, a long pose table, no
+// de-skew): control block and pose staging, then the public entry points.  *rc and the return value: as for fast_prologue.
+int general_prologue(lii_handle h, const JobView& jv, const lii_iekf_opts* opts, const lii_state* state, const lii_state* state_prop, bool adopt,
+                     const void* src_dev, int src_n, int n_next, int* rc) {
+  if (jv.undistort == 1 && !h->host_solve && jv.poses && jv.n_poses >= 2 && jv.n_poses <= 1024 && n_next > 0) {
     // the control block of the update AND the pose table of the de-skew (they sit behind each other) reach the device once.
     // The staging buffer is free again: the previous call returned after its stopping pass, which runs behind the kernel
     // that read the buffer - unless that call failed half way (then wait).  No event: recording one between the de-skew and
     // the voxel filter cost a ~5 us bubble on the device per scan.
-    if (h->staging_busy) HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev_poses));  // a pose table uploaded by a stand-alone lii_undistort_imu (long done)
-    h->staging_busy = true;
-    fill_ctrl(h, state, state_prop, &job->opts);
-    std::memcpy(h->h_poses, job->imu_poses, sizeof(lii_pose6d) * size_t(job->n_imu_poses));
-    const size_t bytes = kCtrlBytes + sizeof(lii_pose6d) * size_t(job->n_imu_poses);
+    const int rc_claim = claim_staging(h, true);
+    if (rc_claim != LII_OK) return rc_claim;
+    fill_ctrl(h, state, state_prop, opts);
+    std::memcpy(h->h_poses, jv.poses, sizeof(lii_pose6d) * size_t(jv.n_poses));
+    const size_t bytes = kCtrlBytes + sizeof(lii_pose6d) * size_t(jv.n_poses);
     if (adopt || !h->extent_valid) {
       h->ctrl_pending = (bytes + 15) / 16 * 16;  // rides in the scan's first kernel (k_time_extent), which is launched below
     } else {
@@ -694,36 +630,112 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
   }
   if (adopt) {
     const bool keep = h->inten.have;  // (a selected ingest frame moves into the handle's buffer: its intensities, copied when it was selected, stay)
-    rc = lii_scan_set_device(h, src_dev, src_n);
-    if (rc == LII_OK) h->inten.have = keep;
-    if (rc != LII_OK) { h->ctrl_pending = 0; h->poses_preloaded = h->ctrl_preloaded = false; return rc; }
+    const int rc_set = lii_scan_set_device(h, src_dev, src_n);
+    if (rc_set == LII_OK) h->inten.have = keep;
+    if (rc_set != LII_OK) { h->ctrl_pending = 0; h->poses_preloaded = h->ctrl_preloaded = false; return rc_set; }
   }
-  if (job->undistort == 1) {
-    h->fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;  // (the voxel filter follows in this call: its insert may ride in the de-skew)
-    rc = lii_undistort_imu(h, job->imu_poses, job->n_imu_poses, state->rot_end, state->pos_end, state->offset_R_L_I,
-                           state->offset_T_L_I);
+  if (jv.undistort == 1 || jv.undistort == 2) {
+    h->fuse_leaf = jv.leaf;  // (the voxel filter follows in this call: its insert may ride in the de-skew)
+    *rc = jv.undistort == 1 ? lii_undistort_imu(h, jv.poses, jv.n_poses, state->rot_end, state->pos_end, state->offset_R_L_I, state->offset_T_L_I)
+                            : lii_undistort_cv(h, state->bias_g, state->vel_end, state->rot_end);  // CV model: bias_g = omega, vel_end = v
     h->fuse_leaf = 0.f;
-    if (rc != LII_OK) h->vh_inserted = false;
-  } else if (job->undistort == 2) {
-    h->fuse_leaf = job->leaf > 0 ? job->leaf : 0.f;
-    rc = lii_undistort_cv(h, state->bias_g, state->vel_end, state->rot_end);  // CV model: bias_g = omega, vel_end = v
-    h->fuse_leaf = 0.f;
-    if (rc != LII_OK) h->vh_inserted = false;
+    if (*rc != LII_OK) h->vh_inserted = false;
   }
+  return LII_OK;
+}
+
+// LII_DIAG: the host's times of one call (lii_context::prof.host_us)
+void note_host_times(lii_handle h, std::chrono::steady_clock::time_point t_entry, std::chrono::steady_clock::time_point t_first,
+                     std::chrono::steady_clock::time_point t_pre) {
+  if (!h->diag) return;
+  const auto t_end = std::chrono::steady_clock::now();
+  h->prof.host_us[0] += std::chrono::duration<double, std::micro>(t_first - t_entry).count();
+  h->prof.host_us[1] += std::chrono::duration<double, std::micro>(t_pre - t_entry).count();
+  h->prof.host_us[2] += h->prof.host_loop_enq_us;
+  h->prof.host_us[3] += std::chrono::duration<double, std::micro>(t_end - t_entry).count();
+  h->prof.host_us[4] += 1;
+  h->prof.host_last_return = t_end;
+}
+
+}  // namespace
+
+// lii_scan_register, and - feed != nullptr - lii_scan_register_imu, - cv != nullptr - lii_scan_register_cv (lii_capi_imu.cpp: their checks
+// are made there; state_prop is not used)
+int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state* state, const lii_state* state_prop, lii_iekf_report* report,
+                                const ImuFeed* feed, const CvFeed* cv) {
+  const char* const who = feed ? "lii_scan_register_imu" : (cv ? "lii_scan_register_cv" : "lii_scan_register");
+  if (!h || !job || !job_size_ok(job->struct_size) || !state || (!state_prop && !feed && !cv) || job->opts.max_iterations < 1)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments");
+  const JobView jv = job_view(job);
+  if (jv.sort_first && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": scan_sorted = 2 is single rank only for now (a communicator is attached)");
+  // lii_local_map_set(enabled): this call segments by itself (update_on_device).  Single rank, and not under LII_TEST=host_solve: the
+  // decision reads the device-resident control block, which the host-driven loop does not have.
+  const bool local_map = h->lm.enabled;
+  if (local_map && (h->net.comm || h->net.n_ranks > 1)) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is single rank only for now (a communicator is attached)");
+  if (local_map && h->host_solve) return fail(h, LII_ERR_STATE, std::string(who) + ": the local map (lii_local_map_set) is not available under LII_TEST=host_solve; call lii_local_map_segment");
+  h->scan_buf_idle = false;
+  int rc = LII_OK;
+  const auto t_entry = std::chrono::steady_clock::now();
+  if (h->diag && h->prof.host_us[4] > 0) h->prof.host_us[5] += std::chrono::duration<double, std::micro>(t_entry - h->prof.host_last_return).count();
+  // the scan to adopt: the caller's device buffer (lii_scan_job::scan_dev), or the frame lii_frame_select left where the ingest put it
+  const bool from_job = jv.scan_dev != nullptr && jv.n_scan_dev > 0;
+  const void* src_dev = from_job ? jv.scan_dev : static_cast<const void*>(h->scan_pending);
+  const int src_n = from_job ? jv.n_scan_dev : h->scan_pending_n;
+  bool adopt = src_dev != nullptr && src_n > 0;
+  // (this refusal comes BEFORE a waiting launch is told to end, the undistort range check below behind it: both stay where they were)
+  if (adopt && src_n > h->cfg.max_scan_points) return fail(h, LII_ERR_CAPACITY, std::string(who) + ": n_scan_dev > max_scan_points");
+  if (from_job) intensity_detach(h);  // (the job's scan_dev replaces the current scan: a scan with intensities is handed over by lii_scan_set_device + lii_scan_intensity_set_device)
+  const int n_next = adopt ? src_n : h->n_scan;
+  // A gated de-skew launch waits on the stream (the previous call enqueued it for the scan its job announced): it is used when THIS
+  // call asks for exactly that, and told to end otherwise - before anything here could wait for the stream.
+  // (the announced scan: the job's own device buffer, or - announced while lii_scan_upload_next was bringing it - the handle's current
+  // scan after lii_scan_advance, de-skewed in place)
+  const void* const cur_dev = from_job ? jv.scan_dev : (adopt ? nullptr : static_cast<const void*>(h->d_scan));
+  const int cur_n = from_job ? jv.n_scan_dev : h->n_scan;
+  // (lii_scan_register_imu / _cv, a job that sorts, a handle with the local map enabled: a waiting launch is ended, and nothing is announced)
+  const bool may_announce = !feed && !cv && !jv.sort_first && !local_map;
+  bool use_pre = may_announce && h->pre.armed && jv.sorted && jv.undistort == 1 && jv.poses && jv.n_poses >= 2 && jv.n_poses <= lii::kGateMaxPoses &&
+                 cur_dev != nullptr && cur_dev == h->pre.scan_dev && cur_n == h->pre.n && h->pre.late == !from_job && jv.leaf == h->pre.leaf && !h->host_solve && !h->no_fast_prologue &&
+                 h->prof.prof_mode != 3 && !h->staging_busy && fuse_filter(h, jv.leaf) == h->pre.fuse;
+  if (!use_pre) prearm_cancel(h);
+  prearm_wanted(h, jv, may_announce, from_job);
+  h->prof.kp_active = h->prof.prof_mode == 3 && !h->host_solve;
+  h->prof.kp_n = 0;
+  if (h->prof.kp_active) { rc = kp_mark(h, feed ? LII_KP_PROPAGATE : LII_KP_DESKEW); if (rc != LII_OK) { h->prof.kp_active = false; return rc; } }
+  const bool fast = jv.sorted && !h->host_solve && n_next > 0 && !h->no_fast_prologue &&
+                    ((jv.undistort == 1 && jv.poses && jv.n_poses >= 2 && jv.n_poses <= 64) || jv.undistort == 2);
+  if (use_pre && !fast) { prearm_cancel(h); use_pre = false; }  // (cannot happen with the conditions above; a waiting launch must never be left behind a call that will not feed it)
+  if (jv.undistort != 0 && jv.undistort != 1 && jv.undistort != 2) return fail(h, LII_ERR_INVALID, std::string(who) + ": undistort must be 0, 1 or 2");
+  const auto t_first = std::chrono::steady_clock::now();
+  if (jv.sort_first && n_next > 0) {
+    // (behind the first profiling mark: lii_set_profiling(h, 3) counts these launches where it counts the time-extent launch of a scan in any order)
+    rc = scan_sort_into(h, adopt ? static_cast<const float4*>(src_dev) : h->d_scan.get(), n_next);
+    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
+    extent_discard(h);  // (the sorted scan in d_scan is the current one: a selected frame has been read, an extent of the old order is void)
+    h->n_scan = n_next;
+    h->bbox_rows = 0;
+    adopt = false;
+    src_dev = nullptr;
+  }
+  const float4* const src4 = static_cast<const float4*>(src_dev);
+  if (feed || cv) {
+    rc = feed ? imu_prologue(h, jv, &job->opts, feed, state, adopt, src4, n_next) : cv_prologue(h, jv, &job->opts, cv, state, adopt, src4, n_next);
+    if (rc != LII_OK) { h->prof.kp_active = false; return rc; }
+  } else {
+    const int rc_now = fast ? fast_prologue(h, jv, &job->opts, state, state_prop, adopt, src4, n_next, use_pre, &rc)
+                            : general_prologue(h, jv, &job->opts, state, state_prop, adopt, src_dev, src_n, n_next, &rc);
+    if (rc_now != LII_OK) return rc_now;
   }
   if (h->ctrl_preloaded && h->ctrl_pending) {  // no kernel picked the block up (cannot happen with the conditions above; a guard)
     HIPCHK(h, hipMemcpyAsync(h->d_ctrl, h->h_ctrl, h->ctrl_pending, hipMemcpyHostToDevice, h->stream));
     h->ctrl_pending = 0;
   }
-  if (rc == LII_OK) rc = job->leaf > 0 ? lii_downsample(h, job->leaf, nullptr, nullptr) : lii_downsample_skip(h, nullptr);
+  if (rc == LII_OK) rc = jv.leaf > 0 ? lii_downsample(h, jv.leaf, nullptr, nullptr) : lii_downsample_skip(h, nullptr);
   const auto t_pre = std::chrono::steady_clock::now();
-  const bool map_update = job->struct_size >= 56u && job->map_update == 1;
-  h->map_after_update = map_update && !h->host_solve;
+  h->map_after_update = jv.map_update && !h->host_solve;
   h->map_enqueued_early = false;
-  // lii_scan_job::while_waiting (ABI 9): update_on_device calls it when its launches are out, before it waits for the result; an
-  // arrangement without that wait (LII_TEST=host_solve) calls it behind the update - once per call that got this far, never otherwise
-  h->wait_hook = (rc == LII_OK && job->struct_size >= 88u) ? job->while_waiting : nullptr;
-  h->wait_hook_arg = job->struct_size >= 88u ? job->while_waiting_arg : nullptr;
+  h->wait_hook = rc == LII_OK ? jv.while_waiting : nullptr;  // (run_wait_hook)
+  h->wait_hook_arg = jv.while_waiting_arg;
   h->lm.in_job = local_map && rc == LII_OK;
   if (rc == LII_OK) rc = lii_iekf_update(h, state, state_prop ? state_prop : state, &job->opts, report);
   if (h->lm.in_job) {
@@ -733,30 +745,18 @@ int lii_impl::scan_register_job(lii_handle h, const lii_scan_job* job, lii_state
     else h->lm.counts_pending = true;
     h->lm.in_job = false;
   }
-  if (h->wait_hook) {
-    void (*hook)(void*) = h->wait_hook;
-    h->wait_hook = nullptr;
-    hook(h->wait_hook_arg);
-  }
+  run_wait_hook(h, false);
   h->map_after_update = false;
   // map_incremental behind the update: already enqueued behind its passes (update_on_device), or made now
-  if (rc == LII_OK && map_update && !h->map_enqueued_early) rc = lii_map_incremental(h, state, nullptr, nullptr);
+  if (rc == LII_OK && jv.map_update && !h->map_enqueued_early) rc = lii_map_incremental(h, state, nullptr, nullptr);
   h->map_enqueued_early = false;
   h->poses_preloaded = h->ctrl_preloaded = false;  // also on the error paths
   h->prof.kp_active = false;
-  if (h->diag) {
-    const auto t_end = std::chrono::steady_clock::now();
-    h->prof.host_us[0] += std::chrono::duration<double, std::micro>(t_first - t_entry).count();
-    h->prof.host_us[1] += std::chrono::duration<double, std::micro>(t_pre - t_entry).count();
-    h->prof.host_us[2] += h->prof.host_loop_enq_us;
-    h->prof.host_us[3] += std::chrono::duration<double, std::micro>(t_end - t_entry).count();
-    h->prof.host_us[4] += 1;
-    h->prof.host_last_return = t_end;
-  }
-  // lii_scan_register_imu: the propagated state, as k_imu_propagate left it in mapped host memory (it ran in front of the passes whose result has arrived)
-  if (rc == LII_OK && feed && feed->prop_out) std::memcpy(feed->prop_out, h->imu.h_out.get(), sizeof(lii_state));
-  // lii_scan_register_cv: likewise, as the extra workgroup of k_deskew_cv_prop left it
-  if (rc == LII_OK && cv && cv->prop_out) std::memcpy(cv->prop_out, h->imu.h_out.get(), sizeof(lii_state));
+  note_host_times(h, t_entry, t_first, t_pre);
+  // the propagated state, as k_imu_propagate (lii_scan_register_imu) / the extra workgroup of k_deskew_cv_prop (lii_scan_register_cv) left
+  // it in mapped host memory (it ran in front of the passes whose result has arrived)
+  lii_state* const prop_out = feed ? feed->prop_out : (cv ? cv->prop_out : nullptr);
+  if (rc == LII_OK && prop_out) std::memcpy(prop_out, h->imu.h_out.get(), sizeof(lii_state));
   return rc;
 }
 
@@ -857,13 +857,7 @@ int lii_iekf_update(lii_handle h, lii_state* state, const lii_state* state_prop,
     host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stop) { it++; break; }
   }
-  if (report) {
-    report->iterations = it;
-    report->searches = searches;
-    report->effect_num = int(ne[90]);
-    report->converged = converged ? 1 : 0;
-    std::memcpy(report->normal_eq, ne, sizeof(ne));
-  }
+  fill_report(report, it, searches, int(ne[90]), converged ? 1 : 0, ne);
   h->prof.timings[3] = host_ms;
   h->prof.timings[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return LII_OK;

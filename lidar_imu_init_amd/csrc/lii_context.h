@@ -465,6 +465,12 @@ RegistrationBuffers reg_buffers(const lii_context* c);
 PoseArg pose_of(const lii_state& s);
 int resolve_n_body(lii_handle h);
 bool fuse_filter(lii_handle h, float leaf);  // does the de-skew of this scan fill the hashed voxel filter's table on the way?
+// The one place that fills a DeskewPlan (bbox_rows, vh, the control-block pull and the LII_GAP_TRACE field are its business).  ctrl:
+// none - a stand-alone de-skew (lii_undistort_imu / _cv); ahead - a registration call whose control block a launch in front has pulled
+// (k_imu_propagate); pulled - a registration call whose de-skew launch pulls the block itself, with one extra workgroup.
+enum class DeskewCtrl { none, ahead, pulled };
+DeskewPlan deskew_plan(lii_handle h, const float4* in, float4* out, int n, bool sorted, const unsigned long long* extent, float leaf, bool fused,
+                       DeskewCtrl ctrl);
 int pcl_order(lii_handle h, const int** perm);
 void extent_discard(lii_handle h);
 // `src` (n points: a caller's device buffer, a frame of the ingest, or d_scan itself) -> d_scan in ascending time order, stable; the
@@ -475,6 +481,8 @@ int intensity_buffers(lii_handle h);  // creates lii_context::inten's scan / dow
 int scan_materialize(lii_handle h);  // a frame selected by lii_frame_select and not read yet -> d_scan (lii_scan_set_device)
 bool gate_move(lii::GateState* st, unsigned long long seq, unsigned long long to);  // the state word: armed -> `to`, if still armed
 void prearm_cancel(lii_handle h);  // a gated de-skew launch that waits on the stream is told to end (every entry point that uses the stream calls this first)
+void prearm_arm(lii_handle h);  // update_on_device: the launch for the scan the job announced (lii_context::pre.want_*) goes out behind the passes, gate armed
+bool prearm_go(lii_handle h, const lii_state* state, const lii_pose6d* poses, int K);  // the gate to GO and the record into the ring; false: the launch had given up
 unsigned long long* extent_of_scan(lii_handle h);
 MailboxView mailbox_view(lii_handle h);
 lii::GatherView gather_view(lii_handle h);  // .peers == nullptr: this job has no list exchange (single rank, host-memory mailbox, RCCL)
