@@ -195,7 +195,7 @@ int lii_local_map_segment(lii_handle h, const double pos_end[3], lii_local_map_i
  *   When: as the delete runs.  The reference hands the same points over LATER - when a rebuild happens to flatten the sub-tree that holds
  *   them (ikd_Tree.cpp:1242-1249 sits in flatten) - so its timing depends on the shape of its tree; the multiset over a run is the same.
  *   Order: unspecified - the buffer is a multiset of the map's stored float bits of x, y, z (16-byte records on the device, the fourth
- *   float unspecified).
+ *   float the point's intensity: what lii_map_build_xyzi / lii_map_add_points_xyzi stored with it, 0.0f for every other point).
  *   Overflow: the delete always completes, the map never depends on the buffer.  Points that find no room are not stored and are counted in
  *   lost_total; nothing already held is overwritten.  From then on lii_map_removed_acquire / _view deliver what the buffer holds AND return
  *   LII_ERR_CAPACITY, until an acquire with clear != 0 has emptied it (the rule of lii_publish_saved).
@@ -337,6 +337,77 @@ int lii_map_delete_points(lii_handle h, const void* xyz, int32_t n, int32_t stri
 int lii_map_delete_points_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes);
 int lii_map_range(lii_handle h, float range6[6] /* min xyz, max xyz */);
 int lii_map_box_search(lii_handle h, const float* boxes, int32_t n_boxes, float* xyz_out, int32_t capacity, int32_t* n);
+/* ---- map points keep their intensity.  The reference's tree stores whole PointType values: map_incremental pushes feats_down_world[i]
+ * (src/laserMapping.cpp:516-559), into which pointBodyToWorld has copied the intensity (:219); Add_Points keeps downsample_result, a whole
+ * point - the new one or a stored one (include/ikd-Tree/ikd_Tree.cpp:381-456); Nearest_Search (:349-379), Search_by_range (:970-998),
+ * flatten (:1229-1251) and acquire_removed_points (:522-534) hand whole points back.  The device map's records are float4: the fourth
+ * word is the point's intensity.
+ * RULE.  A stored point's intensity is the intensity of the input point that the existing rules keep - through every layer that moves,
+ * chooses, squeezes, parks, rebuilds or returns a map point.  No rule that decides which xyz survives changes; where such a choice is
+ * unspecified (bit-equal twins, equal d2) the intensity that goes with it is unspecified in the same way.  Points stored through
+ * lii_map_build and lii_map_add_points - and, while lii_map_intensity_set is off, through lii_map_build_from_scan, lii_map_incremental and
+ * a registration's own map update - carry 0.0f: lii_publish_saved_pcd's convention for "none kept".  LII_ABI_VERSION stays 9: every
+ * entry point below is new.
+ * Scan-driven updates:
+ *   lii_map_intensity_set / lii_map_intensity_get  durable handle state, OFF by default.  ON: the updates a scan feeds - lii_map_incremental
+ *                            (src/laserMapping.cpp:516-559), a registration's own lii_scan_job::map_update, lii_map_build_from_scan (:921-931)
+ *                            - take each inserted point's intensity from the down-sampled cloud's (what pointBodyToWorld copies, :219; the
+ *                            values lii_scan_intensity_download(h, 1) returns): one more load per inserted point, no launch added.  A cloud
+ *                            that carried none (nothing attached when the voxel filter ran; a job that adopted scan_dev) stores 0.0f.  The
+ *                            world points of lii_scan_download(h, 2) keep their fourth float 0.  OFF: those calls enqueue exactly the launches
+ *                            and instantiations they did before the switch existed.
+ *                            Refusals.  LII_ERR_STATE: a communicator is attached (single rank for now; lii_comm_init / lii_comm_init_ex on
+ *                            a handle with the switch on refuse likewise); from inside lii_scan_job::while_waiting.  LII_ERR_INVALID: on
+ *                            not 0 / 1, NULL arguments.  It works under LII_TEST=host_solve (where no intensities can be attached: zeros).
+ *                            A job on such a handle keeps its pre-armed prologue: the map update is not part of it.
+ *   A handle whose map may hold intensities - an _xyzi input, or the switch, since the last lii_map_reset / lii_map_build - runs the
+ *   carrying instantiations of the fold and insert kernels in every later update, 3-float batches and recoveries included (same results:
+ *   their fourth word is 0), until lii_map_reset or lii_map_build starts an empty or plain map.
+ * Inputs:
+ *   lii_map_build_xyzi       <- ikdtree.Build(feats_down_world->points), src/laserMapping.cpp:921-931: lii_map_build, plus a float read
+ *                            at intensity_offset bytes into each record (12 with stride 16 for packed xyzi, 32 with stride 48 for
+ *                            pcl::PointXYZINormal, include/common_lib.h:37).
+ *   lii_map_add_points_xyzi  <- ikdtree.Add_Points(PointToAdd, downsample_on), ikd_Tree.cpp:381-456: lii_map_add_points likewise.  With
+ *                            down-sampling the voxel keeps its closest-to-centre point WITH that point's intensity (downsample_result,
+ *                            :400-420); a stored point that wins keeps its own.
+ *   LII_ERR_INVALID, nothing changed: an intensity_offset that is negative, not a multiple of 4, overlaps x / y / z (< 12) or has
+ *   offset + 4 > stride_bytes; everything lii_map_build / lii_map_add_points refuse.  A NaN intensity is stored as given, bit for bit: only
+ *   coordinates decide anything.
+ * Outputs - each is its sibling with 4 floats a row (x, y, z, intensity) where the sibling has 3: the same counts, order rules,
+ * capacities (in rows), errors and observer guarantees; they return the stored word whatever entry point stored it:
+ *   lii_map_download_xyzi         <- flatten / PCL_Storage (ikd_Tree.cpp:1229-1251)
+ *   lii_map_nearest_xyzi, lii_map_nearest_xyzi_dev  <- Nearest_Points[i].intensity of Nearest_Search (ikd_Tree.cpp:349-379); the rows from
+ *                                 count[i] on are zeros
+ *   lii_map_radius_xyzi, lii_map_radius_xyzi_dev    <- the ball query, LII_RADIUS_SORTED included
+ *   lii_map_box_search_xyzi       <- Search_by_range (ikd_Tree.cpp:970-998)
+ *   lii_map_removed_acquire_xyzi  <- acquire_removed_points (ikd_Tree.cpp:522-534) / _featsArray (src/laserMapping.cpp:249-254)
+ *   The host forms of nearest and radius stage 20 bytes a row through the buffers of their siblings (16 a row there): their chunks are cut
+ *   at four fifths of the siblings' rows, the buffers keep their bound.
+ * lii_map_pcd <- publish_map / featsFromMap (src/laserMapping.cpp:638-645: the save of the down-sampled map the reference meant and never
+ *               fills) as pcd_writer.writeBinary (:609) would write it: the live map as the 32-byte rows lii_pcd_header describes - x y z,
+ *               normals 0, intensity the stored word, curvature 0 - in lii_map_download's order rule (none).  Gathered and repacked on the
+ *               device, brought over through the staging of lii_publish_saved_pcd, 65 536 rows at a time.  *n_points is ALWAYS the live
+ *               count; rows_out == NULL returns the count only; capacity_bytes < 32 x *n_points is LII_ERR_CAPACITY and nothing is
+ *               written.  An OBSERVER in the sense of lii_map_nearest; from inside lii_scan_job::while_waiting: LII_ERR_STATE. */
+int lii_map_build_xyzi(lii_handle h, const void* pts, int32_t n, int32_t stride_bytes, int32_t intensity_offset);
+int lii_map_add_points_xyzi(lii_handle h, const void* pts, int32_t n, int32_t stride_bytes, int32_t intensity_offset,
+                            int32_t downsample_on, int32_t* n_added);
+int lii_map_download_xyzi(lii_handle h, float* xyzi_out, int32_t capacity, int32_t* n);
+int lii_map_nearest_xyzi(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
+                         float* pts_out /* n*k*4 */, float* d2_out /* n*k */, int32_t* count_out /* n */);
+int lii_map_nearest_xyzi_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, int32_t k, double max_dist,
+                             float* pts_dev, float* d2_dev, int32_t* count_dev);
+int lii_map_radius_xyzi(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
+                        int64_t* offsets_out /* n + 1, required */, float* pts_out /* capacity x 4, may be NULL */,
+                        float* d2_out /* capacity, may be NULL */, int64_t capacity, int64_t* total /* required */);
+int lii_map_radius_xyzi_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
+                            int64_t* offsets_dev /* n + 1 */, float* pts_dev, float* d2_dev, int64_t capacity,
+                            int64_t* total_dev /* one word */);
+int lii_map_box_search_xyzi(lii_handle h, const float* boxes, int32_t n_boxes, float* xyzi_out, int32_t capacity, int32_t* n);
+int lii_map_removed_acquire_xyzi(lii_handle h, float* xyzi_out, int32_t capacity, int32_t* n, int32_t clear);
+int lii_map_pcd(lii_handle h, void* rows_out, int64_t capacity_bytes, int32_t* n_points);
+int lii_map_intensity_set(lii_handle h, int32_t on);
+int lii_map_intensity_get(lii_handle h, int32_t* on);
 
 /* ---------------------------------------------------------------- scan in / undistortion / down-sampling
  * lii_scan_upload: host AoS -> device float4 (x,y,z,t_ms).  For pcl::PointXYZINormal use stride 48,

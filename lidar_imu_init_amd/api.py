@@ -162,19 +162,30 @@ _DECLS = {
     "lii_synchronize": (C.c_int, [C.c_void_p]),
     "lii_map_reset": (C.c_int, [C.c_void_p]),
     "lii_map_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "lii_map_build_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_map_add_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_add_points_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_delete_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_delete_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_delete_points_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "lii_map_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "lii_map_box_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_box_search_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_map_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_download_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "lii_map_pcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "lii_map_intensity_set": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lii_map_intensity_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "lii_map_commit": (C.c_int, [C.c_void_p]),
     "lii_map_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_nearest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_map_nearest_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_map_nearest_xyzi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lii_map_radius_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lii_map_radius_xyzi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_scan_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_upload_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "lii_scan_advance": (C.c_int, [C.c_void_p]),
@@ -219,6 +230,7 @@ _DECLS = {
     "lii_map_removed_set": (C.c_int, [C.c_void_p, C.c_int32]),
     "lii_map_removed_get": (C.c_int, [C.c_void_p, C.POINTER(lii_map_removed_info)]),
     "lii_map_removed_acquire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "lii_map_removed_acquire_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "lii_map_removed_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "lii_publish_set": (C.c_int, [C.c_void_p, C.POINTER(lii_publish_opts)]),
     "lii_publish_now": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -502,6 +514,30 @@ class Registrar:
         xyz = np.ascontiguousarray(xyz, np.float32)
         self._check(self.L.lii_map_build(self.h, _ptr(xyz), len(xyz), xyz.strides[0]))
 
+    @staticmethod
+    def _xyzi_records(pts):
+        """(array, stride, intensity offset) of an _xyzi input: (n, 4) float32 = x, y, z, intensity, or (n, 12) = pcl::PointXYZINormal."""
+        pts = np.ascontiguousarray(pts, np.float32)
+        assert pts.ndim == 2 and pts.shape[1] in (4, 12)
+        return pts, (pts.strides[0] if len(pts) else 4 * pts.shape[1]), (12 if pts.shape[1] == 4 else 32)
+
+    def map_build_xyzi(self, pts, stride_bytes=None, intensity_offset=None):
+        """map_build with an intensity a point (lii_map_build_xyzi): pts (n, 4) = x, y, z, intensity, or (n, 12) = the 48-byte
+        pcl::PointXYZINormal record (intensity at byte 32).  stride_bytes / intensity_offset override what the shape implies."""
+        pts, stride, off = self._xyzi_records(pts)
+        self._check(self.L.lii_map_build_xyzi(self.h, _ptr(pts) if len(pts) else None, len(pts), int(stride if stride_bytes is None else stride_bytes),
+                                              int(off if intensity_offset is None else intensity_offset)))
+
+    def map_intensity_set(self, on: bool):
+        """lii_map_intensity_set: the scan-driven map updates (map_incremental, a registration's own map_update, map_build_from_scan) store
+        each inserted point's intensity from the down-sampled cloud's; off by default."""
+        self._check(self.L.lii_map_intensity_set(self.h, int(bool(on))))
+
+    def map_intensity_get(self) -> bool:
+        on = C.c_int32(0)
+        self._check(self.L.lii_map_intensity_get(self.h, C.byref(on)))
+        return bool(on.value)
+
     def map_build_from_scan(self, state: "State") -> int:
         """The first scan seeds the map (src/laserMapping.cpp:921-929): the current down-sampled cloud, moved to the world frame at
         `state` on the device, becomes the map (lii_map_build_from_scan).  Returns the number of map points (0: five points or
@@ -515,6 +551,15 @@ class Registrar:
         n = C.c_int32(0)
         self._check(self.L.lii_map_add_points(self.h, _ptr(xyz), len(xyz), xyz.strides[0] if len(xyz) else 12,
                                               int(downsample_on), C.byref(n)))
+        return n.value
+
+    def map_add_points_xyzi(self, pts, downsample_on: bool, stride_bytes=None, intensity_offset=None) -> int:
+        """map_add_points with an intensity a point (lii_map_add_points_xyzi; records as for map_build_xyzi): the stored point keeps the
+        intensity of the input point the keep-closest-to-centre rule keeps."""
+        pts, stride, off = self._xyzi_records(pts)
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_add_points_xyzi(self.h, _ptr(pts) if len(pts) else None, len(pts), int(stride if stride_bytes is None else stride_bytes),
+                                                   int(off if intensity_offset is None else intensity_offset), int(downsample_on), C.byref(n)))
         return n.value
 
     def map_delete_boxes(self, boxes6) -> int:
@@ -553,6 +598,15 @@ class Registrar:
         self._check(self.L.lii_map_box_search(self.h, _ptr(b) if len(b) else None, len(b), None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 3), np.float32)
         self._check(self.L.lii_map_box_search(self.h, _ptr(b) if len(b) else None, len(b), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def map_box_search_xyzi(self, boxes6):
+        """map_box_search as (m, 4) float32: x, y, z and the stored intensity."""
+        b = np.ascontiguousarray(boxes6, np.float32).reshape(-1, 6)
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_box_search_xyzi(self.h, _ptr(b) if len(b) else None, len(b), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._check(self.L.lii_map_box_search_xyzi(self.h, _ptr(b) if len(b) else None, len(b), _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
     # ---- the moving local map (lasermap_fov_segment + the box delete upstream never made)
@@ -611,6 +665,18 @@ class Registrar:
             self._check(rc)
         return out[:n.value]
 
+    def map_removed_acquire_xyzi(self, clear=False, strict=True):
+        """map_removed_acquire as (n, 4) float32: x, y, z and the intensity the point was stored with."""
+        n = C.c_int32(0)
+        rc = self.L.lii_map_removed_acquire_xyzi(self.h, None, 0, C.byref(n), 0)
+        if rc != 0 and (strict or rc != -4):
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        rc = self.L.lii_map_removed_acquire_xyzi(self.h, _ptr(out), len(out), C.byref(n), int(bool(clear)))
+        if rc != 0 and (strict or rc != -4):
+            self._check(rc)
+        return out[:n.value]
+
     def map_removed_view(self):
         """(device float4 records as an object with __cuda_array_interface__ - torch.as_tensor(v, device="cuda") -, n); valid until the next
         call that deletes or clears.  n == 0: (None, 0)."""
@@ -636,6 +702,23 @@ class Registrar:
         self._check(self.L.lii_map_download(self.h, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
+    def map_download_xyzi(self):
+        """map_download as (n, 4) float32: x, y, z and the stored intensity (0.0 for points that came without one)."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_download_xyzi(self.h, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._check(self.L.lii_map_download_xyzi(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def map_pcd(self):
+        """lii_map_pcd: the live map as the 32-byte rows pcd_header(n) describes (normals and curvature 0, intensity the stored word):
+        (n, 32) uint8; pcd_header(len(rows)) + rows.tobytes() is the file."""
+        n = C.c_int32(0)
+        self._check(self.L.lii_map_pcd(self.h, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 32), np.uint8)
+        self._check(self.L.lii_map_pcd(self.h, _ptr(out), out.nbytes, C.byref(n)))
+        return out[:n.value]
+
     def map_commit(self):
         self._check(self.L.lii_map_commit(self.h))
 
@@ -652,6 +735,19 @@ class Registrar:
         cnt = np.zeros(n, np.int32)
         self._check(self.L.lii_map_nearest(self.h, _ptr(q) if n else None, n, q.strides[0] if n else 12, k, float(max_dist),
                                            _ptr(pts), _ptr(d2), _ptr(cnt)))
+        return pts, d2, cnt
+
+    def map_nearest_xyzi(self, q, k=5, max_dist=5.0):
+        """map_nearest with 4 floats a row: (pts (n, k, 4) = x, y, z, intensity, d2 (n, k), count (n,))."""
+        q = np.asarray(q, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n, k = len(q), int(k)
+        pts = np.zeros((n, max(k, 0), 4), np.float32)
+        d2 = np.zeros((n, max(k, 0)), np.float32)
+        cnt = np.zeros(n, np.int32)
+        self._check(self.L.lii_map_nearest_xyzi(self.h, _ptr(q) if n else None, n, q.strides[0] if n else 12, k, float(max_dist),
+                                                _ptr(pts), _ptr(d2), _ptr(cnt)))
         return pts, d2, cnt
 
     def dev_alloc(self, nbytes: int) -> int:
@@ -673,6 +769,11 @@ class Registrar:
         (pts_dev / d2_dev may be None).  Enqueued on the handle's stream; synchronize() - or any synchronous call - orders it."""
         self._check(self.L.lii_map_nearest_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), int(k), float(max_dist),
                                                _dev_address(pts_dev), _dev_address(d2_dev), _dev_address(count_dev)))
+
+    def map_nearest_xyzi_dev(self, q_dev, n, k, max_dist, pts_dev, d2_dev, count_dev, stride_bytes=12):
+        """map_nearest_dev with (n, k, 4) float32 rows: x, y, z, intensity."""
+        self._check(self.L.lii_map_nearest_xyzi_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), int(k), float(max_dist),
+                                                    _dev_address(pts_dev), _dev_address(d2_dev), _dev_address(count_dev)))
 
     def map_radius(self, q, max_dist, sorted=False, points=True):
         """The ball query (upstream ikd-Tree's Radius_Search) for the points q (n, >= 3) float: EVERY map point with d2 <= max_dist
@@ -704,6 +805,30 @@ class Registrar:
         self._check(self.L.lii_map_radius_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), float(max_dist),
                                               LII_RADIUS_SORTED if sorted else 0, _dev_address(offsets_dev), _dev_address(pts_dev),
                                               _dev_address(d2_dev), int(capacity), _dev_address(total_dev)))
+
+    def map_radius_xyzi(self, q, max_dist, sorted=False, points=True):
+        """map_radius with 4 floats a row: (offsets, pts (total, 4) = x, y, z, intensity, d2 (total,))."""
+        q = np.asarray(q, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n = len(q)
+        flags = LII_RADIUS_SORTED if sorted else 0
+        qp, stride = (_ptr(q) if n else None), (q.strides[0] if n else 12)
+        offsets = np.zeros(n + 1, np.int64)
+        total = C.c_int64(0)
+        self._check(self.L.lii_map_radius_xyzi(self.h, qp, n, stride, float(max_dist), flags, _ptr(offsets), None, None, 0, C.byref(total)))
+        rows = total.value if points else 0
+        pts = np.zeros((rows, 4), np.float32)
+        d2 = np.zeros(rows, np.float32)
+        if rows:
+            self._check(self.L.lii_map_radius_xyzi(self.h, qp, n, stride, float(max_dist), flags, _ptr(offsets), _ptr(pts), _ptr(d2), rows, C.byref(total)))
+        return offsets, pts, d2
+
+    def map_radius_xyzi_dev(self, q_dev, n, max_dist, offsets_dev, pts_dev, d2_dev, capacity, total_dev, sorted=False, stride_bytes=12):
+        """map_radius_dev with (capacity, 4) float32 rows: x, y, z, intensity."""
+        self._check(self.L.lii_map_radius_xyzi_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), float(max_dist),
+                                                   LII_RADIUS_SORTED if sorted else 0, _dev_address(offsets_dev), _dev_address(pts_dev),
+                                                   _dev_address(d2_dev), int(capacity), _dev_address(total_dev)))
 
     # ------------------------------------------------------------------ scan
     def scan_upload(self, pts):

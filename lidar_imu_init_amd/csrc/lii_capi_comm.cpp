@@ -177,6 +177,7 @@ int lii_comm_init_ex(lii_handle h, int32_t n_ranks, int32_t rank, const uint8_t 
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   if (!h || !id_in || n_ranks < 1 || rank < 0 || rank >= n_ranks || transport < LII_COMM_AUTO || transport > LII_COMM_MAILBOX_HOST)
     return fail(h, LII_ERR_INVALID, "lii_comm_init: bad arguments");
+  if (h->map_intensity) return fail(h, LII_ERR_STATE, "lii_comm_init: lii_map_intensity_set is on - single rank for now");
   const int rc = comm_init(h, n_ranks, rank, id_in, transport);
   partition_refresh(h);  // (n_ranks / rank as the set-up left them: 1 / 0 after a failure)
   return rc;

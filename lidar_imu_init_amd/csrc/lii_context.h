@@ -82,6 +82,8 @@ struct lii_context {
   long long win_kept = 0, win_dropped = 0;  // LII_DIAG: in-place updates the window was kept current through / times it had to be dropped
   bool win_keep = true;          // LII_WINDOW_KEEP=0: the first in-place update drops the window (round 6's first form) instead of keeping it current
   DevBuf<unsigned long long> d_block_key;  // packed block coordinates by block id (WinKeep::key_of_id), cells_cap_blocks entries
+  bool map_has_w = false;       // the map may hold intensities (an _xyzi input since the last lii_map_reset / lii_map_build, or map_intensity): the folds and the insert launches carry the points' fourth word
+  bool map_intensity = false;   // lii_map_intensity_set: the scan-driven map updates take each inserted point's intensity from inten.d_body
   bool map_tight = false;       // LII_TEST=map_tight: no spare room is provisioned (tests: forces the recovery path)
   long long map_recoveries = 0;
   DevBuf<float4> d_ins;         // fold output (M)

@@ -38,7 +38,7 @@ struct CvArgH { double omega[3], vel[3], endR[9]; };
 // map index (lii_mapindex.hip)
 void launch_map_keys(const float4* pts, int n, float inv_cs, unsigned long long* keys, unsigned int* idx, hipStream_t s);
 void launch_map_gather(const float4* src, const unsigned int* idx, int n, float4* dst, hipStream_t s);
-void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s);  // pointBodyToWorld over a cloud: dst[i] = (world xyz, 0)
+void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s, const float* inten = nullptr);  // pointBodyToWorld over a cloud: dst[i] = (world xyz, inten ? inten[i] : 0)
 void launch_block_flags(const unsigned long long* keys, int n, unsigned int* flags, hipStream_t s);
 void launch_table_clear(BlockEntry* blocks, unsigned int cap, hipStream_t s);
 void launch_win_bbox(const BlockEntry* blocks, unsigned int cap, unsigned int* box, hipStream_t s);
@@ -50,7 +50,7 @@ void launch_cells_fill(const unsigned long long* keys, const unsigned int* ranks
 // that is <= max_dist; r_max: rings of cells that cover the ball (ceil(sqrt(max_dist) / cell) + 1).  Row i * k + j of pts_out (3 floats)
 // / d2_out: neighbour j of query i, zeros from count_out[i] on; pts_out / d2_out may be nullptr.
 void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, int k,
-                        float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s);
+                        float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s, int row_floats = 3);
 // ... and the ball query (lii_map_radius): every point with d2 <= max_d2, in two walks of the same cells.  _count: count_out[i] = points in
 // the ball of query i (64 bits, so that the scan below turns them into offsets in place).  _fill: the points of query i into rows
 // offsets[i] - base .. offsets[i + 1] - base - 1, only rows < capacity; per row 3 floats of pts_out, d2_out, and - for LII_RADIUS_SORTED -
@@ -60,9 +60,11 @@ void launch_map_radius_count(const GridView& g, unsigned int n_entries, unsigned
                              int r_max, long long* count_out, hipStream_t s);
 void launch_map_radius_fill(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2,
                             int r_max, const long long* offsets, long long base, long long capacity, float* pts_out, float* d2_out,
-                            unsigned long long* key_out, unsigned int* slot_out, hipStream_t s);
+                            unsigned long long* key_out, unsigned int* slot_out, hipStream_t s, int row_floats = 3);
 void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const unsigned long long* keys, const unsigned int* slots, const long long* total,
-                              long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s);
+                              long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s, int row_floats = 3);
+// row_floats (the three launches above): 3 - x, y, z a row of pts_out - or 4: the stored fourth word, the point's intensity, behind them
+// (lii_map_nearest_xyzi / lii_map_radius_xyzi; instantiations of their own)
 // (lii_sort.hip) counts -> offsets in place: io[i] = io[0] + ... + io[i - 1] over n words; and the sort of the sorted form: bits [0, end_bit)
 // of 64-bit keys with 32-bit values, stable.  *_temp_bytes: the temporary storage either needs for that size.
 size_t scan_i64_temp_bytes(size_t n);
@@ -270,12 +272,13 @@ void launch_map_decide_compact(const RegistrationBuffers& rb, const PoseArg& ps,
                                const IekfCtrl* guard = nullptr, int seq = 0, int test_late = 0,
                                // (hkey != nullptr: the hash insert of the fold that follows rides in this launch - table sized by bound_add)
                                unsigned long long* hkey = nullptr, unsigned long long* hbest = nullptr, unsigned int* slot_of = nullptr, float ds = 0.f,
-                               unsigned int* ins_flag = nullptr, int* events = nullptr);  // blk_counts: one word per 256 points; epoch: the number of this run (never 0); guard: see k_map_decide
+                               unsigned int* ins_flag = nullptr, int* events = nullptr,
+                               const float* inten = nullptr /* != nullptr: the lists' records take their fourth word from inten[i] (k_map_decide<true>) */);  // blk_counts: one word per 256 points; epoch: the number of this run (never 0); guard: see k_map_decide
 void launch_map_publish(const int* ctr, int n_words, int* host, int seq_at, int seq, hipStream_t s);
 void launch_add_keys(const float4* pts, int n, const int* n_dev, float ds, unsigned long long* keys, unsigned int* idx, int* events, hipStream_t s);
 void launch_add_fold(const float4* add_pts, const unsigned long long* keys, const unsigned int* idx, int n, float ds, const GridView& g,
                      unsigned char* tomb, float4* ins_pts, unsigned int* ins_flag, unsigned int* events, unsigned int* tp, unsigned int* work,
-                     int* ctr, unsigned int work_cap, hipStream_t s);
+                     int* ctr, unsigned int work_cap, hipStream_t s, bool carry_w = false);  // carry_w: ins_pts keeps the batch points' fourth word
 size_t add_hash_slots(int max_n);
 // the cells of the inserts found / created inside the fold launch (k_add_fold8<true, true>) instead of by launch_ins_cells behind it
 struct FoldCellsH {
@@ -285,11 +288,12 @@ struct FoldCellsH {
 void launch_add_fold_hashed(const float4* add_pts, int n, const int* n_dev, float ds, const GridView& g, unsigned long long* hkey,
                             unsigned long long* hbest, unsigned int* slot_of, unsigned char* tomb, float4* ins_pts, unsigned int* ins_flag,
                             unsigned int* events, unsigned int* tp, unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s,
-                            bool inserted = false, const FoldCellsH* cells = nullptr);
+                            bool inserted = false, const FoldCellsH* cells = nullptr, bool carry_w = false);  // carry_w: the leader keeps its fourth word
 // in-place map update (lii_map.hip)
 void launch_ins_cells(const float4* list, const unsigned int* flags, int n, const int* n_dev, const float4* list2, int n2, const int* n2_dev, unsigned int* ins_e2,
                       BlockEntry* blocks, unsigned int mask, float inv_cs, unsigned int tables_cap, unsigned int* ins_e, unsigned int* tp,
-                      unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s);
+                      unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s,
+                      bool carry_w = false);  // carry_w: a parked insert keeps its fourth word
 // the history of what box deletes remove (lii_map_removed_*): the squeeze of a box delete appends the points it drops.  `reserved` counts the
 // records asked for since the last clear - it runs past `cap` when the buffer is full: min(reserved, cap) records are held, the rest was not stored.
 struct RemovedSink {
@@ -374,6 +378,8 @@ constexpr int kPcdChunkRows = 65536;  // lii_publish_saved_pcd's staging area (t
 void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s);
 // the save buffer as binary PCD rows (8 floats: x y z 0 0 0 intensity 0): rows [first, first + n) -> out[0, n); inten == nullptr: 0.0f
 void launch_pcd_rows(const float4* save, const float* inten, int first, int n, uint4* out, hipStream_t s);
+// ... and map points as such rows (lii_map_pcd): the intensity is the point's own fourth word
+void launch_pcd_rows_w(const float4* pts, int first, int n, uint4* out, hipStream_t s);
 
 // rocPRIM wrappers (lii_sort.hip)
 size_t sort_temp_bytes(int max_n);

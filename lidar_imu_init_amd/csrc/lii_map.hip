@@ -221,11 +221,14 @@ __device__ __forceinline__ unsigned int map_decide_count(unsigned int fa, unsign
   *ma_out = ma; *mn_out = mn;
   return ((s_a[0] + s_a[1] + s_a[2] + s_a[3]) << 16) | (s_n[0] + s_n[1] + s_n[2] + s_n[3]);
 }
+// INT (lii_map_intensity_set, a down-sampled cloud that carries intensities): the point that goes into either list takes its fourth word
+// from inten[i] - one more load per inserted point; world_out keeps .w = 0 (other readers use it).  INT = false: the launch as it was.
+template <bool INT>
 __global__ __launch_bounds__(256) void k_map_decide(RegistrationBuffers rb, PoseArg ps_val, double fsd, int have_search,
                                                     unsigned long long* __restrict__ blk_counts, unsigned int epoch, float4* __restrict__ world_out,
                                                     float4* __restrict__ dst_add, float4* __restrict__ dst_nodown, int* __restrict__ counts, int bound_a,
                                                     int bound_n, const IekfCtrl* __restrict__ guard, int seq, int test_late, AddHash tb, float ds,
-                                                    unsigned int* __restrict__ ins_flag, int* __restrict__ events) {
+                                                    unsigned int* __restrict__ ins_flag, int* __restrict__ events, const float* __restrict__ inten) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const PoseArg ps = load_pose(guard != nullptr, reinterpret_cast<const PoseArg*>(guard), ps_val);  // (IekfCtrl::st leads the block)
   const bool go = !guard || (guard->stop == 1 && guard->singular == 0 && guard->seq == seq);  // uniform
@@ -269,8 +272,10 @@ __global__ __launch_bounds__(256) void k_map_decide(RegistrationBuffers rb, Pose
   for (int k = 0; k < w; k++) { base_a += s_a[k]; base_n += s_n[k]; }
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   const unsigned int at_a = base_a + (unsigned int)__popcll(ma & lanes_below);
-  if (fa) dst_add[at_a] = wp;
-  if (fn) dst_nodown[base_n + (unsigned int)__popcll(mn & lanes_below)] = wp;
+  float4 lp = wp;  // the list's record
+  if (INT && (fa | fn)) lp.w = inten[i];
+  if (fa) dst_add[at_a] = lp;
+  if (fn) dst_nodown[base_n + (unsigned int)__popcll(mn & lanes_below)] = lp;
   // lii_scan_job::map_update (round 6): the fold's hash insert rides here - every point of the add list knows its place in the list, which
   // is all k_addh_insert took from a launch of its own.  Only places below the bound the fold is enqueued for are inserted (its table is
   // sized by the bound); a list that outgrows the bound leaves a table the repeated update clears first (map_join).
@@ -324,9 +329,11 @@ __global__ void k_addh_insert(const float4* __restrict__ pts, int n, const int* 
 
 // An insert that found no room (block tables full, no slack left and no tail to move the cell to) is kept for the host: the
 // next read of the counters rebuilds the index with more room and inserts these points again.
+// INT: all four words are kept - the fourth is the point's intensity (a handle whose map was given intensities); else 0.f, as ever.
+template <bool INT>
 __device__ __forceinline__ void drop_point(float4* __restrict__ dropped, unsigned int drop_cap, int* __restrict__ ctr, const float4 p) {
   const unsigned int at = (unsigned int)atomicAdd(&ctr[kMapCtrDropped], 1);
-  if (at < drop_cap) dropped[at] = make_float4(p.x, p.y, p.z, 0.f);
+  if (at < drop_cap) dropped[at] = INT ? p : make_float4(p.x, p.y, p.z, 0.f);
 }
 
 // One insert finds its cell entry - creating the 8x8x8 block when the map has never seen it -, bumps the cell's pending count and puts the
@@ -344,6 +351,7 @@ struct InsCells {
   unsigned int drop_cap;
   unsigned long long* key_of_id;
 };
+template <bool INT>
 __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __restrict__ ins_e_out, const InsCells& a) {
   BlockEntry* blocks = a.blocks;
   const unsigned int mask = a.mask, tables_cap = a.tables_cap;
@@ -402,7 +410,7 @@ __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __res
   if (id < 0) {  // no table left for a new block: the point waits in the dropped list for the host's rebuild (nothing is lost)
     *ins_e_out = 0xFFFFFFFFu;
     ctr[kMapCtrOverflow] = 1;
-    drop_point(a.dropped, a.drop_cap, ctr, p);
+    drop_point<INT>(a.dropped, a.drop_cap, ctr, p);
     return;
   }
   const unsigned int e = (unsigned int)id * kBlockCells + local_cell(ix, iy, iz);
@@ -427,6 +435,9 @@ __device__ __forceinline__ void ins_cell_one(const float4 p, unsigned int* __res
 // finds / creates that point's cell at once (fc.ins_e[i]; every other position of the list gets 0xFFFFFFFF), and the workgroups behind the
 // fold's own (blockIdx >= fc.fold_blocks) do the same for the second insert list, which does not pass through the fold.  Cell lookups of
 // such a launch run beside block creations: cell_range<FRESH>.
+// INT (the sorted form; lii_map_add_points_xyzi): the fourth word of the batch point that stays - its intensity, Add_Points keeps whole
+// PointType values (ikd_Tree.cpp:381-456) - goes into ins_pts with it: a fourth running value and a fourth shuffle in the replay.  INT = false
+// is the fold as it was and writes 0.f.
 struct FoldCells {
   InsCells a;
   unsigned int* ins_e;     // per position of the folded list
@@ -437,7 +448,7 @@ struct FoldCells {
   unsigned int* ins_e2;
   unsigned int fold_blocks;
 };
-template <bool HASHED, bool CELLS>
+template <bool HASHED, bool CELLS, bool INT>
 __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ add_pts, const unsigned long long* __restrict__ keys,
                                                    const unsigned int* __restrict__ idx, AddHash tb, int n, float ds, GridView g,
                                                    unsigned char* __restrict__ tomb, float4* __restrict__ ins_pts,
@@ -446,7 +457,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
                                                    unsigned int work_cap, FoldCells fc) {
   if (CELLS && blockIdx.x >= fc.fold_blocks) {  // (uniform per workgroup) the second insert list
     const int j = (int)((blockIdx.x - fc.fold_blocks) * blockDim.x + threadIdx.x);
-    if (j < fc.n2 && !(fc.n2_dev && j >= *fc.n2_dev)) ins_cell_one(fc.list2[j], &fc.ins_e2[j], fc.a);
+    if (j < fc.n2 && !(fc.n2_dev && j >= *fc.n2_dev)) ins_cell_one<INT>(fc.list2[j], &fc.ins_e2[j], fc.a);
     return;
   }
   const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 3;
@@ -554,7 +565,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
     cur_new = !old_wins;
     cur_old = old_wins ? best : -1;
     if (c == 0) {
-      if (cur_new) { ins_pts[i] = make_float4(p0.x, p0.y, p0.z, 0.f); ins_flag[i] = 1; }
+      if (cur_new) { ins_pts[i] = INT ? p0 : make_float4(p0.x, p0.y, p0.z, 0.f); ins_flag[i] = 1; }  // (INT: the leader keeps p0.w)
       tb.key[slot] = kInvalidKey;  // the slot is free again for the next batch
       tb.best[slot] = ~0ull;
     }
@@ -564,7 +575,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
     const int m8 = __popc(gm);
     float4 qb = make_float4(0.f, 0.f, 0.f, 0.f);
     if (n0 > 0 && best >= 0) qb = g.pts[best];  // the existing point a batch point may lose against
-    float cx_ = 0, cy_ = 0, cz_ = 0, cd = 0;
+    float cx_ = 0, cy_ = 0, cz_ = 0, cw_ = 0, cd = 0;
     unsigned int n_events = 0;
     auto replay = [&](const float4 p) {
       const float dp = dist2_ref(p.x, p.y, p.z, mid[0], mid[1], mid[2]);
@@ -578,6 +589,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
           cur_new = !old_wins;
           cur_old = old_wins ? best : -1;
           cx_ = rx; cy_ = ry; cz_ = rz;
+          if (INT) cw_ = p.w;  // (read only where a batch point stays: a stored point that wins keeps its own slot and word)
           cd = old_wins ? bestd : dp;
         }
       } else {
@@ -585,13 +597,13 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
         const float rx = cur_wins ? cx_ : p.x, ry = cur_wins ? cy_ : p.y, rz = cur_wins ? cz_ : p.z;
         if (d_same_point(p.x, p.y, p.z, rx, ry, rz)) {
           n_events++;
-          if (!cur_wins) { cur_new = true; cur_old = -1; cx_ = p.x; cy_ = p.y; cz_ = p.z; cd = dp; }
+          if (!cur_wins) { cur_new = true; cur_old = -1; cx_ = p.x; cy_ = p.y; cz_ = p.z; cd = dp; if (INT) cw_ = p.w; }
         }
       }
     };
     for (int t = 0; t < m8; t++) {
       float4 p;
-      p.x = __shfl(mp.x, lead + t); p.y = __shfl(mp.y, lead + t); p.z = __shfl(mp.z, lead + t); p.w = 0.f;
+      p.x = __shfl(mp.x, lead + t); p.y = __shfl(mp.y, lead + t); p.z = __shfl(mp.z, lead + t); p.w = INT ? __shfl(mp.w, lead + t) : 0.f;
       replay(p);
     }
     if (m8 == 8)
@@ -599,7 +611,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
     wave_atomic_add_few(events, c == 0 && ev, n_events);  // (the groups of this wavefront that are still here: all leaders)
     if (c == 0 && ev) {
       if (cur_new) {
-        ins_pts[i] = make_float4(cx_, cy_, cz_, 0.f);
+        ins_pts[i] = make_float4(cx_, cy_, cz_, INT ? cw_ : 0.f);
         ins_flag[i] = 1;
       }
     }
@@ -663,7 +675,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
         touch_cell(tp, work, ctr, work_cap, (unsigned int)e_lane);
         atomicAdd(&tp[e_lane], 1u);
       } else {
-        ins_cell_one(make_float4(p0.x, p0.y, p0.z, 0.f), &fc.ins_e[i], fc.a);
+        ins_cell_one<INT>(INT ? p0 : make_float4(p0.x, p0.y, p0.z, 0.f), &fc.ins_e[i], fc.a);
       }
     }
   }
@@ -688,6 +700,7 @@ __global__ __launch_bounds__(256) void k_add_fold8(const float4* __restrict__ ad
 
 // flags == nullptr: every point of the list is an insert.  n_dev != nullptr: the list holds *n_dev points (n is the launch bound).
 // A second list (list2, n2 points, all of them inserts, entries to ins_e2) rides in the same launch: lanes [n, n + n2).
+template <bool INT>
 __global__ void k_ins_cells(const float4* __restrict__ list, const unsigned int* __restrict__ flags, int n, const int* __restrict__ n_dev,
                             const float4* __restrict__ list2, int n2, const int* __restrict__ n2_dev, unsigned int* __restrict__ ins_e2,
                             unsigned int* __restrict__ ins_e, InsCells a) {
@@ -700,7 +713,7 @@ __global__ void k_ins_cells(const float4* __restrict__ list, const unsigned int*
     return;
   }
   if (flags && !flags[i]) { ins_e[i] = 0xFFFFFFFFu; return; }
-  ins_cell_one(list[i], &ins_e[i], a);
+  ins_cell_one<INT>(list[i], &ins_e[i], a);
 }
 
 // the tombstones of one listed cell, counted in front of its squeeze (the collecting form: what the wavefront reserves in the history buffer)
@@ -834,7 +847,7 @@ __global__ void k_ins_write(const float4* __restrict__ list, const unsigned int*
       const unsigned int slot = atomicAdd(reinterpret_cast<unsigned int*>(&cells[e]) + 1, 1u);
       const float4 p = list[i];
       if (slot < cell_cap[e]) {
-        pts[slot] = make_float4(p.x, p.y, p.z, 0.f);
+        pts[slot] = p;  // (all four words: the fourth is the point's intensity)
         added = 1;
         if (wk.win) {  // (uniform) the window counts the insert as the cell table did (k_cell_apply left the two entries equal)
           const long long wi = win_index_of_entry(wk, e);
@@ -843,7 +856,7 @@ __global__ void k_ins_write(const float4* __restrict__ list, const unsigned int*
       } else {
         atomicSub(reinterpret_cast<unsigned int*>(&cells[e]) + 1, 1u);
         __hip_atomic_store(&ctr[kMapCtrOverflow], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        drop_point(dropped, drop_cap, ctr, p);
+        drop_point<true>(dropped, drop_cap, ctr, p);  // (the whole point, as the slot above would have got it)
       }
     }
   }
@@ -1266,14 +1279,17 @@ void launch_box_gather(const float4* pts, const uint2* cells, const unsigned lon
 }
 void launch_ins_cells(const float4* list, const unsigned int* flags, int n, const int* n_dev, const float4* list2, int n2, const int* n2_dev, unsigned int* ins_e2,
                       BlockEntry* blocks, unsigned int mask, float inv_cs, unsigned int tables_cap, unsigned int* ins_e, unsigned int* tp,
-                      unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s) {
+                      unsigned int* work, int* ctr, unsigned int work_cap, float4* dropped, unsigned int drop_cap, unsigned long long* key_of_id, hipStream_t s,
+                      bool carry_w) {
   if (n < 0) n = 0;
   if (n2 < 0) n2 = 0;
   InsCells a;
   a.blocks = blocks; a.mask = mask; a.inv_cs = inv_cs; a.tables_cap = tables_cap; a.tp = tp; a.work = work; a.ctr = ctr; a.work_cap = work_cap;
   a.dropped = dropped; a.drop_cap = drop_cap; a.key_of_id = key_of_id;
-  if (n + n2 > 0)
-    hipLaunchKernelGGL(k_ins_cells, dim3(nblk(n + n2, 256)), dim3(256), 0, s, list, flags, n, n_dev, list2, n2, n2_dev, ins_e2, ins_e, a);
+  if (n + n2 <= 0) return;
+  // carry_w: an insert that is parked for the host's rebuild keeps its fourth word (an instantiation of its own)
+  if (carry_w) hipLaunchKernelGGL(k_ins_cells<true>, dim3(nblk(n + n2, 256)), dim3(256), 0, s, list, flags, n, n_dev, list2, n2, n2_dev, ins_e2, ins_e, a);
+  else hipLaunchKernelGGL(k_ins_cells<false>, dim3(nblk(n + n2, 256)), dim3(256), 0, s, list, flags, n, n_dev, list2, n2, n2_dev, ins_e2, ins_e, a);
 }
 void launch_cell_apply(const unsigned int* work, uint2* cells, unsigned int* cell_cap, float4* pts, unsigned char* tomb, unsigned int* tp, int* ctr,
                        unsigned int pts_cap, int launch_bound, const WinKeep& wk, hipStream_t s, const RemovedSink* removed) {
@@ -1349,33 +1365,43 @@ size_t add_hash_slots(int max_n) {
 void launch_map_decide_compact(const RegistrationBuffers& rb, const PoseArg& ps, double fsd, int have_search, unsigned long long* blk_counts, unsigned int epoch,
                                float4* world, float4* dst_add, float4* dst_nodown, int* counts, int bound_add, int bound_nodown, hipStream_t s,
                                const IekfCtrl* guard, int seq, int test_late, unsigned long long* hkey, unsigned long long* hbest, unsigned int* slot_of,
-                               float ds, unsigned int* ins_flag, int* events) {
+                               float ds, unsigned int* ins_flag, int* events, const float* inten) {
   if (rb.n <= 0) return;
   AddHash tb;  // hkey != nullptr: the hash insert of the fold behind this launch rides in it (table sized by bound_add, as launch_add_fold_hashed sizes it)
   tb.key = hkey; tb.best = hbest; tb.slot_of = slot_of;
   tb.mask = hkey ? (unsigned int)(add_hash_slots(bound_add) - 1) : 0u;
-  hipLaunchKernelGGL(k_map_decide, dim3(nblk(rb.n, 256)), dim3(256), 0, s, rb, ps, fsd, have_search, blk_counts, epoch, world, dst_add, dst_nodown, counts,
-                     bound_add, bound_nodown, guard, seq, test_late, tb, ds, ins_flag, events);
+  if (inten)
+    hipLaunchKernelGGL(k_map_decide<true>, dim3(nblk(rb.n, 256)), dim3(256), 0, s, rb, ps, fsd, have_search, blk_counts, epoch, world, dst_add, dst_nodown, counts,
+                       bound_add, bound_nodown, guard, seq, test_late, tb, ds, ins_flag, events, inten);
+  else
+    hipLaunchKernelGGL(k_map_decide<false>, dim3(nblk(rb.n, 256)), dim3(256), 0, s, rb, ps, fsd, have_search, blk_counts, epoch, world, dst_add, dst_nodown, counts,
+                       bound_add, bound_nodown, guard, seq, test_late, tb, ds, ins_flag, events, inten);
 }
 void launch_add_keys(const float4* pts, int n, const int* n_dev, float ds, unsigned long long* keys, unsigned int* idx, int* events, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_add_keys, dim3(nblk(n, 256)), dim3(256), 0, s, pts, n, n_dev, ds, keys, idx, events);
 }
 void launch_add_fold(const float4* add_pts, const unsigned long long* keys, const unsigned int* idx, int n, float ds, const GridView& g,
                      unsigned char* tomb, float4* ins_pts, unsigned int* ins_flag, unsigned int* events, unsigned int* tp, unsigned int* work,
-                     int* ctr, unsigned int work_cap, hipStream_t s) {
+                     int* ctr, unsigned int work_cap, hipStream_t s, bool carry_w) {
   AddHash none;
   none.key = nullptr; none.best = nullptr; none.slot_of = nullptr; none.mask = 0;
   FoldCells fc;
   std::memset(&fc, 0, sizeof(fc));
-  if (n > 0) hipLaunchKernelGGL((k_add_fold8<false, false>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, keys, idx, none, n, ds, g, tomb, ins_pts, ins_flag,
-                            events, tp, work, ctr, work_cap, fc);
+  if (n <= 0) return;
+  // carry_w (lii_map_add_points_xyzi): the batch points' fourth word travels through the replay - an instantiation of its own
+  if (carry_w)
+    hipLaunchKernelGGL((k_add_fold8<false, false, true>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, keys, idx, none, n, ds, g, tomb, ins_pts, ins_flag,
+                       events, tp, work, ctr, work_cap, fc);
+  else
+    hipLaunchKernelGGL((k_add_fold8<false, false, false>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, keys, idx, none, n, ds, g, tomb, ins_pts, ins_flag,
+                       events, tp, work, ctr, work_cap, fc);
 }
 // The hash-grouped form: n is a launch bound when n_dev != nullptr.  key / best: add_hash_slots(max batch) words each, all ones
 // between calls (the fold leaves them so); slot_of: one word per batch point.
 void launch_add_fold_hashed(const float4* add_pts, int n, const int* n_dev, float ds, const GridView& g, unsigned long long* hkey,
                             unsigned long long* hbest, unsigned int* slot_of, unsigned char* tomb, float4* ins_pts, unsigned int* ins_flag,
                             unsigned int* events, unsigned int* tp, unsigned int* work, int* ctr, unsigned int work_cap, hipStream_t s,
-                            bool inserted, const FoldCellsH* cells) {
+                            bool inserted, const FoldCellsH* cells, bool carry_w) {
   if (n <= 0) return;
   AddHash tb;
   tb.key = hkey; tb.best = hbest; tb.slot_of = slot_of;
@@ -1386,8 +1412,12 @@ void launch_add_fold_hashed(const float4* add_pts, int n, const int* n_dev, floa
   std::memset(&fc, 0, sizeof(fc));
   fc.n_dev = n_dev;
   if (!cells) {
-    hipLaunchKernelGGL((k_add_fold8<true, false>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g, tomb, ins_pts, ins_flag,
-                       events, tp, work, ctr, work_cap, fc);
+    if (carry_w)
+      hipLaunchKernelGGL((k_add_fold8<true, false, true>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g, tomb, ins_pts, ins_flag,
+                         events, tp, work, ctr, work_cap, fc);
+    else
+      hipLaunchKernelGGL((k_add_fold8<true, false, false>), dim3(nblk(n * 8, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g, tomb, ins_pts, ins_flag,
+                         events, tp, work, ctr, work_cap, fc);
     return;
   }
   // cells: the inserts' cells ride in the fold (and the second list's in workgroups behind it)
@@ -1397,8 +1427,12 @@ void launch_add_fold_hashed(const float4* add_pts, int n, const int* n_dev, floa
   fc.ins_e = cells->ins_e;
   fc.list2 = cells->list2; fc.n2 = cells->n2 > 0 ? cells->n2 : 0; fc.n2_dev = cells->n2_dev; fc.ins_e2 = cells->ins_e2;
   fc.fold_blocks = (unsigned int)nblk(n * 8, 256);
-  hipLaunchKernelGGL((k_add_fold8<true, true>), dim3(fc.fold_blocks + (unsigned int)nblk(fc.n2, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g,
-                     tomb, ins_pts, ins_flag, events, tp, work, ctr, work_cap, fc);
+  if (carry_w)
+    hipLaunchKernelGGL((k_add_fold8<true, true, true>), dim3(fc.fold_blocks + (unsigned int)nblk(fc.n2, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g,
+                       tomb, ins_pts, ins_flag, events, tp, work, ctr, work_cap, fc);
+  else
+    hipLaunchKernelGGL((k_add_fold8<true, true, false>), dim3(fc.fold_blocks + (unsigned int)nblk(fc.n2, 256)), dim3(256), 0, s, add_pts, nullptr, nullptr, tb, n, ds, g,
+                       tomb, ins_pts, ins_flag, events, tp, work, ctr, work_cap, fc);
 }
 
 }  // namespace lii

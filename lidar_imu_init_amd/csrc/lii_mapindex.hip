@@ -88,6 +88,14 @@ __global__ __launch_bounds__(256) void k_body_to_map(const float4* __restrict__ 
   body_to_world(ps, body[i], wx, wy, wz);
   dst[i] = make_float4(wx, wy, wz, 0.f);
 }
+// ... with the cloud's intensities as the map points' fourth word (lii_map_intensity_set; pointBodyToWorld copies it, src/laserMapping.cpp:219)
+__global__ __launch_bounds__(256) void k_body_to_map_w(const float4* __restrict__ body, const float* __restrict__ inten, int n, PoseArg ps, float4* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float wx, wy, wz;
+  body_to_world(ps, body[i], wx, wy, wz);
+  dst[i] = make_float4(wx, wy, wz, inten[i]);
+}
 
 // ---- dense cell window (GridView::win) ---------------------------------------------------------------------------------------------
 // box[0..2] = min, box[3..5] = max of the BIASED block coordinates over the occupied slots of the block table
@@ -122,7 +130,11 @@ static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 void launch_map_keys(const float4* pts, int n, float inv_cs, unsigned long long* keys, unsigned int* idx, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_map_keys, dim3(nblk(n, 256)), dim3(256), 0, s, pts, n, inv_cs, keys, idx);
 }
-void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s) {
+void launch_body_to_map(const float4* body, int n, const PoseArg& ps, float4* dst, hipStream_t s, const float* inten) {
+  if (n > 0 && inten) {
+    hipLaunchKernelGGL(k_body_to_map_w, dim3((n + 255) / 256), dim3(256), 0, s, body, inten, n, ps, dst);
+    return;
+  }
   if (n <= 0) return;
   hipLaunchKernelGGL(k_body_to_map, dim3(nblk(n, 256)), dim3(256), 0, s, body, n, ps, dst);
 }

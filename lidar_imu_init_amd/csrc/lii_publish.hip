@@ -173,6 +173,15 @@ __global__ __launch_bounds__(256) void k_pcd_rows(const float4* __restrict__ sav
   }
 }
 
+// ... and map points as the same rows (lii_map_pcd): the intensity is the point's own fourth word
+__global__ __launch_bounds__(256) void k_pcd_rows_w(const float4* __restrict__ pts, int first, int n, uint4* __restrict__ out) {
+  for (int i = (int)(blockIdx.x * 256 + threadIdx.x); i < n; i += (int)(gridDim.x * 256)) {
+    const float4 p = pts[(size_t)first + i];
+    out[2 * (size_t)i] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), 0u);
+    out[2 * (size_t)i + 1] = make_uint4(0u, 0u, __float_as_uint(p.w), 0u);
+  }
+}
+
 void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& ps, hipStream_t s) {
   const int blocks = a.dense_blocks + down_blocks;
   if (blocks <= 0) return;
@@ -187,6 +196,10 @@ void launch_publish_world(const PublishArgs& a, int down_blocks, const PoseArg& 
 void launch_pcd_rows(const float4* save, const float* inten, int first, int n, uint4* out, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_pcd_rows, dim3((unsigned int)std::min((n + 255) / 256, 1024)), dim3(256), 0, s, save, inten, first, n, out);
+}
+void launch_pcd_rows_w(const float4* pts, int first, int n, uint4* out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_pcd_rows_w, dim3((unsigned int)std::min((n + 255) / 256, 1024)), dim3(256), 0, s, pts, first, n, out);
 }
 
 }  // namespace lii

@@ -77,6 +77,8 @@ __device__ __forceinline__ int query_cell(float q, float inv_cs) {
   return (int)fminf(fmaxf(floorf(q * inv_cs), -lim), lim);
 }
 
+// W: floats a row of pts_out - 3, or 4 with the stored fourth word (the point's intensity) behind x, y, z; one more load per row written
+template <int W>
 __global__ __launch_bounds__(kBlock) void k_map_nearest(GridView g, unsigned int n_entries, unsigned int pts_cap, const char* __restrict__ queries,
                                                         int n, int stride_bytes, int k, float max_d2, int r_max, float* __restrict__ pts_out,
                                                         float* __restrict__ d2_out, int* __restrict__ count_out) {
@@ -169,13 +171,17 @@ __global__ __launch_bounds__(kBlock) void k_map_nearest(GridView g, unsigned int
   const int count = __popcll(__ballot(lane < k && my_i != kFree));
   if (lane == 0) count_out[qi] = count;
   if (lane < k) {
-    float ox = 0.f, oy = 0.f, oz = 0.f, od = 0.f;
+    float ox = 0.f, oy = 0.f, oz = 0.f, ow = 0.f, od = 0.f;
     if (lane < count) {
       const F3 m = load_xyz(g.pts, my_i);
       ox = m.x; oy = m.y; oz = m.z; od = my_d;
+      if (W == 4) ow = g.pts[my_i].w;
     }
     const size_t row = (size_t)qi * (size_t)k + (size_t)lane;
-    if (pts_out) { pts_out[3 * row] = ox; pts_out[3 * row + 1] = oy; pts_out[3 * row + 2] = oz; }
+    if (pts_out) {
+      pts_out[W * row] = ox; pts_out[W * row + 1] = oy; pts_out[W * row + 2] = oz;
+      if (W == 4) pts_out[W * row + 3] = ow;
+    }
     if (d2_out) d2_out[row] = od;
   }
 }
@@ -183,11 +189,15 @@ __global__ __launch_bounds__(kBlock) void k_map_nearest(GridView g, unsigned int
 }  // namespace
 
 void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, int k,
-                        float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s) {
+                        float max_d2, int r_max, float* pts_out, float* d2_out, int* count_out, hipStream_t s, int row_floats) {
   if (n <= 0) return;
   const unsigned int blocks = (unsigned int)(((long long)n + kQueryWaves - 1) / kQueryWaves);
-  hipLaunchKernelGGL(k_map_nearest, dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes, k,
-                     max_d2, r_max, pts_out, d2_out, count_out);
+  if (row_floats == 4)
+    hipLaunchKernelGGL(k_map_nearest<4>, dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes, k,
+                       max_d2, r_max, pts_out, d2_out, count_out);
+  else
+    hipLaunchKernelGGL(k_map_nearest<3>, dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes, k,
+                       max_d2, r_max, pts_out, d2_out, count_out);
 }
 
 // ------------------------------------------------------------------------------------------------ the ball query
@@ -203,7 +213,7 @@ void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int 
 // count pass did (it cannot: both launches sit behind every map update on the stream) stores none of them - and by `capacity` rows.
 namespace {
 
-template <bool kFill>
+template <bool kFill, int W>
 __global__ __launch_bounds__(kBlock) void k_map_radius(GridView g, unsigned int n_entries, unsigned int pts_cap, const char* __restrict__ queries, int n,
                                                        int stride_bytes, float max_d2, int r_max, long long* __restrict__ count_out,
                                                        const long long* __restrict__ offsets, long long base, long long capacity,
@@ -283,7 +293,10 @@ __global__ __launch_bounds__(kBlock) void k_map_radius(GridView g, unsigned int 
           const unsigned int at = accepted + (unsigned int)__popcll(hits & below);
           const long long row = seg_first + (long long)at;
           if (in_ball && at < seg_len && row < capacity) {
-            if (pts_out) { pts_out[3 * row] = mx; pts_out[3 * row + 1] = my; pts_out[3 * row + 2] = mz; }
+            if (pts_out) {
+              pts_out[W * row] = mx; pts_out[W * row + 1] = my; pts_out[W * row + 2] = mz;
+              if (W == 4) pts_out[W * row + 3] = g.pts[slot].w;
+            }
             if (d2_out) d2_out[row] = d;
             if (key_out) key_out[row] = ((unsigned long long)qi << 32) | (unsigned long long)__float_as_uint(d);
             if (slot_out) slot_out[row] = slot;
@@ -298,6 +311,7 @@ __global__ __launch_bounds__(kBlock) void k_map_radius(GridView g, unsigned int 
 
 // LII_RADIUS_SORTED, behind the sort of (query << 32 | d2 bits, slot): row r of the result is the point in slot slots[r] at the d2 in the
 // key's low word.  rows = min(total[0] - base, capacity) is read from the device (the device form does not know the total on the host).
+template <int W>
 __global__ __launch_bounds__(kBlock) void k_radius_gather(const float4* __restrict__ pts, unsigned int pts_cap, const unsigned long long* __restrict__ keys,
                                                           const unsigned int* __restrict__ slots, const long long* __restrict__ total, long long base,
                                                           long long capacity, float* __restrict__ pts_out, float* __restrict__ d2_out) {
@@ -307,12 +321,14 @@ __global__ __launch_bounds__(kBlock) void k_radius_gather(const float4* __restri
     if (d2_out) d2_out[row] = __uint_as_float((unsigned int)(keys[row] & 0xFFFFFFFFull));
     if (pts_out) {
       const unsigned int slot = slots[row];
-      float x = 0.f, y = 0.f, z = 0.f;
+      float x = 0.f, y = 0.f, z = 0.f, w = 0.f;
       if (slot < pts_cap) {
         const F3 m = load_xyz(pts, slot);
         x = m.x; y = m.y; z = m.z;
+        if (W == 4) w = pts[slot].w;
       }
-      pts_out[3 * row] = x; pts_out[3 * row + 1] = y; pts_out[3 * row + 2] = z;
+      pts_out[W * row] = x; pts_out[W * row + 1] = y; pts_out[W * row + 2] = z;
+      if (W == 4) pts_out[W * row + 3] = w;
     }
   }
 }
@@ -323,26 +339,31 @@ void launch_map_radius_count(const GridView& g, unsigned int n_entries, unsigned
                              int r_max, long long* count_out, hipStream_t s) {
   if (n <= 0) return;
   const unsigned int blocks = (unsigned int)(((long long)n + kQueryWaves - 1) / kQueryWaves);
-  hipLaunchKernelGGL(k_map_radius<false>, dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes,
+  hipLaunchKernelGGL((k_map_radius<false, 3>), dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes,
                      max_d2, r_max, count_out, (const long long*)nullptr, 0ll, 0ll, (float*)nullptr, (float*)nullptr, (unsigned long long*)nullptr,
                      (unsigned int*)nullptr);
 }
 
 void launch_map_radius_fill(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2,
                             int r_max, const long long* offsets, long long base, long long capacity, float* pts_out, float* d2_out,
-                            unsigned long long* key_out, unsigned int* slot_out, hipStream_t s) {
+                            unsigned long long* key_out, unsigned int* slot_out, hipStream_t s, int row_floats) {
   if (n <= 0 || capacity <= 0) return;
   const unsigned int blocks = (unsigned int)(((long long)n + kQueryWaves - 1) / kQueryWaves);
-  hipLaunchKernelGGL(k_map_radius<true>, dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes,
-                     max_d2, r_max, (long long*)nullptr, offsets, base, capacity, pts_out, d2_out, key_out, slot_out);
+  if (row_floats == 4)
+    hipLaunchKernelGGL((k_map_radius<true, 4>), dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes,
+                       max_d2, r_max, (long long*)nullptr, offsets, base, capacity, pts_out, d2_out, key_out, slot_out);
+  else
+    hipLaunchKernelGGL((k_map_radius<true, 3>), dim3(blocks), dim3(kBlock), 0, s, g, n_entries, pts_cap, static_cast<const char*>(queries), n, stride_bytes,
+                       max_d2, r_max, (long long*)nullptr, offsets, base, capacity, pts_out, d2_out, key_out, slot_out);
 }
 
 void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const unsigned long long* keys, const unsigned int* slots, const long long* total,
-                              long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s) {
+                              long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s, int row_floats) {
   if (capacity <= 0) return;
   const long long want = (capacity - 1) / kBlock + 1;
   const unsigned int blocks = want < 2048 ? (unsigned int)want : 2048u;  // (grid-stride beyond that)
-  hipLaunchKernelGGL(k_radius_gather, dim3(blocks), dim3(kBlock), 0, s, g.pts, pts_cap, keys, slots, total, base, capacity, pts_out, d2_out);
+  if (row_floats == 4) hipLaunchKernelGGL(k_radius_gather<4>, dim3(blocks), dim3(kBlock), 0, s, g.pts, pts_cap, keys, slots, total, base, capacity, pts_out, d2_out);
+  else hipLaunchKernelGGL(k_radius_gather<3>, dim3(blocks), dim3(kBlock), 0, s, g.pts, pts_cap, keys, slots, total, base, capacity, pts_out, d2_out);
 }
 
 }  // namespace lii

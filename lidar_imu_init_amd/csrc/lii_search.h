@@ -19,7 +19,7 @@ __device__ __forceinline__ int xcd_remap(int b, int nb_real) {
 struct F3 {
   float x, y, z;
 };
-// xyz of map slot `idx`: 12 of the 16 bytes (w is the insertion id).  The byte offset is formed in 32 bits (the point array holds
+// xyz of map slot `idx`: 12 of the 16 bytes (w is the point's intensity).  The byte offset is formed in 32 bits (the point array holds
 // fewer than 2^28 slots), so the load takes the uniform base from scalar registers and ONE address register.
 __device__ __forceinline__ F3 load_xyz(const float4* __restrict__ pts, unsigned int idx) {
   typedef float f3v __attribute__((ext_vector_type(3)));
