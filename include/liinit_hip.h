@@ -627,6 +627,48 @@ int lii_last_solve_info(lii_handle h, int32_t* pivoted_passes);
  * launch's (one small device read, synchronises the handle's stream). */
 int lii_last_unfinished_queries(lii_handle h, int32_t* n_last);
 
+/* ---- per-point measurement noise from range and bearing.  src/laserMapping.cpp:1039-1042 forms a 3 x 3 covariance for every selected
+ * point - calcBodyVar(point_this, 0.02, 0.05, var) (:158-181): range_var along the ray plus a bearing term across it, rotated into the world
+ * frame by rot_end - and :1050 discards it: R_inv(i) = 1000 for every point, whose square root :1051 stores as the effect cloud's intensity.
+ * This is the model its authors meant, switched on by choice.  LII_ABI_VERSION stays 9: everything below is new.
+ * THE DEFECT.  calcBodyVar builds the basis of the ray's tangent plane as base_vector1 = (1, 1, -(dx + dy) / dz) (:170-171): NaN for any
+ * point with z = 0 in the IMU frame - a spinning LiDAR's horizontal ring - so the literal form cannot be switched on.
+ * THE CLOSED FORM.  The update needs only n^T (R_end var R_end^T) n.  With p_I = R_LI p_L + T_LI (:1039), t = R_end^T n (n: the float-cast
+ * normal the Jacobian reads back, :1047-1048), A = p_I x t (the row's first three columns), u = t . p_I, r^2 = |p_I|^2:
+ *     sigma^2_i = 1 / laser_point_cov_inv + sr2 u^2 / r^2 + s2 |A|^2        (the radial term 0 when r^2 == 0)
+ *     R_inv_i   = 1 / sigma^2_i
+ * because N = [base_vector1, base_vector2] (:170-177) is an orthonormal basis of the tangent plane, so A diag(s2) A^T = s2 r^2 (I - d d^T)
+ * (:178-180) whatever basis is chosen.  Finite everywhere; all arithmetic in double.  The two constants are formed once per
+ * lii_point_noise_set:  sr2 = (double)((float)range_inc * (float)range_inc) - range_inc and range_var are floats in calcBodyVar (:158-161) - and
+ * s2 = sin((double)(float)degree_inc * 0.017453293)^2 (:163-164), the constant being PCL's DEG2RAD macro as the reference compiles it (restated
+ * from knowledge of PCL, not pinned by a build).
+ *   lii_point_noise           <- the arguments of calcBodyVar at :1041.  model 0 (default): R_inv = lii_config::laser_point_cov_inv for every
+ *                             point, :1050 - every launch, instantiation and result as before the setting existed.  model 1: the above.
+ *   lii_point_noise_set       a standing setting of the handle, like lii_map_intensity_set; m == NULL: model 0.  Honoured by every fit pass,
+ *                             search or cached-plane, of lii_iekf_iterate, lii_iekf_update, lii_scan_register, lii_scan_register_imu,
+ *                             lii_scan_register_cv and LII_TEST=host_solve (<- :1039-1050 inside the loop :957-1134: the weights are a function
+ *                             of the current state, recomputed by every pass).  The two gates (:987-1011) and effect_feat_num do not look at them.
+ *                             The buffer behind lii_point_noise_download is created by the first call with model 1.  Ends a pre-armed launch first.
+ *                             LII_ERR_INVALID: NULL handle, struct_size != sizeof(lii_point_noise), a model other than 0 / 1, a negative or
+ *                             non-finite constant.  LII_ERR_STATE: a communicator is attached (single rank only for now; lii_comm_init /
+ *                             lii_comm_init_ex on a handle with model 1 refuse likewise); from inside lii_scan_job::while_waiting.
+ *   lii_point_noise_get       the setting as the handle holds it (struct_size is checked on the way in).
+ *   lii_point_noise_download  <- feats_down_body->points[i].intensity = sqrt(R_inv(i)) (:1051): the buffer of the last fit pass, one float per
+ *                             point of the down-sampled cloud in the device's order (the rows of lii_scan_download(h, 2)) - (float)sqrt(R_inv_i)
+ *                             of a selected point, 0.0f otherwise.  *n: the number of rows (always set); capacity < *n: LII_ERR_CAPACITY.
+ *                             LII_ERR_STATE: model 0, or no fit pass since the model was set.
+ *   The wire form of LII_PUB_EFFECT (lii_publish_wire_*) carries these values as the records' intensity under model 1 - what :1051 plus
+ *   publish_effect_world (:625-636) would publish - and the constant (float)sqrt(1000.0) under model 0. */
+typedef struct lii_point_noise {
+  uint32_t struct_size;
+  int32_t model;     /* 0: R_inv = laser_point_cov_inv for every point (default, :1050); 1: range / bearing (:1039-1042) */
+  double range_inc;  /* [m]   calcBodyVar's range_inc  (0.02 at :1041) */
+  double degree_inc; /* [deg] calcBodyVar's degree_inc (0.05 at :1041) */
+} lii_point_noise;
+int lii_point_noise_set(lii_handle h, const lii_point_noise* m);
+int lii_point_noise_get(lii_handle h, lii_point_noise* m);
+int lii_point_noise_download(lii_handle h, float* sqrt_rinv, int32_t capacity, int32_t* n);
+
 /* The per-scan sequence of main() (src/laserMapping.cpp:909-1134) in ONE call, enqueued back to back on the handle's
  * stream with a single host round trip at the end: p_imu->Process' undistortion (:909; the scan is the one handed over by
  * lii_scan_upload / lii_scan_set_device, or job->scan_dev), downSizeFilterSurf.filter (:917-919) and the iterated update

@@ -95,6 +95,10 @@ class lii_map_removed_info(C.Structure):
                 ("collected_total", C.c_int64), ("lost_total", C.c_int64)]
 
 
+class lii_point_noise(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int32), ("range_inc", C.c_double), ("degree_inc", C.c_double)]
+
+
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
@@ -177,6 +181,9 @@ _DECLS = {
     "lii_map_pcd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "lii_map_intensity_set": (C.c_int, [C.c_void_p, C.c_int32]),
     "lii_map_intensity_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "lii_point_noise_set": (C.c_int, [C.c_void_p, C.POINTER(lii_point_noise)]),
+    "lii_point_noise_get": (C.c_int, [C.c_void_p, C.POINTER(lii_point_noise)]),
+    "lii_point_noise_download": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),
     "lii_map_commit": (C.c_int, [C.c_void_p]),
     "lii_map_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_nearest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1030,6 +1037,33 @@ class Registrar:
         rep = lii_iekf_report()
         self._check(self.L.lii_scan_register(self.h, C.byref(job), _ptr(state.pod), _ptr(state_prop.pod), C.byref(rep)))
         return _report(rep)
+
+    # ------------------------------------------------------------------ per-point measurement noise (calcBodyVar, src/laserMapping.cpp:158-181)
+    def set_point_noise(self, range_inc=0.02, degree_inc=0.05):
+        """lii_point_noise_set, model 1: every fit pass from here on weights a selected point by R_inv_i = 1 / sigma^2_i,
+        sigma^2_i = LASER_POINT_COV + the range term along the ray + the bearing term across it (the arguments of calcBodyVar at
+        src/laserMapping.cpp:1041: 0.02 m, 0.05 deg) - a standing setting of the handle, off by default."""
+        m = lii_point_noise(C.sizeof(lii_point_noise), 1, float(range_inc), float(degree_inc))
+        self._check(self.L.lii_point_noise_set(self.h, C.byref(m)))
+
+    def clear_point_noise(self):
+        """Back to model 0: R_inv = laser_point_cov_inv for every point (src/laserMapping.cpp:1050)."""
+        self._check(self.L.lii_point_noise_set(self.h, None))
+
+    def point_noise(self):
+        """dict(model, range_inc, degree_inc) as the handle holds them."""
+        m = lii_point_noise(C.sizeof(lii_point_noise), 0, 0.0, 0.0)
+        self._check(self.L.lii_point_noise_get(self.h, C.byref(m)))
+        return dict(model=int(m.model), range_inc=float(m.range_inc), degree_inc=float(m.degree_inc))
+
+    def point_noise_download(self):
+        """(n,) float32: (float)sqrt(R_inv_i) of every point of the down-sampled cloud as the last fit pass left it - 0 where the point
+        was not selected - in the device's order (the intensity src/laserMapping.cpp:1051 stores).  LIIError(-5) under model 0 or before
+        the first pass."""
+        n = C.c_int32(0)
+        out = np.zeros(max(self.max_scan_points, 1), np.float32)
+        self._check(self.L.lii_point_noise_download(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), len(out), C.byref(n)))
+        return out[:n.value].copy()
 
     # ------------------------------------------------------------------ IMU processing (ImuProcess::Process on the device)
     def set_imu_noise(self, cov_gyr=None, cov_acc=None, cov_bias_gyr=None, cov_bias_acc=None, cov_R_LI=None, cov_T_LI=None,

@@ -82,6 +82,7 @@ RegistrationBuffers reg_buffers(const lii_context* c) {
   rb.shard_rank = c->net.rank;
   rb.shard_world = (c->net.n_ranks > 1 && c->net.library_partition && !c->body_partitioned) ? c->net.n_ranks : 1;
   if (c->solo_share < -1 && c->net.n_ranks <= 1) { rb.shard_world = -c->solo_share; rb.shard_rank = 0; }
+  rb.sqrt_rinv = c->noise.model == 1 ? c->noise.d_sqrt_rinv() : nullptr;
   return rb;
 }
 PoseArg pose_of(const lii_state& s) {

@@ -178,6 +178,7 @@ int lii_comm_init_ex(lii_handle h, int32_t n_ranks, int32_t rank, const uint8_t 
   if (!h || !id_in || n_ranks < 1 || rank < 0 || rank >= n_ranks || transport < LII_COMM_AUTO || transport > LII_COMM_MAILBOX_HOST)
     return fail(h, LII_ERR_INVALID, "lii_comm_init: bad arguments");
   if (h->map_intensity) return fail(h, LII_ERR_STATE, "lii_comm_init: lii_map_intensity_set is on - single rank for now");
+  if (h->noise.model == 1) return fail(h, LII_ERR_STATE, "lii_comm_init: lii_point_noise_set holds model 1 - single rank only for now");
   const int rc = comm_init(h, n_ranks, rank, id_in, transport);
   partition_refresh(h);  // (n_ranks / rank as the set-up left them: 1 / 0 after a failure)
   return rc;

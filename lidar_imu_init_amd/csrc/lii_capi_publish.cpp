@@ -81,6 +81,7 @@ int lii_impl::publish_enqueue(lii_handle h, const IekfCtrl* guard, const PoseArg
   a.w_body = (w_clouds & LII_PUB_BODY) ? W.d_cloud[3][slot].get() : nullptr;
   a.w_scan_int = (w_clouds && h->inten.have && n_scan > 0) ? h->inten.d_scan.get() : nullptr;
   a.w_body_int = (a.w_scan_int && h->inten.body_have) ? h->inten.d_body.get() : nullptr;
+  a.w_effect_int = (a.w_effect && h->noise.model == 1) ? h->noise.d_sqrt_rinv() : nullptr;  // (written by the fit passes this launch stands behind)
   a.dense = want_dense ? P.d_cloud[0][slot].get() : nullptr;
   a.save = want_save ? P.d_save.get() : nullptr;
   a.scan_int = scan_int ? h->inten.d_scan.get() : nullptr;

@@ -21,6 +21,9 @@ void launch_knn(lii_handle h, const GridView& g, const RegistrationBuffers& rb, 
   lii::launch_knn(g, rb, pose, h->d_ctrl, forced, h->d_ctrl->search_pose, h->stream, epoch, ev_start, ev_stop);
 }
 
+// lii_point_noise_set, model 1: a fit launch has been enqueued - lii_point_noise_download has something to serve
+void note_noise_pass(lii_handle h) { if (h->noise.model == 1) h->noise.have_pass = true; }
+
 int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double* out91) {
   if (h->n_body <= 0) return fail(h, LII_ERR_STATE, "no down-sampled scan (call lii_downsample / lii_downsample_skip)");
   int rc = commit_map(h);
@@ -42,6 +45,7 @@ int iterate(lii_handle h, const lii_state* st, bool search, bool imu_en, double*
   if (prof) HIPCHK(h, hipEventRecord(h->prof.ev[3], h->stream));
   launch_fit_reduce(g, rb, h->d_pose, h->d_ctrl, search ? 1 : 0, imu_en ? 1 : 0, h->cfg.plane_threshold,
                     h->cfg.laser_point_cov_inv, h->stream, epoch);
+  note_noise_pass(h);
   if (prof) HIPCHK(h, hipEventRecord(h->prof.ev[1], h->stream));
   launch_reduce91(rb, h->d_out91, h->d_ctrl, 1, h->stream, epoch);
   if (prof) HIPCHK(h, hipEventRecord(h->prof.ev[2], h->stream));
@@ -184,6 +188,7 @@ struct DevicePasses {
     // are finished by a launch of their own, one wavefront per listed query (k_complete_listed; nothing to do -> it returns at once)
     if (knn && h->wide_listed && !h->net.comm && h->net.n_ranks <= 1) launch_complete_listed(g, rb, h->d_ctrl, -1, s, epoch);
     launch_fit_reduce(g, rb, pose, h->d_ctrl, -1, opts->imu_en ? 1 : 0, h->cfg.plane_threshold, h->cfg.laser_point_cov_inv, s, epoch);
+    note_noise_pass(h);
     if (h->prof.kp_active) { const int r = kp_mark(h, LII_KP_SOLVE, it); if (r != LII_OK) return r; }
     if (!h->net.comm) {  // single GPU or node-local mailbox: final sum (+ exchange) and solve in one launch
       launch_reduce_solve(rb, h->d_gran, h->d_ctrl, h->h_res, mailbox_view(h), s, epoch);
@@ -867,6 +872,67 @@ int lii_scan_register(lii_handle h, const lii_scan_job* job, lii_state* state, c
                       lii_iekf_report* report) {
   return scan_register_job(h, job, state, state_prop, report, nullptr);
 }
+// ------------------------------------------------------------------------------------------------ per-point measurement noise
+int lii_point_noise_set(lii_handle h, const lii_point_noise* m) {
+  if (!h) return LII_ERR_INVALID;
+  if (m && m->struct_size != sizeof(lii_point_noise)) return fail(h, LII_ERR_INVALID, "lii_point_noise_set: struct_size");
+  const int model = m ? m->model : 0;
+  if (model != 0 && model != 1) return fail(h, LII_ERR_INVALID, "lii_point_noise_set: model must be 0 or 1");
+  if (m && !(std::isfinite(m->range_inc) && m->range_inc >= 0.0 && std::isfinite(m->degree_inc) && m->degree_inc >= 0.0))
+    return fail(h, LII_ERR_INVALID, "lii_point_noise_set: range_inc and degree_inc must be finite and not negative");
+  if (h->net.comm || h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, "lii_point_noise_set: single rank only for now (a communicator is attached)");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_point_noise_set: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end)
+  if (model == 1 && !h->noise.d_buf) {
+    const size_t bytes = size_t(lii::kNoiseHeadBytes) + sizeof(float) * size_t(std::max(h->cfg.max_scan_points, 1));
+    HIPCHK(h, h->noise.d_buf.alloc(bytes));
+    HIPCHK(h, hipMemsetAsync(h->noise.d_buf, 0, bytes, h->stream));  // (nothing reads a point's entry before a fit pass has written it; zeros all the same)
+  }
+  h->noise.model = model;
+  h->noise.range_inc = m ? m->range_inc : 0.0;
+  h->noise.degree_inc = m ? m->degree_inc : 0.0;
+  h->noise.have_pass = false;
+  if (model == 1) {
+    // calcBodyVar (src/laserMapping.cpp:158-164): range_inc, range_var and degree_inc are floats there.  0.017453293: PCL's DEG2RAD macro as
+    // the reference compiles it - restated from knowledge of PCL, not pinned by a build.
+    const float ri = (float)m->range_inc;
+    const double sn = std::sin((double)(float)m->degree_inc * 0.017453293);
+    static_assert(sizeof(lii::NoiseArg) <= size_t(lii::kNoiseHeadBytes), "the constants stand in front of the buffer");
+    const lii::NoiseArg arg = {1.0 / h->cfg.laser_point_cov_inv /* LASER_POINT_COV */, (double)(ri * ri), sn * sn};
+    // (the fit launches read them there; launches still on the stream are drained passes, which return before they would)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->noise.d_buf, &arg, sizeof(arg), hipMemcpyHostToDevice));
+  }
+  return LII_OK;
+}
+int lii_point_noise_get(lii_handle h, lii_point_noise* m) {
+  if (!h) return LII_ERR_INVALID;
+  if (!m || m->struct_size != sizeof(lii_point_noise)) return fail(h, LII_ERR_INVALID, "lii_point_noise_get: bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_point_noise_get: a registration is under way (lii_scan_job::while_waiting)");
+  m->model = h->noise.model;
+  m->range_inc = h->noise.range_inc;
+  m->degree_inc = h->noise.degree_inc;
+  return LII_OK;
+}
+int lii_point_noise_download(lii_handle h, float* sqrt_rinv, int32_t capacity, int32_t* n) {
+  if (!h) return LII_ERR_INVALID;
+  if (!n) return fail(h, LII_ERR_INVALID, "lii_point_noise_download: bad arguments");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, "lii_point_noise_download: a registration is under way (lii_scan_job::while_waiting)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (h->noise.model != 1) return fail(h, LII_ERR_STATE, "lii_point_noise_download: model 0 (lii_point_noise_set)");
+  if (!h->noise.have_pass) return fail(h, LII_ERR_STATE, "lii_point_noise_download: no fit pass since the model was set");
+  { int rc0 = resolve_n_body(h); if (rc0 != LII_OK) return rc0; }
+  const int rows = h->n_body;
+  *n = rows;
+  if (capacity < rows) return fail(h, LII_ERR_CAPACITY, "lii_point_noise_download: capacity too small");
+  if (rows == 0) return LII_OK;
+  if (!sqrt_rinv) return fail(h, LII_ERR_INVALID, "lii_point_noise_download: bad arguments");
+  HIPCHK(h, hipMemcpyAsync(h->h_stage, h->noise.d_sqrt_rinv(), sizeof(float) * size_t(rows), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::memcpy(sqrt_rinv, h->h_stage.get(), sizeof(float) * size_t(rows));
+  return LII_OK;
+}
+
 int lii_neighbors_download(lii_handle h, float* pts, int32_t* counts, uint8_t* selected, int32_t capacity) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
   if (!h) return LII_ERR_INVALID;

@@ -447,6 +447,17 @@ struct lii_context {
     std::chrono::steady_clock::time_point host_last_return;
     double host_loop_enq_us = 0;
   } prof;
+  // ---- the per-point measurement noise (lii_point_noise_*, lii_capi_register.cpp): a standing setting, model 0 by default.  The buffer
+  // does not exist before the first lii_point_noise_set with model 1.
+  struct PointNoise {
+    int model = 0;                  // 0: R_inv = laser_point_cov_inv for every point; 1: range / bearing (calcBodyVar)
+    double range_inc = 0.0, degree_inc = 0.0;  // as set (lii_point_noise_get)
+    // the model's constants as the fit launches read them (lii::NoiseArg, kNoiseHeadBytes) | max_scan_points floats: one allocation, so
+    // that the launch finds the constants through the pointer it carries anyway
+    DevBuf<unsigned char> d_buf;
+    float* d_sqrt_rinv() const { return d_buf ? reinterpret_cast<float*>(d_buf.get() + lii::kNoiseHeadBytes) : nullptr; }  // RegistrationBuffers::sqrt_rinv
+    bool have_pass = false;         // a fit pass has written the buffer since the model was set (lii_point_noise_download)
+  } noise;
 };
 
 

@@ -229,7 +229,23 @@ struct RegistrationBuffers {
   // An entry is everything the completion needs to start with: (world point, query index) and (neighbour count with its flags, -, -, -).
   int* flag_count;
   float4* flag_list;  // 2 x kListCap entries of two float4
+  // lii_point_noise_set, model 1: per point, beside `selected`, what the fit pass leaves of the point's own weight - (float)sqrt(R_inv_i) for a
+  // selected point, 0.0f otherwise (the intensity src/laserMapping.cpp:1051 stores).  nullptr under model 0.  (The last member: every
+  // other one keeps its place in the kernels' arguments.)
+  float* sqrt_rinv;
 };
+// The constants of the range / bearing noise model (lii_point_noise_set), formed once on the host; read by the NOISE instantiations of
+// k_fit_reduce alone:  sigma^2_i = base + sr2 u^2 / r^2 + s2 |A|^2  (include/liinit_hip.h: lii_point_noise).  They live in device memory,
+// kNoiseHeadBytes in front of the floats RegistrationBuffers::sqrt_rinv points to: the fit launch keeps its arguments.
+struct NoiseArg {
+  double base;  // 1 / laser_point_cov_inv (LASER_POINT_COV)
+  double sr2;   // range_inc^2, formed in float as calcBodyVar does
+  double s2;    // sin(degree_inc in radians)^2
+};
+constexpr int kNoiseHeadBytes = 64;
+__host__ __device__ inline const NoiseArg* noise_head(const float* sqrt_rinv) {
+  return reinterpret_cast<const NoiseArg*>(reinterpret_cast<const unsigned char*>(sqrt_rinv) - kNoiseHeadBytes);
+}
 constexpr int kFlagCap = 256;          // listed queries a fit launch hands to its completion workgroups (more: every workgroup finishes its own, as in round 4 ...
 constexpr int kListCap = 4096;         // ... unless a launch of its own in front of the fit launch has finished the listed ones, one wavefront per query:
                                        // k_complete_listed, enqueued when the scan before listed more than kFlagCap - the launch plan's way)

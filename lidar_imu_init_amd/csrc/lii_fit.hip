@@ -5,7 +5,8 @@
 // Kernels and the reference code they replace (paths relative to the reference root):
 //   k_fit_reduce       its completion workgroups finish the searches the 3 x 3 x 3 pass could not prove exact (knn_fallback_wave:
 //                      ikd_Tree.cpp:827-842), then esti_plane + residual / selection (src/laserMapping.cpp:987-1011), Jacobian rows
-//                      (:1035-1071) and the H^T R^-1 H / H^T R^-1 z sums (:1073-1080)
+//                      (:1035-1071) and the H^T R^-1 H / H^T R^-1 z sums (:1073-1080); with lii_point_noise_set's model 1 each point's
+//                      own R^-1 from its range and bearing (calcBodyVar, :158-181, :1039-1042) instead of the constant of :1050
 //   k_knn_complete     the completion alone (lii_map_incremental of a sharded job)
 //   k_complete_listed  the completion of a search pass that listed more unfinished queries than the fit launch's completion workgroups
 //                      take (a sensor looking into unmapped space): one wavefront per listed query, in a launch of its own
@@ -225,13 +226,23 @@ struct ReduceShared {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 // partial_out[t * stride] (t < 91) receives this block's sums
+// NOISE (lii_point_noise_set, model 1): every point has a weight of its own - `rinv` is then the LANE's R_inv_i (residual_row), the
+// factors go into LDS scaled by sqrt(R_inv_i) and the sums are taken as they come out: S = (W^1/2 V)^T (W^1/2 V), still the one product.
+template <bool NOISE>
 __device__ __forceinline__ void block_reduce_rows(ReduceShared& sh, const double (&h)[12], double z, bool sel, double rinv,
                                                   double* __restrict__ partial_out, int stride) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double* row = sh.row[wave];
+  if (NOISE) {
+    const double sw = sqrt(rinv);
 #pragma unroll
-  for (int c = 0; c < 12; c++) row[lane * kRowStride + c] = sel ? h[c] : 0.0;
-  row[lane * kRowStride + 12] = sel ? z : 0.0;
+    for (int c = 0; c < 12; c++) row[lane * kRowStride + c] = sel ? sw * h[c] : 0.0;
+    row[lane * kRowStride + 12] = sel ? sw * z : 0.0;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 12; c++) row[lane * kRowStride + c] = sel ? h[c] : 0.0;
+    row[lane * kRowStride + 12] = sel ? z : 0.0;
+  }
   row[lane * kRowStride + 13] = 0.0; row[lane * kRowStride + 14] = 0.0; row[lane * kRowStride + 15] = 0.0;
   unsigned long long m = __ballot(sel);
   if (lane == 0) sh.cnt[wave] = __popcll(m);
@@ -250,7 +261,7 @@ __device__ __forceinline__ void block_reduce_rows(ReduceShared& sh, const double
     const int i = q + 4 * r, j = c;
     if (i < 12 && j <= 12 && i <= j) {
       const int t = j == 12 ? 78 + i : i * 12 - (i * (i - 1)) / 2 + (j - i);
-      sh.part[wave][t] = acc[r] * rinv;
+      sh.part[wave][t] = acc[r] * (NOISE ? 1.0 : rinv);  // (NOISE: the weights are in the factors)
     }
   }
   __syncthreads();
@@ -276,9 +287,16 @@ struct RowOut {
   double z;
   bool sel;
 };
+// NOISE (lii_point_noise_set, model 1): a selected point also yields R_inv_i = 1 / sigma^2_i (`w`), the weight src/laserMapping.cpp:1039-1042
+// computes and :1050 discards.  calcBodyVar (:158-181) gives the point var = range_var d d^T + A diag(s^2) A^T in the IMU frame, d the ray,
+// A = [p_I]x N with N a basis of the ray's tangent plane - (1, 1, -(dx + dy) / dz): NaN for any point with z = 0 - and the update needs
+// n^T (R_end var R_end^T) n alone.  N is orthonormal, so A diag(s^2) A^T = s^2 r^2 (I - d d^T) whatever the basis, and with t = R_end^T n:
+//   sigma^2_i = LASER_POINT_COV + range_var (t . p_I)^2 / r^2 + s^2 |p_I x t|^2      (the radial term 0 when r^2 == 0)
+// finite everywhere, from values the row holds already: p_I x t is h[0 .. 2].
+template <bool NOISE>
 __device__ __forceinline__ void residual_row(const PoseArg& ps, int imu_en, double bx, double by, double bz, double ix,
                                              double iy, double iz, float wx, float wy, float wz, double pa, double pbn,
-                                             double pc, double pd, RowOut& o) {
+                                             double pc, double pd, RowOut& o, const NoiseArg& na, double& w) {
   float pd2 = (float)(pa * wx + pbn * wy + pc * wz + pd);
   double pbnorm = sqrt(bx * bx + by * by + bz * bz);
   float s = (float)(1 - 0.9 * fabsf(pd2) / sqrt(pbnorm));
@@ -303,6 +321,13 @@ __device__ __forceinline__ void residual_row(const PoseArg& ps, int imu_en, doub
       o.h[9] = tx; o.h[10] = ty; o.h[11] = tz;
     }
     o.z = -(double)pd2;
+    if (NOISE) {
+      const double a2 = o.h[0] * o.h[0] + o.h[1] * o.h[1] + o.h[2] * o.h[2];
+      const double u = tx * ix + ty * iy + tz * iz;
+      const double r2 = ix * ix + iy * iy + iz * iz;
+      const double radial = r2 > 0.0 ? na.sr2 * (u * u) / r2 : 0.0;
+      w = 1.0 / (na.base + radial + na.s2 * a2);
+    }
   }
 }
 // esti_plane on 5 neighbours; returns validity and (n̂, d)
@@ -985,7 +1010,11 @@ __global__ __launch_bounds__(kBlock) void k_complete_listed(GridView g, Registra
 // PRE: the launch stands behind a search launch (the host knows when it enqueues it): a lane requests its five neighbours at the head,
 // together with everything else, instead of its cached plane and selection flag - the fit of a search pass is then one round trip
 // (head) instead of two (head, lists) in front of the QR.  Should the device not search after all, the plane is fetched late.
-template <bool POSE_V, bool PRE>
+// NOISE: lii_point_noise_set, model 1 - every selected point carries its own R_inv_i into the sums (residual_row, block_reduce_rows) and
+// leaves (float)sqrt(R_inv_i) in rb.sqrt_rinv, 0.0f when it is not selected; `rinv` is not used and the model's constants are read from
+// the record in front of that buffer (noise_head), so that the launch has the arguments it always had.  NOISE = false is the kernel
+// without the model.
+template <bool POSE_V, bool PRE, bool NOISE>
 __global__ __launch_bounds__(kBlock, POSE_V ? 2 : 3) void k_fit_reduce(GridView g, RegistrationBuffers rb,
                                                         const PoseArg* __restrict__ pose,
                                                         const IekfCtrl* __restrict__ ctrl, int forced, int imu_en,
@@ -1158,6 +1187,9 @@ __global__ __launch_bounds__(kBlock, POSE_V ? 2 : 3) void k_fit_reduce(GridView 
   for (int c = 0; c < 12; c++) o.h[c] = 0;
   o.z = 0;
   o.sel = false;
+  double w_i = 0.0;  // (NOISE: the point's R_inv_i)
+  NoiseArg noise = {0.0, 0.0, 0.0};
+  if (NOISE) noise = *noise_head(rb.sqrt_rinv);  // (uniform: scalar loads)
   if (live && !skip_row) {
     float4 pb = e_body;
     if (!early) {  // (by value on every path: a choice between the three ADDRESSES sends e_body to scratch and waits for it at the head)
@@ -1210,10 +1242,11 @@ __global__ __launch_bounds__(kBlock, POSE_V ? 2 : 3) void k_fit_reduce(GridView 
         pa = pl[0]; pbn = pl[1]; pc = pl[2]; pd = pl[3];
       }
     }
-    if (candidate) residual_row(ps, imu_en, bx, by, bz, ix, iy, iz, wx, wy, wz, pa, pbn, pc, pd, o);
+    if (candidate) residual_row<NOISE>(ps, imu_en, bx, by, bz, ix, iy, iz, wx, wy, wz, pa, pbn, pc, pd, o, noise, w_i);
     rb.selected[i] = o.sel ? 1 : 0;
+    if (NOISE) rb.sqrt_rinv[i] = o.sel ? (float)sqrt(w_i) : 0.0f;
   }
-  block_reduce_rows(sh, o.h, o.z, o.sel, rinv, rb.partials + blk, rb.partial_stride);
+  block_reduce_rows<NOISE>(sh, o.h, o.z, o.sel, NOISE ? w_i : rinv, rb.partials + blk, rb.partial_stride);
 #ifdef LII_FALLBACK_TRACE
   if (completion_wg && defer && threadIdx.x == 0 && sh_needy.n > 0)
     atomicAdd(&g_fb_trace[19], (unsigned long long)(((int)(wall_clock64() & 0x7FFFFFFF) - sh_needy.key[kBlock - 1]) & 0x7FFFFFFF));
@@ -1251,8 +1284,10 @@ void launch_complete_listed(const GridView& g, const RegistrationBuffers& rb, co
   if (epoch <= 0) return;
   hipLaunchKernelGGL(k_complete_listed, dim3(kListCap / (kBlock / 64)), dim3(kBlock), 0, s, g, rb, ctrl, forced, epoch);
 }
-void launch_fit_reduce(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
-                       const IekfCtrl* ctrl, int forced, int imu_en, double plane_thr, double rinv, hipStream_t s, int epoch) {
+// which of the four instantiations of a model: by the scan's size and by what stands in front of the launch
+template <bool NOISE>
+static void launch_fit_reduce_as(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose, const IekfCtrl* ctrl, int forced, int imu_en,
+                                 double plane_thr, double rinv, hipStream_t s, int epoch) {
   int nb = nblk(shard_bound(rb), kBlock);
   if (nb < 1) nb = 1;
   const int nb_pad = ((nb + 7) / 8) * 8;
@@ -1261,12 +1296,18 @@ void launch_fit_reduce(const GridView& g, const RegistrationBuffers& rb, const P
   const dim3 grid(nb_pad + completion_blocks(epoch)), block(kBlock);
   const bool pre = epoch > 0;  // behind a search launch that lists its unfinished queries: the lanes request their neighbour lists at the head
   if (nb <= 512) {
-    if (pre) hipLaunchKernelGGL((k_fit_reduce<true, true>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
-    else hipLaunchKernelGGL((k_fit_reduce<true, false>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
+    if (pre) hipLaunchKernelGGL((k_fit_reduce<true, true, NOISE>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
+    else hipLaunchKernelGGL((k_fit_reduce<true, false, NOISE>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
   } else {
-    if (pre) hipLaunchKernelGGL((k_fit_reduce<false, true>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
-    else hipLaunchKernelGGL((k_fit_reduce<false, false>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
+    if (pre) hipLaunchKernelGGL((k_fit_reduce<false, true, NOISE>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
+    else hipLaunchKernelGGL((k_fit_reduce<false, false, NOISE>), grid, block, 0, s, g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, nb, epoch);
   }
+}
+void launch_fit_reduce(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
+                       const IekfCtrl* ctrl, int forced, int imu_en, double plane_thr, double rinv, hipStream_t s, int epoch) {
+  // rb.sqrt_rinv != nullptr: lii_point_noise_set holds model 1 - the instantiations with per-point weights (`rinv` is not used)
+  if (rb.sqrt_rinv != nullptr) launch_fit_reduce_as<true>(g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, s, epoch);
+  else launch_fit_reduce_as<false>(g, rb, pose, ctrl, forced, imu_en, plane_thr, rinv, s, epoch);
 }
 void launch_reduce91(const RegistrationBuffers& rb, double* out91, const IekfCtrl* ctrl, int forced, hipStream_t s, int epoch) {
   int nb = nblk(shard_bound(rb), kBlock);

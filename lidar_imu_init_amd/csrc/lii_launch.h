@@ -86,6 +86,7 @@ void fb_trace_read(unsigned long long out[32]);  // (measurement builds: the com
 #endif
 void launch_knn_complete(const GridView& g, const RegistrationBuffers& rb, hipStream_t s);
 void launch_complete_listed(const GridView& g, const RegistrationBuffers& rb, const IekfCtrl* ctrl, int forced, hipStream_t s, int epoch);  // (k_complete_listed: behind search launch `epoch`)
+// rb.sqrt_rinv != nullptr: lii_point_noise_set, model 1 - the instantiations with per-point weights; `rinv` is not used then
 void launch_fit_reduce(const GridView& g, const RegistrationBuffers& rb, const PoseArg* pose,
                        const IekfCtrl* ctrl, int forced, int imu_en, double plane_thr, double rinv, hipStream_t s, int epoch);
 void launch_reduce91(const RegistrationBuffers& rb, double* out91, const IekfCtrl* ctrl, int forced, hipStream_t s, int epoch);  // epoch: of the fit launch whose columns it sums
@@ -372,6 +373,9 @@ struct PublishArgs {
   uint4* w_effect;
   const float* w_scan_int;
   const float* w_body_int;
+  // lii_point_noise_set, model 1: the intensity of the EFFECT records, per point of the down-sampled cloud (RegistrationBuffers::sqrt_rinv);
+  // nullptr: the constant (float)sqrt(1000)
+  const float* w_effect_int;
 };
 constexpr int kWireQuads = 3;       // a record: 48 bytes = 3 x 16
 constexpr int kPcdChunkRows = 65536;  // lii_publish_saved_pcd's staging area (the chunk of lii_map_delete_points)

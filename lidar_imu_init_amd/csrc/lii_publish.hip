@@ -62,7 +62,8 @@ __device__ __forceinline__ void wire_store_slab(uint4* __restrict__ cloud, int b
 // five pointers null the launch is the INT = false instantiation: the kernel without the channel, instruction for instruction.
 // lii_publish_wire_set (WIRE): the same workgroups also form the clouds as 48-byte pcl::PointXYZINormal records (include/liinit_hip.h:
 // x y z 1.0f | 0 0 0 0 | intensity curvature 0 0) - the scan's write the DENSE and the BODY record (curvature: 0 / t_ms), the
-// down-sampled cloud's the DOWN record and, at the compacted place, the EFFECT record (intensity sqrt(1000), src/laserMapping.cpp:1050-1051).
+// down-sampled cloud's the DOWN record and, at the compacted place, the EFFECT record (intensity sqrt(1000), src/laserMapping.cpp:1050-1051;
+// under lii_point_noise_set's model 1 the point's own sqrt(R_inv_i), a.w_effect_int).
 // A workgroup's 256 records of DENSE / BODY / DOWN are 12 288 contiguous bytes: wire_store_slab.  With the six pointers null the launch is
 // the WIRE = false instantiation: the code of the kernel without the order.
 template <bool INT, bool WIRE>
@@ -156,7 +157,9 @@ __global__ __launch_bounds__(256) void k_publish_world(PublishArgs a, PoseArg ps
     const unsigned int at = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
     if (!WIRE || a.effect) a.effect[at] = o;
     if (WIRE && a.w_effect) {  // an arbitrary base: the lane's own record, three 16-byte stores
-      const WireRecord r = wire_record(o.x, o.y, o.z, __float_as_uint((float)__builtin_sqrt(1000.0)), 0u);
+      // (lii_point_noise_set, model 1: the point's own sqrt(R_inv_i) as the fit pass left it, :1051; else the constant of :1050)
+      const unsigned int q = a.w_effect_int ? __float_as_uint(a.w_effect_int[j]) : __float_as_uint((float)__builtin_sqrt(1000.0));
+      const WireRecord r = wire_record(o.x, o.y, o.z, q, 0u);
       uint4* at_w = a.w_effect + (size_t)at * kWireQuads;
       at_w[0] = r.q[0]; at_w[1] = r.q[1]; at_w[2] = r.q[2];
     }
