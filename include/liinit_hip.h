@@ -297,6 +297,39 @@ int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_byte
 int lii_map_radius_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
                        int64_t* offsets_dev /* n + 1 */, float* pts_dev, float* d2_dev, int64_t capacity,
                        int64_t* total_dev /* one word */);
+/* ---- candidate poses scored against the map in one call: the ranking step of a re-localisation (restart in a saved map, flg_reset -
+ * src/laserMapping.cpp:895-900 -, recovery after drift), where the caller holds no pose inside the update's convergence basin.
+ * For pose k the figures of ONE pass of src/laserMapping.cpp:957-1020, run with nearest_search_en on an all-true selection at the state
+ * `base` with rot_end / pos_end replaced by pose k (the extrinsic is base's; cov and the rest are not read): pointBodyToWorld with the
+ * registration path's rounding, the exact 5-NN with d2 <= max_match_dist2 inclusive, esti_plane at plane_threshold, pd2 and the gate
+ * s > 0.9 (:1001).  total_residual is what :961 / :1022 meant and the reference never accumulates (quirk A13).
+ *   res (optional, n_poses x n_down): res[k * n_down + i] = res_last[i] - fabs(pd2) as a float for a selected point, -1000.0f otherwise
+ *   (:987).  The cloud is the handle's current down-sampled cloud, the one lii_iekf_iterate would use; the host form's rows are in the
+ *   order of lii_scan_download(1), the device form's in the device's order of that cloud.
+ * Reads the map and the down-sampled cloud, writes NOTHING of the registration state: neighbour lists, sticky selection, cached planes,
+ * point-noise weights, lii_last_unfinished_queries and the publish buffers stay as they were.  Ends a pre-armed launch and joins a map
+ * update in flight first.  The host form waits; the _dev form only enqueues on the handle's stream (it waits only where the size of the
+ * down-sampled cloud is still on the device, and where the call needs more scratch than any call before it: growing it frees device
+ * memory, which waits for the device).  Scratch of the handle's, created by the first call and kept until lii_destroy: the _dev form holds
+ * 16 bytes per 64 (pose, point) pairs of its largest call - 128 KiB at 256 poses x 2 048 points, 512 MiB at the limit of 2^31 pairs -,
+ * the host form stages chunks of 2^22 pairs (about 50 MiB, device and pinned, with res).
+ * DETERMINISTIC: pose k's score and res row are the same bits scored alone or as any member of any batch, in one call or another
+ * (fixed-order sums in double, no atomics).
+ * LII_ERR_STATE: no map, no down-sampled cloud, inside lii_scan_job::while_waiting, a communicator of more than one rank attached.
+ * LII_ERR_INVALID: NULL arguments, n_poses < 1 or > 65 536, n_poses * n_down >= 2^31.
+ * A pose with a NaN or Inf entry, or one that puts every point outside the addressable grid, scores {0, 0, 0.0} with every res at -1000;
+ * its neighbours in the batch are not disturbed. */
+/* (a struct TAG only, no typedef: the record and the call that fills it share their name, which C and C++ allow for a tag and a function
+ * and for nothing else - write `struct lii_pose_score`) */
+struct lii_pose_score {   /* 16 bytes */
+  int32_t n_full;         /* points whose Nearest_Search returned NUM_MATCH_POINTS neighbours (d2 <= max_match_dist2) */
+  int32_t effect_num;     /* effect_feat_num of a search pass at this pose (:1013-1020) */
+  double  total_residual; /* sum of res_last[i] = |pd2| over the selected points (what :961/:1022 meant); 0 when none */
+};
+int lii_pose_score(lii_handle h, const lii_state* base, const double* poses /* n_poses x 12: rot_end row-major, pos_end */,
+                   int32_t n_poses, struct lii_pose_score* scores, float* res /* NULL, or n_poses x n_down */);
+int lii_pose_score_dev(lii_handle h, const lii_state* base, const double* poses_dev, int32_t n_poses,
+                       struct lii_pose_score* scores_dev, float* res_dev /* 0 or device */);
 /* ---- edits and queries by point and box: the rest of what a holder of the tree can do (include/ikd-Tree/ikd_Tree.h:165-187).
  * lii_map_delete_points <- ikdtree.Delete_Points(PointToDel)  (include/ikd-Tree/ikd_Tree.cpp:479-498, Delete_by_point :672-719,
  *                       same_point :1269-1271).  Every listed point (float xyz every stride_bytes, as for lii_map_build) takes ONE live

@@ -5,6 +5,7 @@ This package is the thin Python mirror used by tests, bench.py and harnesses: ct
 no compute happens in Python and nothing here falls back to a CPU implementation.
 """
 from .api import (LIIError, Registrar, State, calib_state_array, library_path, load_library,  # noqa: F401
-                  pcd_header, pose6d_array, wire_layout)
+                  pcd_header, pose6d_array, pose_grid, rank_poses, wire_layout)
 
-__all__ = ["LIIError", "Registrar", "State", "load_library", "library_path", "calib_state_array", "pose6d_array", "wire_layout", "pcd_header"]
+__all__ = ["LIIError", "Registrar", "State", "load_library", "library_path", "calib_state_array", "pose6d_array", "wire_layout", "pcd_header",
+           "pose_grid", "rank_poses"]

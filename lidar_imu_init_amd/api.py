@@ -99,6 +99,12 @@ class lii_point_noise(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int32), ("range_inc", C.c_double), ("degree_inc", C.c_double)]
 
 
+class lii_pose_score(C.Structure):
+    _fields_ = [("n_full", C.c_int32), ("effect_num", C.c_int32), ("total_residual", C.c_double)]
+
+
+POSE_SCORE_DTYPE = np.dtype([("n_full", "<i4"), ("effect_num", "<i4"), ("total_residual", "<f8")])  # struct lii_pose_score as a numpy record
+
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
@@ -189,6 +195,8 @@ _DECLS = {
     "lii_map_nearest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_nearest_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_nearest_xyzi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lii_pose_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lii_pose_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "lii_map_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -464,6 +472,51 @@ def calib_state_array(n):
     a = np.zeros((n, 22))
     a[:, 0] = a[:, 4] = a[:, 8] = 1.0
     return a
+
+
+def poses_array(poses):
+    """Candidate poses as lii_pose_score takes them: (K, 12) float64, rot_end row-major then pos_end.  Accepts that array, or a pair
+    (R (K, 3, 3), p (K, 3))."""
+    if isinstance(poses, (tuple, list)) and len(poses) == 2 and np.ndim(poses[0]) == 3:
+        R, p = np.asarray(poses[0], np.float64), np.asarray(poses[1], np.float64)
+        return np.ascontiguousarray(np.concatenate([R.reshape(len(R), 9), p.reshape(len(R), 3)], axis=1))
+    return np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12))
+
+
+def pose_grid(center_R, center_p, half_xy, step_xy, yaw_from, yaw_to, yaw_step):
+    """Candidate poses around (center_R, center_p) - pure numpy: yaw-about-world-z variations of center_R at positions offset in x and y.
+    Offsets: o_i = -half_xy + i step_xy for i = 0 .. floor(2 half_xy / step_xy + 1e-9) on each axis; yaws: yaw_from + j yaw_step while
+    < yaw_to - 1e-9 (yaw_to is exclusive: 0 .. 2 pi lists every direction once).  Pose (ix, iy, j) is R = Rz(yaw_j) center_R,
+    p = center_p + (o_ix, o_iy, 0) - roll, pitch and z are the centre's.  ORDER: x slowest, then y, yaw fastest - index
+    (ix * ny + iy) * n_yaw + j.  Returns (R (K, 3, 3), p (K, 3)), float64.  A step that is not positive: ValueError."""
+    if not (step_xy > 0 and yaw_step > 0 and half_xy >= 0 and np.isfinite([half_xy, step_xy, yaw_from, yaw_to, yaw_step]).all()):
+        raise ValueError("pose_grid: step_xy and yaw_step must be positive, half_xy not negative, everything finite")
+    center_R = np.asarray(center_R, np.float64).reshape(3, 3)
+    center_p = np.asarray(center_p, np.float64).reshape(3)
+    n_off = int(np.floor(2.0 * half_xy / step_xy + 1e-9)) + 1
+    off = -float(half_xy) + float(step_xy) * np.arange(n_off)
+    n_yaw = max(int(np.ceil((yaw_to - yaw_from) / yaw_step - 1e-9)), 0)
+    yaws = float(yaw_from) + float(yaw_step) * np.arange(n_yaw)
+    c, s = np.cos(yaws), np.sin(yaws)
+    Rz = np.zeros((n_yaw, 3, 3))
+    Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = c, -s, s, c, 1.0
+    Ry = Rz @ center_R
+    K = n_off * n_off * n_yaw
+    R = np.broadcast_to(Ry, (n_off, n_off, n_yaw, 3, 3)).reshape(K, 3, 3).copy()
+    p = np.empty((n_off, n_off, n_yaw, 3))
+    p[..., 0] = center_p[0] + off[:, None, None]
+    p[..., 1] = center_p[1] + off[None, :, None]
+    p[..., 2] = center_p[2]
+    return R, p.reshape(K, 3)
+
+
+def rank_poses(effect_num, total_residual):
+    """The ranking rule of Registrar.relocalize: indices by effect_num descending, then mean residual (total_residual / effect_num; +inf
+    where nothing was selected) ascending, then index ascending."""
+    eff = np.asarray(effect_num, np.int64)
+    tot = np.asarray(total_residual, np.float64)
+    mean = np.where(eff > 0, tot / np.maximum(eff, 1), np.inf)
+    return np.lexsort((np.arange(len(eff)), mean, -eff))
 
 
 class Registrar:
@@ -781,6 +834,54 @@ class Registrar:
         """map_nearest_dev with (n, k, 4) float32 rows: x, y, z, intensity."""
         self._check(self.L.lii_map_nearest_xyzi_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), int(k), float(max_dist),
                                                     _dev_address(pts_dev), _dev_address(d2_dev), _dev_address(count_dev)))
+
+    # ------------------------------------------------------------------ candidate poses against the map
+    def pose_score(self, base: State, poses, want_res=False):
+        """lii_pose_score: the figures of one search pass (src/laserMapping.cpp:957-1020, all-true selection) of the current
+        down-sampled cloud at each of the K poses - `poses` is (K, 12) doubles, rot_end row-major then pos_end, or a pair (R (K, 3, 3),
+        p (K, 3)) as pose_grid returns it; the extrinsic is base's.  Returns (n_full int32 (K,), effect_num int32 (K,), total_residual
+        float64 (K,)) and, with want_res, res float32 (K, n_down): |pd2| of a selected point, -1000 otherwise.  Leaves the neighbour
+        lists, the selection and everything else of a registration alone."""
+        P = poses_array(poses)
+        K = len(P)
+        sc = np.zeros(K, POSE_SCORE_DTYPE)
+        res = None
+        if want_res:
+            n = C.c_int32(0)
+            self._check(self.L.lii_scan_download(self.h, 1, None, 0, C.byref(n)))  # (the size of the down-sampled cloud)
+            res = np.zeros((K, n.value), np.float32)
+        self._check(self.L.lii_pose_score(self.h, _ptr(base.pod), _ptr(P) if K else None, K, _ptr(sc) if K else None,
+                                          _ptr(res) if res is not None and res.size else None))
+        out = (sc["n_full"].copy(), sc["effect_num"].copy(), sc["total_residual"].copy())
+        return out + (res,) if want_res else out
+
+    def pose_score_dev(self, base: State, poses_dev, n_poses, scores_dev, res_dev=None):
+        """pose_score with poses, scores (16-byte struct lii_pose_score records) and res in device memory the caller owns - raw
+        addresses or objects with __cuda_array_interface__; res rows in the device's order of the down-sampled cloud.  Enqueued on
+        the handle's stream; synchronize() - or any synchronous call - orders it."""
+        self._check(self.L.lii_pose_score_dev(self.h, _ptr(base.pod), _dev_address(poses_dev), int(n_poses), _dev_address(scores_dev),
+                                              _dev_address(res_dev)))
+
+    def relocalize(self, base: State, poses, top=3, max_iterations=4, updates=2):
+        """Re-localisation over candidate poses: pose_score ranks them (rank_poses: effect_num descending, mean residual ascending, index),
+        the `top` best each start `updates` consecutive iekf_update calls in LO mode (imu_en = False) on a copy of `base` with that pose,
+        and the state whose last update selected the most points wins (the earlier rank on a tie).  Returns (state, info) with info =
+        dict(order, n_full, effect_num, total_residual, tried = [(pose index, effect_num after its updates)], best = pose index)."""
+        P = poses_array(poses)
+        n_full, effect, total = self.pose_score(base, P)
+        order = rank_poses(effect, total)
+        best, best_eff, best_k, tried = None, -1, -1, []
+        for k in order[:max(int(top), 1)]:
+            st = base.copy()
+            st.rot_end[:] = P[k, :9].reshape(3, 3)
+            st.pos_end[:] = P[k, 9:]
+            eff = 0
+            for _ in range(max(int(updates), 1)):
+                eff = self.iekf_update(st, st.copy(), max_iterations=max_iterations, imu_en=False)["effect_num"]
+            tried.append((int(k), int(eff)))
+            if eff > best_eff:
+                best, best_eff, best_k = st, eff, int(k)
+        return best, dict(order=order, n_full=n_full, effect_num=effect, total_residual=total, tried=tried, best=best_k)
 
     def map_radius(self, q, max_dist, sorted=False, points=True):
         """The ball query (upstream ikd-Tree's Radius_Search) for the points q (n, >= 3) float: EVERY map point with d2 <= max_dist

@@ -1190,6 +1190,88 @@ int lii_map_nearest_xyzi(lii_handle h, const void* xyz, int32_t n, int32_t strid
   return map_nearest(h, "lii_map_nearest_xyzi", xyz, n, stride_bytes, k, max_dist, pts_out, d2_out, count_out, 4);
 }
 
+// ---- pose scoring (kernels: lii_score.hip): the figures of one search pass at K candidate poses
+namespace {
+static_assert(sizeof(struct lii_pose_score) == sizeof(lii::ScorePartial) && sizeof(struct lii_pose_score) == 16, "lii_pose_score is the kernels' record");
+constexpr int kPoseScoreMax = 65536;
+// What both forms check and settle before a launch; *n_down: the size of the down-sampled cloud, *r_max: the rings that cover max_match_dist2.
+// Nothing of the registration state is touched: the map update in flight is joined (commit_map), the cloud's size is read if it is still on
+// the device.
+int pose_score_begin(lii_handle h, const char* who, const lii_state* base, const void* poses, int32_t n_poses, const void* scores, int* n_down, int* r_max) {
+  if (!h) return LII_ERR_INVALID;
+  if (!base || !poses || !scores) return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments (base, poses, scores)");
+  if (n_poses < 1 || n_poses > kPoseScoreMax) return fail(h, LII_ERR_INVALID, std::string(who) + ": n_poses must be 1 .. 65536");
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, std::string(who) + ": a registration is under way (lii_scan_job::while_waiting)");  // (before anything touches the stream)
+  if (h->net.n_ranks > 1) return fail(h, LII_ERR_STATE, std::string(who) + ": single rank only (a communicator of more than one rank is attached)");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (h->n_body <= 0) return fail(h, LII_ERR_STATE, std::string(who) + ": no down-sampled scan (call lii_downsample / lii_downsample_skip)");
+  int rc = resolve_n_body(h);
+  if (rc != LII_OK) return rc;
+  if (h->n_body <= 0) return fail(h, LII_ERR_STATE, std::string(who) + ": no down-sampled scan (call lii_downsample / lii_downsample_skip)");
+  if ((long long)n_poses * (long long)h->n_body >= (1ll << 31)) return fail(h, LII_ERR_INVALID, std::string(who) + ": n_poses * n_down must stay below 2^31");
+  rc = nearest_map(h, who);
+  if (rc != LII_OK) return rc;
+  const double cells = std::sqrt(double(h->cfg.max_match_dist2)) / double(h->cell_size);
+  if (cells > 32.0) return refuse_reach(h, who, double(h->cfg.max_match_dist2));
+  *n_down = h->n_body;
+  *r_max = int(std::ceil(cells)) + 1;
+  return LII_OK;
+}
+void pose_score_launch(lii_handle h, const lii_state* base, const double* poses_dev, int n_poses, int n_down, int r_max, lii::ScorePartial* scores_dev, float* res_dev) {
+  const size_t entries = std::min<size_t>(h->cells_cap_blocks * 512, 0xFFFFFFFFu);
+  launch_pose_score(grid_view(h), (unsigned int)entries, h->pts_cap, h->d_body, n_down, pose_of(*base), poses_dev, n_poses, r_max, h->cfg.plane_threshold,
+                    h->psc.d_part, scores_dev, res_dev, h->stream);
+}
+}  // namespace
+
+int lii_pose_score_dev(lii_handle h, const lii_state* base, const double* poses_dev, int32_t n_poses, struct lii_pose_score* scores_dev, float* res_dev) {
+  int n_down = 0, r_max = 0;
+  const int rc = pose_score_begin(h, "lii_pose_score_dev", base, poses_dev, n_poses, scores_dev, &n_down, &r_max);
+  if (rc != LII_OK) return rc;
+  HIPCHK(h, h->psc.d_part.at_least(lii::pose_score_partials(n_down, n_poses)));
+  pose_score_launch(h, base, poses_dev, n_poses, n_down, r_max, reinterpret_cast<lii::ScorePartial*>(scores_dev), res_dev);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+
+int lii_pose_score(lii_handle h, const lii_state* base, const double* poses, int32_t n_poses, struct lii_pose_score* scores, float* res) {
+  int n_down = 0, r_max = 0;
+  int rc = pose_score_begin(h, "lii_pose_score", base, poses, n_poses, scores, &n_down, &r_max);
+  if (rc != LII_OK) return rc;
+  // a chunk of poses: at most kPairsMax (pose, point) pairs - the staging stays bounded whatever n_poses is
+  auto& S = h->psc;
+  const size_t N = size_t(n_down);
+  const size_t chunk = std::min<size_t>(size_t(n_poses), std::max<size_t>(lii_context::PoseScore::kPairsMax / N, 1));
+  HIPCHK(h, S.d_part.at_least(lii::pose_score_partials(n_down, int(chunk))));
+  HIPCHK(h, S.d_poses.at_least(12 * chunk));
+  HIPCHK(h, S.h_poses.at_least(12 * chunk, hipHostMallocDefault));
+  HIPCHK(h, S.d_scores.at_least(chunk));
+  HIPCHK(h, S.h_scores.at_least(chunk, hipHostMallocDefault));
+  if (res) {
+    HIPCHK(h, S.d_res.at_least(chunk * N));
+    HIPCHK(h, S.h_res.at_least(chunk * N, hipHostMallocDefault));
+  }
+  const int* perm = nullptr;  // res rows come out in the order lii_scan_download(1) uses, as lii_neighbors_download's do
+  if (res) { rc = pcl_order(h, &perm); if (rc != LII_OK) return rc; }
+  hipStream_t s = h->stream;
+  for (size_t at = 0; at < size_t(n_poses); at += chunk) {
+    const size_t m = std::min(chunk, size_t(n_poses) - at);
+    std::memcpy(S.h_poses.get(), poses + 12 * at, sizeof(double) * 12 * m);
+    HIPCHK(h, hipMemcpyAsync(S.d_poses, S.h_poses, sizeof(double) * 12 * m, hipMemcpyHostToDevice, s));
+    pose_score_launch(h, base, S.d_poses, int(m), n_down, r_max, S.d_scores, res ? S.d_res.get() : nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(S.h_scores, S.d_scores, sizeof(lii::ScorePartial) * m, hipMemcpyDeviceToHost, s));
+    if (res) HIPCHK(h, hipMemcpyAsync(S.h_res, S.d_res, sizeof(float) * m * N, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    std::memcpy(scores + at, S.h_scores.get(), sizeof(struct lii_pose_score) * m);
+    if (res && !perm) std::memcpy(res + at * N, S.h_res.get(), sizeof(float) * m * N);
+    if (res && perm)
+      for (size_t k = 0; k < m; k++)
+        for (size_t i = 0; i < N; i++) res[(at + k) * N + i] = S.h_res[k * N + size_t(perm[i])];
+  }
+  return LII_OK;
+}
+
 // ---- the ball query (kernels: lii_query.hip, k_map_radius; scan and sort: lii_sort.hip)
 namespace {
 // The argument rules both forms share.  Nothing has been touched when this fails.

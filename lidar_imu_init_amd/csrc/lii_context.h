@@ -147,6 +147,18 @@ struct lii_context {
     DevBuf<unsigned long long> d_key_a, d_key_b;  // LII_RADIUS_SORTED: (query << 32 | d2 bits) per row, before and behind the sort
     DevBuf<unsigned int> d_slot_a, d_slot_b;      // ... and the row's slot in the point array
   } mr;
+  // lii_pose_score / lii_pose_score_dev (kernels: lii_score.hip).  Nothing here exists before the first such call; every buffer grows
+  // geometrically and goes with the handle.  d_part serves both forms; the others stage one chunk of poses of the host form.
+  struct PoseScore {
+    static constexpr size_t kPairsMax = size_t(1) << 22;  // (pose, point) pairs of one chunk of the host form: 16 MiB of res
+    DevBuf<lii::ScorePartial> d_part;       // one record per workgroup of k_pose_score
+    DevBuf<double> d_poses;                 // 12 per pose
+    DevBuf<lii::ScorePartial> d_scores;     // lii_pose_score's layout
+    DevBuf<float> d_res;
+    PinnedBuf<double> h_poses;
+    PinnedBuf<lii::ScorePartial> h_scores;
+    PinnedBuf<float> h_res;
+  } psc;
 
   // ---- scan
   DevBuf<float4> d_scan;   // raw / undistorted (x,y,z,t_ms)

@@ -65,6 +65,14 @@ void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const uns
                               long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s, int row_floats = 3);
 // row_floats (the three launches above): 3 - x, y, z a row of pts_out - or 4: the stored fourth word, the point's intensity, behind them
 // (lii_map_nearest_xyzi / lii_map_radius_xyzi; instantiations of their own)
+// pose scoring (lii_score.hip): the figures of one search pass (src/laserMapping.cpp:957-1020, all-true selection) at each of n_poses
+// poses - 12 doubles each in device memory: rot_end row-major, pos_end; the extrinsic is `base`'s - over the n points of `body`.
+// ScorePartial is lii_pose_score's layout: scores[k] receives pose k's figures, partials (pose_score_partials(n, n_poses) records of
+// scratch) one workgroup's share each; res: nullptr, or n_poses x n floats (res_last).  Two launches whatever n_poses is.
+struct ScorePartial { int n_full, effect_num; double total_residual; };
+size_t pose_score_partials(int n, int n_poses);
+void launch_pose_score(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const float4* body, int n, const PoseArg& base, const double* poses_dev,
+                       int n_poses, int r_max, double plane_thr, ScorePartial* partials, ScorePartial* scores, float* res, hipStream_t s);
 // (lii_sort.hip) counts -> offsets in place: io[i] = io[0] + ... + io[i - 1] over n words; and the sort of the sorted form: bits [0, end_bit)
 // of 64-bit keys with 32-bit values, stable.  *_temp_bytes: the temporary storage either needs for that size.
 size_t scan_i64_temp_bytes(size_t n);

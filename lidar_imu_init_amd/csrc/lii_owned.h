@@ -48,6 +48,9 @@ class DevBuf : public OwnedBuf<T, hipFree> {
   }
   // frees first, then allocates: the peak footprint of a growth is the larger of the two sizes, never their sum
   hipError_t grow(size_t n) { this->reset(); return alloc(n); }
+  // room for n elements, the contents not kept: nothing when it is there, else max(n, twice the size) - scratch that creeps upwards
+  // is released (hipFree waits for the device) a handful of times at most
+  hipError_t at_least(size_t n) { return n <= this->n_ ? hipSuccess : grow(n > 2 * this->n_ ? n : 2 * this->n_); }
 };
 
 template <class T>
@@ -57,6 +60,12 @@ class PinnedBuf : public OwnedBuf<T, hipHostFree> {
     if (this->p_) return hipErrorInvalidValue;
     void* p = nullptr;
     return this->adopt(hipHostMalloc(&p, n * sizeof(T), flags), p, n);
+  }
+  hipError_t at_least(size_t n, unsigned int flags) {  // as DevBuf::at_least
+    if (n <= this->n_) return hipSuccess;
+    const size_t want = n > 2 * this->n_ ? n : 2 * this->n_;
+    this->reset();
+    return alloc(want, flags);
   }
 };
 
