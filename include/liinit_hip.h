@@ -330,6 +330,61 @@ int lii_pose_score(lii_handle h, const lii_state* base, const double* poses /* n
                    int32_t n_poses, struct lii_pose_score* scores, float* res /* NULL, or n_poses x n_down */);
 int lii_pose_score_dev(lii_handle h, const lii_state* base, const double* poses_dev, int32_t n_poses,
                        struct lii_pose_score* scores_dev, float* res_dev /* 0 or device */);
+/* ---- candidate poses refined against the map in one call: the step behind the ranking.  For pose k the iterated update of
+ * src/laserMapping.cpp:957-1134 in LO mode (imu_en = false, :1063-1066) on the six pose states, `updates` times in a row, at the state
+ * `base` with rot_end / pos_end replaced by pose k (the extrinsic is base's).  ONE UPDATE starts with state_propagat = the pose it finds,
+ * P = the 6 x 6 pose covariance it finds, nearest_search_en = true, rematch_num = 0, and runs up to max_iterations iterations:
+ *   pass      every point of the handle's current down-sampled cloud.  Searching: pointBodyToWorld with the registration path's rounding, the
+ *             exact 5-NN with d2 <= max_match_dist2 inclusive, the test of :981-984, an all-true selection.  Not searching: the lists and the
+ *             sticky selection of this pose's last pass.  Then esti_plane at plane_threshold, pd2 and the gate s > 0.9,
+ *             h = [[p_I]x R^T n, n] with p_I = R_LI p + T_LI, z = -pd2, R^-1 = lii_config::laser_point_cov_inv for every point.
+ *   solve     G = R^-1 sum h^T h, g = R^-1 sum h^T z, K_1 = (G + P^-1)^-1, v = state_propagat [-] state (Log(R^T R_prop), p_prop - p),
+ *             delta = K_1 g + v - K_1 G v, R <- R Exp(delta_rot), p += delta_p  (:1081-1087)
+ *   schedule  converged iff |delta_rot| 57.3 < 0.01 and |delta_p| 100 < 0.015; the next pass searches iff converged or (rematch_num == 0 and
+ *             iterCount == max_iterations - 2), and rematch_num counts those; with rematch_num >= 2 or iterCount == max_iterations - 1 the
+ *             update ends with P <- (I - K_1 G) P  (:1093-1133), stored as its symmetric part 0.5 (P + P^T) - as lii_iekf_update stores
+ *             its posterior: the next update's gain relies on P = P^T, and the cov of a record is exactly symmetric, so it is a prior
+ *             this call accepts again (a coarse grid, then a fine one around the winner).
+ * prior_cov: the 6 x 6 covariance (row-major) every pose starts from; NULL: the pose block cov[0:6, 0:6] of base.  Where that block is
+ * uncorrelated with the rest of base->cov (lii_state's initial covariance is the identity) this IS lii_iekf_update(imu_en = 0) on the
+ * pose, `updates` times with state_propagat = the state each call finds - and that update leaves the other 18 states alone.  The same
+ * definition, the symmetric posterior included; not the same arithmetic (a 6 x 6 elimination here, a 24-state solve there): the two
+ * agree in every iteration count and to rounding in the pose (below 1e-9 m on the suite's cases), not bit for bit.
+ * An observer, like lii_pose_score: it reads the map and the down-sampled cloud and writes NOTHING of the registration state - neighbour
+ * lists, sticky selection, cached planes, point-noise weights, lii_last_unfinished_queries and the publish buffers stay as they were.
+ * Ends a pre-armed launch and joins a map update in flight first.  updates x max_iterations rounds of two launches are enqueued at
+ * once on the handle's stream - no wait in between; a pose whose last update has ended costs a round one load per workgroup.  The host
+ * form stages poses and records through pinned memory and waits once; the _dev form only enqueues (it waits only where the size of the
+ * down-sampled cloud is still on the device, and where the call needs more scratch than any call before it).  Scratch of the handle's,
+ * created by the first call and kept until lii_destroy: 33 bytes per (pose, point) pair of the largest call (a plane and a selection
+ * flag), 232 bytes per 64 pairs, 512 bytes per pose - 18.4 MiB at 256 poses x 2 048 points, 147 MiB at the limit of 2^22 pairs.
+ * DETERMINISTIC: pose k's record is the same bits refined alone or as any member of any batch, in one call or another, through either
+ * form (fixed-order sums in double, no atomics; a pose reads and writes only its own records).
+ * LII_ERR_STATE: no map, no down-sampled cloud, inside lii_scan_job::while_waiting, a communicator of more than one rank attached,
+ * lii_point_noise_set's model on (the refinement weighs every point alike; it does not silently differ from the update the caller
+ * would otherwise run).
+ * LII_ERR_INVALID: NULL arguments (prior_cov excepted), n_poses < 1 or > 65 536, max_iterations outside 1 .. 16, updates outside 1 .. 8,
+ * n_poses * n_down > 2^22, a prior - prior_cov, or base's pose block - that is not finite, not symmetric or not positive definite.
+ * Nothing is written to `out` by a refused call.
+ * A pose with a NaN or Inf entry is returned as given - pose, the prior as cov, the counts 0 - with LII_REFINE_BAD_POSE.  One that puts
+ * every point outside the grid selects nothing: each update ends after two iterations exactly where it started, P unchanged.  Neither
+ * disturbs its neighbours in the batch. */
+enum { LII_REFINE_CONVERGED = 1, LII_REFINE_BAD_POSE = 2 };
+/* (a struct tag only, as lii_pose_score) */
+struct lii_pose_refined {      /* 408 bytes */
+  double  pose[12];            /* rot_end row-major, pos_end - after the last update */
+  double  cov[36];             /* the 6x6 pose covariance after the last update, row-major */
+  double  total_residual;      /* of the last pass executed: sum of |pd2| over its selected points */
+  int32_t effect_num;          /* of the last pass executed */
+  int32_t iterations;          /* executed, summed over the updates */
+  int32_t searches;            /* search passes executed, summed */
+  int32_t flags;               /* LII_REFINE_CONVERGED: the last update ended on rematch_num >= 2, not on the iteration limit;
+                                  LII_REFINE_BAD_POSE: a NaN / Inf entry - pose and cov returned as given, the counts 0 */
+};
+int lii_pose_refine(lii_handle h, const lii_state* base, const double* prior_cov /* NULL or 36 */, const double* poses /* n_poses x 12 */,
+                    int32_t n_poses, int32_t max_iterations, int32_t updates, struct lii_pose_refined* out);
+int lii_pose_refine_dev(lii_handle h, const lii_state* base, const double* prior_cov /* NULL or 36, host memory */, const double* poses_dev,
+                        int32_t n_poses, int32_t max_iterations, int32_t updates, struct lii_pose_refined* out_dev);
 /* ---- edits and queries by point and box: the rest of what a holder of the tree can do (include/ikd-Tree/ikd_Tree.h:165-187).
  * lii_map_delete_points <- ikdtree.Delete_Points(PointToDel)  (include/ikd-Tree/ikd_Tree.cpp:479-498, Delete_by_point :672-719,
  *                       same_point :1269-1271).  Every listed point (float xyz every stride_bytes, as for lii_map_build) takes ONE live

@@ -104,6 +104,10 @@ class lii_pose_score(C.Structure):
 
 
 POSE_SCORE_DTYPE = np.dtype([("n_full", "<i4"), ("effect_num", "<i4"), ("total_residual", "<f8")])  # struct lii_pose_score as a numpy record
+# struct lii_pose_refined as a numpy record (408 bytes)
+POSE_REFINED_DTYPE = np.dtype([("pose", "<f8", (12,)), ("cov", "<f8", (6, 6)), ("total_residual", "<f8"), ("effect_num", "<i4"),
+                               ("iterations", "<i4"), ("searches", "<i4"), ("flags", "<i4")])
+LII_REFINE_CONVERGED, LII_REFINE_BAD_POSE = 1, 2
 
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
@@ -197,6 +201,8 @@ _DECLS = {
     "lii_map_nearest_xyzi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_pose_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "lii_pose_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lii_pose_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lii_pose_refine_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lii_map_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -862,15 +868,58 @@ class Registrar:
         self._check(self.L.lii_pose_score_dev(self.h, _ptr(base.pod), _dev_address(poses_dev), int(n_poses), _dev_address(scores_dev),
                                               _dev_address(res_dev)))
 
-    def relocalize(self, base: State, poses, top=3, max_iterations=4, updates=2):
+    @staticmethod
+    def _prior_ptr(prior_cov):
+        if prior_cov is None:
+            return None, None
+        pc = np.ascontiguousarray(np.asarray(prior_cov, np.float64).reshape(6, 6))
+        return pc, _ptr(pc)
+
+    def pose_refine(self, base: State, poses, max_iterations=4, updates=2, prior_cov=None):
+        """lii_pose_refine: the iterated update in LO mode (src/laserMapping.cpp:957-1134, imu_en = False) on the six pose states, `updates`
+        times in a row from each of the K poses - `poses` as pose_score takes them; the extrinsic is base's - in ONE call: every round is
+        enqueued at once, one wait.  prior_cov: the 6 x 6 covariance every pose starts from; None: the pose block of base.cov.  Returns a
+        structured array (POSE_REFINED_DTYPE): pose (12), cov (6, 6), total_residual, effect_num, iterations, searches, flags.  Leaves the
+        neighbour lists, the selection and everything else of a registration alone."""
+        P = poses_array(poses)
+        K = len(P)
+        out = np.zeros(K, POSE_REFINED_DTYPE)
+        pc, pc_ptr = self._prior_ptr(prior_cov)
+        self._check(self.L.lii_pose_refine(self.h, _ptr(base.pod), pc_ptr, _ptr(P) if K else None, K, int(max_iterations), int(updates),
+                                           _ptr(out) if K else None))
+        return out
+
+    def pose_refine_dev(self, base: State, poses_dev, n_poses, out_dev, max_iterations=4, updates=2, prior_cov=None):
+        """pose_refine with poses and records (408-byte struct lii_pose_refined) in device memory the caller owns - raw addresses or
+        objects with __cuda_array_interface__; prior_cov stays host memory.  Enqueued on the handle's stream; synchronize() - or any
+        synchronous call - orders it."""
+        pc, pc_ptr = self._prior_ptr(prior_cov)
+        self._check(self.L.lii_pose_refine_dev(self.h, _ptr(base.pod), pc_ptr, _dev_address(poses_dev), int(n_poses), int(max_iterations),
+                                               int(updates), _dev_address(out_dev)))
+
+    def relocalize(self, base: State, poses, top=3, max_iterations=4, updates=2, batched=False):
         """Re-localisation over candidate poses: pose_score ranks them (rank_poses: effect_num descending, mean residual ascending, index),
         the `top` best each start `updates` consecutive iekf_update calls in LO mode (imu_en = False) on a copy of `base` with that pose,
         and the state whose last update selected the most points wins (the earlier rank on a tie).  Returns (state, info) with info =
-        dict(order, n_full, effect_num, total_residual, tried = [(pose index, effect_num after its updates)], best = pose index)."""
+        dict(order, n_full, effect_num, total_residual, tried = [(pose index, effect_num after its updates)], best = pose index).
+        batched=True: the `top` best go through ONE pose_refine call instead - the registration state of the handle is left alone - and
+        the returned state is `base` with the winning pose and its pose-covariance block."""
         P = poses_array(poses)
         n_full, effect, total = self.pose_score(base, P)
         order = rank_poses(effect, total)
         best, best_eff, best_k, tried = None, -1, -1, []
+        if batched:
+            cand = order[:max(int(top), 1)]
+            rec = self.pose_refine(base, P[cand], max_iterations=max_iterations, updates=max(int(updates), 1))
+            for k, r in zip(cand, rec):
+                tried.append((int(k), int(r["effect_num"])))
+                if r["effect_num"] > best_eff:
+                    best_eff, best_k, win = int(r["effect_num"]), int(k), r
+            best = base.copy()
+            best.rot_end[:] = win["pose"][:9].reshape(3, 3)
+            best.pos_end[:] = win["pose"][9:]
+            best.cov[:6, :6] = win["cov"]
+            return best, dict(order=order, n_full=n_full, effect_num=effect, total_residual=total, tried=tried, best=best_k)
         for k in order[:max(int(top), 1)]:
             st = base.copy()
             st.rot_end[:] = P[k, :9].reshape(3, 3)

@@ -1272,6 +1272,106 @@ int lii_pose_score(lii_handle h, const lii_state* base, const double* poses, int
   return LII_OK;
 }
 
+// ---- pose refinement (kernels: lii_refine.hip): the iterated update on the six pose states at K candidate poses, all rounds enqueued at once
+namespace {
+static_assert(sizeof(struct lii_pose_refined) == sizeof(lii::RefineRecord) && sizeof(struct lii_pose_refined) == 408, "lii_pose_refined is the kernels' record");
+static_assert(int(LII_REFINE_CONVERGED) == lii::kRefineConverged && int(LII_REFINE_BAD_POSE) == lii::kRefineBadPose, "the flags of lii_pose_refined");
+// A prior the update can start from: finite, symmetric, positive definite (Cholesky: every pivot > 0).
+bool prior_ok(const double* P) {
+  for (int i = 0; i < 36; i++)
+    if (!std::isfinite(P[i])) return false;
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < i; j++)
+      if (P[6 * i + j] != P[6 * j + i]) return false;
+  double L[36];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j <= i; j++) {
+      double s = P[6 * i + j];
+      for (int k = 0; k < j; k++) s -= L[6 * i + k] * L[6 * j + k];
+      if (i == j) {
+        if (!(s > 0.0)) return false;
+        L[6 * i + i] = std::sqrt(s);
+      } else {
+        L[6 * i + j] = s / L[6 * j + j];
+      }
+    }
+  return true;
+}
+// What both forms check and settle before a launch (nothing has been written when this fails).  The order of refusals: what the arguments
+// alone decide (LII_ERR_INVALID), then everything lii_pose_score refuses, in its order, then the noise model, then the pair limit.
+int pose_refine_begin(lii_handle h, const char* who, const lii_state* base, const double* prior_cov, const void* poses, int32_t n_poses, int32_t max_iterations,
+                      int32_t updates, const void* out, lii::RefinePrior* prior, int* n_down, int* r_max) {
+  if (!h) return LII_ERR_INVALID;
+  if (!base || !poses || !out) return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments (base, poses, out)");
+  if (n_poses < 1 || n_poses > kPoseScoreMax) return fail(h, LII_ERR_INVALID, std::string(who) + ": n_poses must be 1 .. 65536");
+  if (max_iterations < 1 || max_iterations > 16) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_iterations must be 1 .. 16");
+  if (updates < 1 || updates > 8) return fail(h, LII_ERR_INVALID, std::string(who) + ": updates must be 1 .. 8");
+  if (prior_cov) {
+    std::memcpy(prior->P, prior_cov, sizeof(prior->P));
+  } else {
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) prior->P[6 * i + j] = base->cov[24 * i + j];
+  }
+  if (!prior_ok(prior->P))
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": the prior (prior_cov, or the pose block of base->cov) must be finite, symmetric and positive definite");
+  // from here on lii_pose_score's own order of refusals, then the one this call adds
+  const int rc = pose_score_begin(h, who, base, poses, n_poses, out, n_down, r_max);
+  if (rc != LII_OK) return rc;
+  if (h->noise.model != 0)
+    return fail(h, LII_ERR_STATE, std::string(who) + ": the per-point noise model is on (lii_point_noise_set); the refinement weighs every point laser_point_cov_inv");
+  if (size_t(n_poses) * size_t(*n_down) > lii_context::PoseRefine::kPairsMax)
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": n_poses * n_down must not exceed 2^22");
+  return LII_OK;
+}
+int pose_refine_launch(lii_handle h, const lii_state* base, const lii::RefinePrior& prior, const double* poses_dev, int n_poses, int max_iterations, int updates,
+                       int n_down, int r_max, lii::RefineRecord* records_dev) {
+  auto& S = h->prf;
+  const size_t pairs = size_t(n_poses) * size_t(n_down);
+  HIPCHK(h, S.d_ctrl.at_least(size_t(n_poses)));
+  HIPCHK(h, S.d_planes.at_least(4 * pairs));
+  HIPCHK(h, S.d_flags.at_least(pairs));
+  HIPCHK(h, S.d_part.at_least(lii::pose_refine_partials(n_down, n_poses)));
+  const size_t entries = std::min<size_t>(h->cells_cap_blocks * 512, 0xFFFFFFFFu);
+  const lii::RefineScratch sc = {S.d_ctrl, S.d_planes, S.d_flags, S.d_part};
+  launch_pose_refine(grid_view(h), (unsigned int)entries, h->pts_cap, h->d_body, n_down, pose_of(*base), prior, poses_dev, n_poses, max_iterations, updates, r_max,
+                     h->cfg.plane_threshold, double(h->cfg.laser_point_cov_inv), sc, records_dev, h->stream);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+}  // namespace
+
+int lii_pose_refine_dev(lii_handle h, const lii_state* base, const double* prior_cov, const double* poses_dev, int32_t n_poses, int32_t max_iterations,
+                        int32_t updates, struct lii_pose_refined* out_dev) {
+  int n_down = 0, r_max = 0;
+  lii::RefinePrior prior;
+  const int rc = pose_refine_begin(h, "lii_pose_refine_dev", base, prior_cov, poses_dev, n_poses, max_iterations, updates, out_dev, &prior, &n_down, &r_max);
+  if (rc != LII_OK) return rc;
+  return pose_refine_launch(h, base, prior, poses_dev, n_poses, max_iterations, updates, n_down, r_max, reinterpret_cast<lii::RefineRecord*>(out_dev));
+}
+
+int lii_pose_refine(lii_handle h, const lii_state* base, const double* prior_cov, const double* poses, int32_t n_poses, int32_t max_iterations, int32_t updates,
+                    struct lii_pose_refined* out) {
+  int n_down = 0, r_max = 0;
+  lii::RefinePrior prior;
+  int rc = pose_refine_begin(h, "lii_pose_refine", base, prior_cov, poses, n_poses, max_iterations, updates, out, &prior, &n_down, &r_max);
+  if (rc != LII_OK) return rc;
+  auto& S = h->prf;
+  const size_t K = size_t(n_poses);
+  HIPCHK(h, S.d_poses.at_least(12 * K));
+  HIPCHK(h, S.h_poses.at_least(12 * K, hipHostMallocDefault));
+  HIPCHK(h, S.d_records.at_least(K));
+  HIPCHK(h, S.h_records.at_least(K, hipHostMallocDefault));
+  hipStream_t s = h->stream;
+  std::memcpy(S.h_poses.get(), poses, sizeof(double) * 12 * K);
+  HIPCHK(h, hipMemcpyAsync(S.d_poses, S.h_poses, sizeof(double) * 12 * K, hipMemcpyHostToDevice, s));
+  rc = pose_refine_launch(h, base, prior, S.d_poses, n_poses, max_iterations, updates, n_down, r_max, S.d_records);
+  if (rc != LII_OK) return rc;
+  HIPCHK(h, hipMemcpyAsync(S.h_records, S.d_records, sizeof(lii::RefineRecord) * K, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  std::memcpy(out, S.h_records.get(), sizeof(struct lii_pose_refined) * K);
+  return LII_OK;
+}
+
 // ---- the ball query (kernels: lii_query.hip, k_map_radius; scan and sort: lii_sort.hip)
 namespace {
 // The argument rules both forms share.  Nothing has been touched when this fails.

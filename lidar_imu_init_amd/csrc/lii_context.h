@@ -159,6 +159,19 @@ struct lii_context {
     PinnedBuf<lii::ScorePartial> h_scores;
     PinnedBuf<float> h_res;
   } psc;
+  // lii_pose_refine / lii_pose_refine_dev (kernels: lii_refine.hip).  Nothing here exists before the first such call; every buffer grows
+  // geometrically and goes with the handle.  The first four serve both forms; the others stage the poses and records of the host form.
+  struct PoseRefine {
+    static constexpr size_t kPairsMax = size_t(1) << 22;  // (pose, point) pairs of one call: 33 bytes of scratch each - 132 MiB at the limit
+    DevBuf<lii::RefineCtrl> d_ctrl;         // one record per pose
+    DevBuf<double> d_planes;                // 4 per pair
+    DevBuf<unsigned char> d_flags;          // the pair's selection
+    DevBuf<lii::RefinePartial> d_part;      // one record per workgroup of k_refine_pass
+    DevBuf<double> d_poses;                 // 12 per pose
+    DevBuf<lii::RefineRecord> d_records;    // lii_pose_refined's layout
+    PinnedBuf<double> h_poses;
+    PinnedBuf<lii::RefineRecord> h_records;
+  } prf;
 
   // ---- scan
   DevBuf<float4> d_scan;   // raw / undistorted (x,y,z,t_ms)

@@ -70,9 +70,35 @@ void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const uns
 // ScorePartial is lii_pose_score's layout: scores[k] receives pose k's figures, partials (pose_score_partials(n, n_poses) records of
 // scratch) one workgroup's share each; res: nullptr, or n_poses x n floats (res_last).  Two launches whatever n_poses is.
 struct ScorePartial { int n_full, effect_num; double total_residual; };
+// Workgroups up to which four wavefronts search a workgroup's 64 pairs, one above it (launch_pose_score; launch_pose_refine takes it over
+// unmeasured): an estimate (two wavefronts per SIMD) between measured points of k_pose_score at 512 (four win) and 8 192 (one wins) -
+// DESIGN.md section 3.4i; the bits do not depend on it.
+constexpr int kSmallBatchBlocks = 2048;
 size_t pose_score_partials(int n, int n_poses);
 void launch_pose_score(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const float4* body, int n, const PoseArg& base, const double* poses_dev,
                        int n_poses, int r_max, double plane_thr, ScorePartial* partials, ScorePartial* scores, float* res, hipStream_t s);
+// pose refinement (lii_refine.hip): the iterated update of src/laserMapping.cpp:957-1134 in LO mode on the six pose states, `updates` times
+// in a row from each of n_poses poses (laid out as for launch_pose_score) over the n points of `body`; P starts at `prior` for every pose.
+// updates x max_iterations rounds of two launches, all enqueued here; records[k] (lii_pose_refined's layout) is written by the round in
+// which pose k's last update ends.  The scratch belongs to the call while it runs: a control record per pose, a plane and a selection
+// flag per (pose, point) pair, one partial per workgroup of a pass (pose_refine_partials(n, n_poses)).
+constexpr int kRefineConverged = 1, kRefineBadPose = 2;  // LII_REFINE_CONVERGED, LII_REFINE_BAD_POSE
+struct RefineRecord { double pose[12], cov[36], total_residual; int effect_num, iterations, searches, flags; };
+struct RefinePrior { double P[36]; };
+struct RefineCtrl {
+  double R[9], p[3];    // the pose now
+  double Rp[9], pp[3];  // state_propagat of the update under way
+  double P[36];         // the covariance that update started with
+  int search, done;     // the next pass searches; the last update has ended (or the pose was refused)
+  int rem, it, upd;     // rematch_num and iterCount of the update under way; updates ended
+  int iterations, searches, pad;
+};
+struct RefinePartial { double s[28]; int effect_num, pad; };  // 21 sums of h^T h (upper triangle, row by row), 6 of h^T z, sum |pd2|
+struct RefineScratch { RefineCtrl* ctrl; double* planes; unsigned char* flags; RefinePartial* partials; };
+size_t pose_refine_partials(int n, int n_poses);
+void launch_pose_refine(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const float4* body, int n, const PoseArg& base, const RefinePrior& prior,
+                        const double* poses_dev, int n_poses, int max_iterations, int updates, int r_max, double plane_thr, double rinv, const RefineScratch& sc,
+                        RefineRecord* records, hipStream_t s);
 // (lii_sort.hip) counts -> offsets in place: io[i] = io[0] + ... + io[i - 1] over n words; and the sort of the sorted form: bits [0, end_bit)
 // of 64-bit keys with 32-bit values, stable.  *_temp_bytes: the temporary storage either needs for that size.
 size_t scan_i64_temp_bytes(size_t n);

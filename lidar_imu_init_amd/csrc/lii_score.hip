@@ -25,8 +25,7 @@ namespace lii {
 namespace {
 
 constexpr int kScorePairs = 64;  // (pose, point) pairs of a workgroup: one per lane of the wavefront that fits
-constexpr int kSmallBatchBlocks = 2048;  // workgroups up to which four wavefronts search a workgroup's pairs: an estimate (two wavefronts per SIMD) between
-                                         // measured points at 512 (four win) and 8 192 (one wins) - DESIGN.md section 3.4i; the bits do not depend on it
+// (kSmallBatchBlocks - the launch size up to which four wavefronts search a workgroup's pairs: lii_launch.h, shared with lii_refine.hip)
 
 struct ScoreShared {
   float4 nb[kScorePairs][kMatch];  // the list of pair j: xyz, w = d2
