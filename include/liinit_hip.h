@@ -1178,6 +1178,48 @@ int lii_li_init_resident_fetch(lii_handle h, int32_t which, lii_calib_state* imu
  * launch runs, the result comes back.  No buffers uploaded: LII_ERR_STATE. */
 int lii_calib_solve_stage_dev(lii_handle h, int32_t stage, lii_calib_result* inout);
 
+/* LI_Initialization on K sub-ranges ("windows") of one accumulation in one call.  The reference calibrates once per accumulation
+ * (include/LI_init/LI_init.cpp:586-632, called from src/laserMapping.cpp:1190-1198 when data_sufficiency_assess says so); whether
+ * that extrinsic, bias or time offset is stable it cannot say.  Calibrating on prefixes (what the result would have been had the
+ * initialisation fired at frame n) and on sliding windows of the same accumulation answers that, and K independent windows fill
+ * the K workgroups per launch that the single call's one-workgroup launches leave idle.
+ * DEFINITION.  out[w] is what lii_li_init_resident returns for a job with imu = job->imu + imu_begin, n_imu = imu_count,
+ * lidar = job->lidar + lidar_begin, n_lidar = lidar_count, the window's move_start_time and the job's interpolate, orig_odom_freq
+ * and cut_frame_num: the same bits in the result and in every report field but launches / host_waits, which are the whole call's.
+ * The sequences go up once; a fixed number of launches follows, whatever K is, window w being blockIdx.y of each; the host waits once.
+ * A window reads and writes only areas of its own, so a record does not depend on K or on the windows beside it.
+ * REFUSALS FOUND BY THE DATA (where the single call returns LII_ERR_INVALID for a reason only the data decides) are the window's
+ * `status`; the call returns LII_OK and the other windows are unaffected.
+ * REFUSED ON THE HOST, before anything is enqueued, LII_ERR_INVALID: a NULL argument; a wrong job->struct_size or an out_stride
+ * other than sizeof(lii_li_init_window_result); what lii_li_init_resident refuses in the job's scalars; n_windows < 1 or > 4096; a
+ * range outside the job's sequences; aligned form: imu_begin != lidar_begin, imu_count != lidar_count or a count < 200; raw form:
+ * imu_count < 6 or lidar_count < 1.  LII_ERR_CAPACITY: the call's device scratch would exceed 4 GiB, where scratch =
+ *   176 (n_imu + n_lidar) + 24 K + K (904 + 8 (116 c + c / 2 + 8) + [raw form] 32 r)   bytes,
+ * c = the longest lidar_count, r = the longest imu_count (904 bytes hold a window's control and result block).  From inside
+ * lii_scan_job::while_waiting: LII_ERR_STATE.  Like every entry point it ends a pre-armed launch of the handle first.
+ * OBSERVER.  The call touches neither the buffers lii_calib_eval / lii_calib_solve_stage* read nor what lii_li_init_resident_fetch
+ * serves.  It allocates only when a buffer of an earlier call is too small (lii_li_init_windows_scratch counts). */
+typedef struct lii_li_init_window {      /* one sub-range of the job's sequences */
+  int32_t imu_begin, imu_count;          /* aligned form: must equal lidar_begin, lidar_count */
+  int32_t lidar_begin, lidar_count;
+  double  move_start_time;               /* raw form only */
+} lii_li_init_window;
+
+enum { LII_WIN_OK = 0, LII_WIN_FILTER61 = 1, LII_WIN_ALIGNED200 = 2, LII_WIN_RAW6 = 3, LII_WIN_NO_OVERLAP = 4 };
+
+typedef struct lii_li_init_window_result {
+  int32_t status;                        /* LII_WIN_*; everything below is zero unless LII_WIN_OK */
+  int32_t pad;
+  lii_calib_result res;
+  lii_li_init_report rep;                /* struct_size filled in; launches / host_waits are the whole call's */
+} lii_li_init_window_result;
+
+int lii_li_init_windows(lii_handle h, const lii_li_init_job* job, const lii_li_init_window* windows, int32_t n_windows,
+                        lii_li_init_window_result* out, uint32_t out_stride /* sizeof the record */);
+/* The device scratch lii_li_init_windows holds on this handle, in bytes, and the allocations (device and pinned) its calls have
+ * made so far: a call no larger than an earlier one leaves both unchanged.  Either pointer may be NULL. */
+int lii_li_init_windows_scratch(lii_handle h, uint64_t* bytes, int64_t* allocations);
+
 /* ---------------------------------------------------------------- multi-GPU (points of one scan sharded across ranks)
  * One process per GPU.  Rank 0 creates an id, the caller ships the 128 bytes to the other ranks (e.g.
  * torch.distributed broadcast), every rank calls lii_comm_init with the SAME state / options per scan; afterwards

@@ -165,6 +165,27 @@ class lii_li_init_report(C.Structure):
                 ("params", (C.c_double * 24) * 3)]
 
 
+class lii_li_init_window(C.Structure):
+    _fields_ = [("imu_begin", C.c_int32), ("imu_count", C.c_int32), ("lidar_begin", C.c_int32), ("lidar_count", C.c_int32),
+                ("move_start_time", C.c_double)]
+
+
+class lii_li_init_window_result(C.Structure):
+    _fields_ = [("status", C.c_int32), ("pad", C.c_int32), ("res", lii_calib_result), ("rep", lii_li_init_report)]
+
+
+LII_WIN_OK, LII_WIN_FILTER61, LII_WIN_ALIGNED200, LII_WIN_RAW6, LII_WIN_NO_OVERLAP = 0, 1, 2, 3, 4
+# the windows of Registrar.li_init_windows as numpy sees them: lii_li_init_window, field for field
+LI_INIT_WINDOW_IN_DTYPE = np.dtype([("imu_begin", "<i4"), ("imu_count", "<i4"), ("lidar_begin", "<i4"), ("lidar_count", "<i4"),
+                                    ("move_start_time", "<f8")])
+# one record of Registrar.li_init_windows: a window's status (LII_WIN_*), its calibration and what its report says of the run
+LI_INIT_WINDOW_DTYPE = np.dtype([("status", "<i4"), ("R_LI", "<f8", (3, 3)), ("T_LI", "<f8", (3,)), ("gyro_bias", "<f8", (3,)),
+                                 ("acc_bias", "<f8", (3,)), ("grav_L0", "<f8", (3,)), ("time_lag_1", "<f8"), ("time_lag_2", "<f8"),
+                                 ("total_time_lag", "<f8"), ("iterations", "<i4", (3,)), ("final_cost", "<f8", (3,)),
+                                 ("termination", "<i4", (3,)), ("n_aligned", "<i4"), ("n_stage12", "<i4"), ("n_stage3", "<i4"),
+                                 ("lag_samples", "<i4")])
+
+
 _DECLS = {
     # name: (restype, argtypes)
     "lii_abi_version": (C.c_int, []),
@@ -287,6 +308,8 @@ _DECLS = {
                                        C.POINTER(lii_li_init_report)]),
     "lii_li_init_resident_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "lii_calib_solve_stage_dev": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(lii_calib_result)]),
+    "lii_li_init_windows": (C.c_int, [C.c_void_p, C.POINTER(lii_li_init_job), C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32]),
+    "lii_li_init_windows_scratch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "lii_comm_unique_id": (C.c_int, [C.c_void_p]),
     "lii_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "lii_comm_init_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
@@ -523,6 +546,107 @@ def rank_poses(effect_num, total_residual):
     tot = np.asarray(total_residual, np.float64)
     mean = np.where(eff > 0, tot / np.maximum(eff, 1), np.inf)
     return np.lexsort((np.arange(len(eff)), mean, -eff))
+
+
+# ---------------------------------------------------------------------- windows of an accumulation (Registrar.li_init_windows)
+def li_init_window_array(windows):
+    """Windows as an array of LI_INIT_WINDOW_IN_DTYPE: such an array as it is; rows (begin, count) - the aligned form, both
+    sequences - or (imu_begin, imu_count, lidar_begin, lidar_count[, move_start_time])."""
+    if isinstance(windows, np.ndarray) and windows.dtype == LI_INIT_WINDOW_IN_DTYPE:
+        return np.ascontiguousarray(windows)
+    rows = [tuple(w) for w in windows]
+    out = np.zeros(len(rows), LI_INIT_WINDOW_IN_DTYPE)
+    for k, w in enumerate(rows):
+        if len(w) == 2:
+            w = (w[0], w[1], w[0], w[1], 0.0)
+        elif len(w) == 4:
+            w = w + (0.0,)
+        elif len(w) != 5:
+            raise ValueError("a window is (begin, count) or (imu_begin, imu_count, lidar_begin, lidar_count[, move_start_time])")
+        out[k] = w
+    return out
+
+
+def _imu_range(imu_t, t_from, t_to):
+    """[begin, end) of the IMU stamps in [t_from, t_to] (ascending stamps)"""
+    return int(np.searchsorted(imu_t, t_from, "left")), int(np.searchsorted(imu_t, t_to, "right"))
+
+
+def li_init_prefix_windows(lidar_t, imu_t=None, first=200, step=50, margin=0.0, move_start_time=0.0):
+    """The prefixes of an accumulation that the reference's loop (src/laserMapping.cpp:1190-1198) would have calibrated on had the
+    initialisation fired at frame n: LiDAR [0, n) for n = first, first + step, ... and the whole accumulation last.
+    imu_t = None: the aligned form (both sequences take the range; first >= 200).  Else the raw form: the IMU range of a window is
+    [0, e) with e behind the last IMU stamp not later than the window's last LiDAR stamp plus `margin`; every window carries
+    move_start_time.  Returns an array of LI_INIT_WINDOW_IN_DTYPE."""
+    lidar_t = np.asarray(lidar_t, np.float64)
+    n = len(lidar_t)
+    if step < 1 or first < 1:
+        raise ValueError("first and step must be positive")
+    if imu_t is None and first < 200:
+        raise ValueError("an aligned window holds 200 states or more")
+    if first > n:
+        raise ValueError("the accumulation is shorter than the first window")
+    counts = list(range(first, n + 1, step))
+    if counts[-1] != n:
+        counts.append(n)
+    out = np.zeros(len(counts), LI_INIT_WINDOW_IN_DTYPE)
+    out["lidar_count"] = counts
+    if imu_t is None:
+        out["imu_count"] = counts
+    else:
+        imu_t = np.asarray(imu_t, np.float64)
+        out["imu_count"] = [_imu_range(imu_t, -np.inf, lidar_t[c - 1] + margin)[1] for c in counts]
+        out["move_start_time"] = move_start_time
+    return out
+
+
+def li_init_sliding_windows(lidar_t, imu_t=None, length=400, step=100, margin=0.0):
+    """Windows of `length` LiDAR states every `step` states: LiDAR [b, b + length) for b = 0, step, ... while the window fits.
+    imu_t = None: the aligned form (length >= 200).  Else the raw form: the IMU range of a window holds the stamps from the window's
+    first LiDAR stamp minus `margin` to its last plus `margin`, and its move_start_time is its first LiDAR stamp (nothing of the
+    window is older than move_start_time - 3 s).  Returns an array of LI_INIT_WINDOW_IN_DTYPE."""
+    lidar_t = np.asarray(lidar_t, np.float64)
+    n = len(lidar_t)
+    if step < 1 or length < 1:
+        raise ValueError("length and step must be positive")
+    if imu_t is None and length < 200:
+        raise ValueError("an aligned window holds 200 states or more")
+    if length > n:
+        raise ValueError("the accumulation is shorter than one window")
+    begins = np.arange(0, n - length + 1, step)
+    out = np.zeros(len(begins), LI_INIT_WINDOW_IN_DTYPE)
+    out["lidar_begin"], out["lidar_count"] = begins, length
+    if imu_t is None:
+        out["imu_begin"], out["imu_count"] = begins, length
+    else:
+        imu_t = np.asarray(imu_t, np.float64)
+        for k, b in enumerate(begins):
+            lo, hi = _imu_range(imu_t, lidar_t[b] - margin, lidar_t[b + length - 1] + margin)
+            out[k]["imu_begin"], out[k]["imu_count"] = lo, hi - lo
+            out[k]["move_start_time"] = lidar_t[b]
+    return out
+
+
+def li_init_spread(records):
+    """How far the calibrations of Registrar.li_init_windows lie apart.  Over the LII_WIN_OK records, against the last of them:
+    the rotation angle of R_LI_w R_LI_last^T in degrees, |T_LI_w - T_LI_last| and total_time_lag_w - total_time_lag_last per
+    window, and the mean and standard deviation of each.  Returns a dict: index (the OK records' positions), rot_deg, dT, dlag
+    (arrays, one entry per OK record, the last one zero) and rot_deg_mean / _std, dT_mean / _std, dlag_mean / _std."""
+    records = np.asarray(records)
+    idx = np.flatnonzero(records["status"] == LII_WIN_OK)
+    if len(idx) == 0:
+        raise ValueError("no window came back LII_WIN_OK")
+    ok = records[idx]
+    last = ok[-1]
+    D = ok["R_LI"] @ last["R_LI"].T
+    # the angle from both the skew part and the trace: exact near 0 and near 180 degrees
+    skew = 0.5 * np.stack([D[:, 2, 1] - D[:, 1, 2], D[:, 0, 2] - D[:, 2, 0], D[:, 1, 0] - D[:, 0, 1]], axis=1)
+    rot = np.degrees(np.arctan2(np.linalg.norm(skew, axis=1), 0.5 * (np.trace(D, axis1=1, axis2=2) - 1.0)))
+    out = dict(index=idx, rot_deg=rot, dT=np.linalg.norm(ok["T_LI"] - last["T_LI"], axis=1),
+               dlag=ok["total_time_lag"] - last["total_time_lag"])
+    for k in ("rot_deg", "dT", "dlag"):
+        out[k + "_mean"], out[k + "_std"] = float(np.mean(out[k])), float(np.std(out[k]))
+    return out
 
 
 class Registrar:
@@ -1490,6 +1614,43 @@ class Registrar:
         if n.value:
             self._check(self.L.lii_li_init_resident_fetch(self.h, int(which), _ptr(imu), _ptr(lid), n.value, C.byref(n)))
         return imu, lid
+
+    def li_init_windows_records(self, imu22, lidar22, windows, orig_odom_freq, cut_frame_num, interpolate=False):
+        """lii_li_init_windows: LI_Initialization on every window of the sequences in one call (one upload, a fixed number of
+        launches whatever the number of windows, one wait).  windows: what li_init_prefix_windows / li_init_sliding_windows
+        return, or rows (begin, count) - aligned form - or (imu_begin, imu_count, lidar_begin, lidar_count[, move_start_time]).
+        Returns the ctypes array of lii_li_init_window_result, one per window."""
+        imu = np.ascontiguousarray(imu22, np.float64).reshape(-1, 22)
+        lid = np.ascontiguousarray(lidar22, np.float64).reshape(-1, 22)
+        win = li_init_window_array(windows)
+        job = lii_li_init_job(C.sizeof(lii_li_init_job), int(bool(interpolate)), imu.ctypes.data, len(imu), lid.ctypes.data, len(lid),
+                              0.0, int(orig_odom_freq), int(cut_frame_num))
+        out = (lii_li_init_window_result * max(len(win), 1))()
+        self._check(self.L.lii_li_init_windows(self.h, C.byref(job), win.ctypes.data, len(win), C.addressof(out),
+                                               C.sizeof(lii_li_init_window_result)))
+        return out
+
+    def li_init_windows(self, imu22, lidar22, windows, orig_odom_freq, cut_frame_num, interpolate=False):
+        """li_init_windows_records as a structured array of LI_INIT_WINDOW_DTYPE (a refused window: its status, zeros behind it)."""
+        out = self.li_init_windows_records(imu22, lidar22, windows, orig_odom_freq, cut_frame_num, interpolate)
+        rec = np.zeros(len(out), LI_INIT_WINDOW_DTYPE)
+        for k, q in enumerate(out):
+            r = rec[k]
+            r["status"] = q.status
+            r["R_LI"] = np.array(q.res.R_LI[:]).reshape(3, 3)
+            for f in ("T_LI", "gyro_bias", "acc_bias", "grav_L0", "iterations", "final_cost"):
+                r[f] = getattr(q.res, f)[:]
+            r["time_lag_2"] = q.res.time_lag_2
+            r["termination"] = q.rep.termination[:]
+            for f in ("time_lag_1", "total_time_lag", "n_aligned", "n_stage12", "n_stage3", "lag_samples"):
+                r[f] = getattr(q.rep, f)
+        return rec
+
+    def li_init_windows_scratch(self):
+        """(bytes of device scratch li_init_windows holds on this handle, allocations its calls have made so far)"""
+        b, a = C.c_uint64(0), C.c_int64(0)
+        self._check(self.L.lii_li_init_windows_scratch(self.h, C.byref(b), C.byref(a)))
+        return b.value, a.value
 
     def calib_solve_stage_dev(self, stage, result=None):
         """calib_solve_stage with the whole Levenberg-Marquardt in one launch."""

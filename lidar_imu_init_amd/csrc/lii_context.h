@@ -350,6 +350,18 @@ struct lii_context {
       int ib12 = 0, lb12 = 0, n12 = 0;  // ... the view of the stage 1/2 sequences in d_seq
       int n3 = 0;                       // ... the length of the stage 3 copies
     } res;
+    // lii_li_init_windows (lii_li_init_resident.hip): K sub-ranges of one upload, every window in areas of its own.  Nothing here
+    // exists before the first such call; each buffer grows geometrically and is never released before the handle goes.  The call
+    // reads and writes nothing of `res` or of the d_cal_* buffers above.
+    struct Windows {
+      DevBuf<double> d_src;    // the job's sequences as uploaded: IMU records, then LiDAR records
+      DevBuf<double> d_seq;    // K areas of WinLayout::doubles(longest window)
+      DevBuf<double> d_fts;    // raw form: K areas of 4 doubles per raw IMU state of the longest window (filtered accelerations, stamps)
+      DevBuf<double> d_small;  // K control + result blocks
+      DevBuf<lii_li_init_window> d_win;
+      PinnedBuf<double> h_back;  // the K control + result blocks on their way back
+      long long allocations = 0; // allocations made by all calls so far (lii_li_init_windows_scratch)
+    } win;
   } cal;
   // ---- IMU processing (lii_capi_imu.cpp, lii_imu.hip)
   struct ImuState {

@@ -96,15 +96,15 @@ __device__ bool align_views(int& ib, int& ni, int& lb, int& nl, int* s_first, TI
 // ------------------------------------------------------------------------------------------------ downsample_interpolate_IMU
 // every workgroup finds the first raw IMU state not older than move_start_time - 3 s (ka) for itself; workgroup 0 leaves ka / kl in the
 // control block.  facc[i] = the 5-tap running mean of the accelerations (raw at the two ends), ts[i] = the stamp.
-__global__ __launch_bounds__(256) void k_res_interp_filter(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw,
-                                                           int n_imu, const double* __restrict__ lid, int n_lid, double mst,
-                                                           double* __restrict__ facc, double* __restrict__ ts) {
+__device__ __forceinline__ void d_res_interp_filter(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw, int n_imu,
+                                                    const double* __restrict__ lid, int n_lid, double mst, double* __restrict__ facc,
+                                                    double* __restrict__ ts, int bx) {
   if (!interpolate) return;
   __shared__ int s_first;
   const double t_min = mst - 3.0;
   const int ka = block_find_first(n_imu, &s_first, [&](int i) { return !(raw[(size_t)i * 22 + 21] < t_min); });
   const int size = n_imu - ka;
-  if (blockIdx.x == 0) {
+  if (bx == 0) {
     const int kl = block_find_first(n_lid, &s_first, [&](int i) { return !(lid[(size_t)i * 22 + 21] < t_min); });
     if (threadIdx.x == 0) {
       ctl->ka = ka;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void k_res_interp_filter(ResCtl* __restrict__ 
       if (size < 6) ctl->status = kResRaw6;
     }
   }
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = bx * 256 + threadIdx.x;
   if (i >= n_imu) return;
   ts[i] = raw[(size_t)i * 22 + 21];
   const int r = i - ka;
@@ -124,12 +124,17 @@ __global__ __launch_bounds__(256) void k_res_interp_filter(ResCtl* __restrict__ 
   }
   for (int a = 0; a < 3; a++) facc[(size_t)i * 3 + a] = acc[a];
 }
+__global__ __launch_bounds__(256) void k_res_interp_filter(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw,
+                                                           int n_imu, const double* __restrict__ lid, int n_lid, double mst,
+                                                           double* __restrict__ facc, double* __restrict__ ts) {
+  d_res_interp_filter(ctl, interpolate, raw, n_imu, lid, n_lid, mst, facc, ts, blockIdx.x);
+}
 // one workgroup per LiDAR state: the first j in ascending order with all[j - 1].t <= t < all[j].t, 256 candidates per step
-__global__ __launch_bounds__(256) void k_res_interp_search(const ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ ts,
-                                                           int n_imu, const double* __restrict__ lid, int* __restrict__ found) {
+__device__ __forceinline__ void d_res_interp_search(const ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ ts, int n_imu,
+                                                    const double* __restrict__ lid, int* __restrict__ found, int bx) {
   if (!interpolate || ctl->status) return;
   __shared__ int s_first;
-  const int l = blockIdx.x, ka = ctl->ka, size = n_imu - ka;
+  const int l = bx, ka = ctl->ka, size = n_imu - ka;
   if (l < ctl->kl) {
     if (threadIdx.x == 0) found[l] = -1;
     return;
@@ -149,11 +154,15 @@ __global__ __launch_bounds__(256) void k_res_interp_search(const ResCtl* __restr
   }
   if (threadIdx.x == 0) found[l] = hit < size ? ka + hit : -1;
 }
+__global__ __launch_bounds__(256) void k_res_interp_search(const ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ ts,
+                                                           int n_imu, const double* __restrict__ lid, int* __restrict__ found) {
+  d_res_interp_search(ctl, interpolate, ts, n_imu, lid, found, blockIdx.x);
+}
 // the retained states in their order -> the aligned sequences; one workgroup walks the LiDAR states 256 at a time
-__global__ __launch_bounds__(256) void k_res_interp_compact(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw,
-                                                            const double* __restrict__ facc, const double* __restrict__ raw_lid,
-                                                            const int* __restrict__ found, int n_lid, double* __restrict__ imu,
-                                                            double* __restrict__ lid) {
+__device__ __forceinline__ void d_res_interp_compact(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw,
+                                                     const double* __restrict__ facc, const double* __restrict__ raw_lid,
+                                                     const int* __restrict__ found, int n_lid, double* __restrict__ imu,
+                                                     double* __restrict__ lid) {
   if (!interpolate || ctl->status) return;
   __shared__ int s_scan[256];
   __shared__ int s_base;
@@ -197,11 +206,17 @@ __global__ __launch_bounds__(256) void k_res_interp_compact(ResCtl* __restrict__
     if (s_base < 200) ctl->status = kResAligned200;
   }
 }
+__global__ __launch_bounds__(256) void k_res_interp_compact(ResCtl* __restrict__ ctl, int interpolate, const double* __restrict__ raw,
+                                                            const double* __restrict__ facc, const double* __restrict__ raw_lid,
+                                                            const int* __restrict__ found, int n_lid, double* __restrict__ imu,
+                                                            double* __restrict__ lid) {
+  d_res_interp_compact(ctl, interpolate, raw, facc, raw_lid, found, n_lid, imu, lid);
+}
 
 // ------------------------------------------------------------------------------------------------ the chain
 // IMU_time_compensate(0.0, true): discard ten pairs, (stamps - 0.0: unchanged), align
-__global__ __launch_bounds__(256) void k_res_head(ResCtl* __restrict__ ctl, int interpolate, int n_in, const double* __restrict__ imu,
-                                                  const double* __restrict__ lid) {
+__device__ __forceinline__ void d_res_head(ResCtl* __restrict__ ctl, int interpolate, int n_in, const double* __restrict__ imu,
+                                           const double* __restrict__ lid) {
   __shared__ int s_first;
   if (ctl->status) return;
   const int n0 = interpolate ? ctl->n_aligned : n_in;
@@ -214,14 +229,18 @@ __global__ __launch_bounds__(256) void k_res_head(ResCtl* __restrict__ ctl, int 
     if (!ok) ctl->status = kResAlign;
   }
 }
+__global__ __launch_bounds__(256) void k_res_head(ResCtl* __restrict__ ctl, int interpolate, int n_in, const double* __restrict__ imu,
+                                                  const double* __restrict__ lid) {
+  d_res_head(ctl, interpolate, n_in, imu, lid);
+}
 
 // zero_phase_filt of the pair: channel c < 12 is member 9 + c of the IMU records, c >= 12 member 9 + c - 12 of the LiDAR records.
 // Pass 0 filters the view into tmp (24 doubles per state, time-reversed), pass 1 filters tmp back into the view, reversed again;
 // only the channels of `mask` are written back (the second filter: set_states_2nd_filter).  Tiles of kTile padded samples: all lanes
 // form the FIR half into LDS, lanes 0 .. 23 run the recursion over the tile, all lanes store it.
 constexpr int kTile = 256, kTilePitch = 25;
-__global__ __launch_bounds__(256) void k_res_zero_phase(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid,
-                                                        double* __restrict__ tmp, unsigned int mask) {
+__device__ __forceinline__ void d_res_zero_phase(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid,
+                                                 double* __restrict__ tmp, unsigned int mask) {
   __shared__ double s_f[kTile * kTilePitch];
   if (ctl->status) return;
   const int n = ctl->n;
@@ -297,12 +316,16 @@ __global__ __launch_bounds__(256) void k_res_zero_phase(ResCtl* __restrict__ ctl
     }
   }
 }
+__global__ __launch_bounds__(256) void k_res_zero_phase(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid,
+                                                        double* __restrict__ tmp, unsigned int mask) {
+  d_res_zero_phase(ctl, imu, lid, tmp, mask);
+}
 
 // normalize_acc; set_IMU_state / set_Lidar_state drop the last element; cut_sequence_tail; a[i] = |w_imu|, b[i] = |w_lidar| of the
 // view that is left and their running means, as the host forms them: one lane each, over tiles in LDS
 constexpr int kMeanTile = 1024;
-__global__ __launch_bounds__(256) void k_res_mid(ResCtl* __restrict__ ctl, double* __restrict__ imu, const double* __restrict__ lid,
-                                                 double* __restrict__ a, double* __restrict__ b) {
+__device__ __forceinline__ void d_res_mid(ResCtl* __restrict__ ctl, double* __restrict__ imu, const double* __restrict__ lid,
+                                          double* __restrict__ a, double* __restrict__ b) {
   __shared__ int s_first;
   __shared__ double s_nrm;
   __shared__ double s_a[kMeanTile], s_b[kMeanTile];
@@ -348,6 +371,10 @@ __global__ __launch_bounds__(256) void k_res_mid(ResCtl* __restrict__ ctl, doubl
   if (threadIdx.x < 2) ctl->means[threadIdx.x] = mean;
   if (threadIdx.x == 0) { ctl->ib = ib; ctl->lb = lb; ctl->n = n; }
 }
+__global__ __launch_bounds__(256) void k_res_mid(ResCtl* __restrict__ ctl, double* __restrict__ imu, const double* __restrict__ lid,
+                                                 double* __restrict__ a, double* __restrict__ b) {
+  d_res_mid(ctl, imu, lid, a, b);
+}
 
 __global__ __launch_bounds__(256) void k_res_xcorr(const ResCtl* __restrict__ ctl, const double* __restrict__ a, const double* __restrict__ b,
                                                    double* __restrict__ corr) {
@@ -362,7 +389,7 @@ __global__ __launch_bounds__(256) void k_res_argmax(ResCtl* __restrict__ ctl, co
 }
 
 // time_lag_1 = lag / (orig_odom_freq * cut_frame_num); IMU_time_compensate(time_lag_1, false); central_diff
-__global__ __launch_bounds__(256) void k_res_after_lag(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid, int freq_cut) {
+__device__ __forceinline__ void d_res_after_lag(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid, int freq_cut) {
   __shared__ int s_first;
   if (ctl->status) return;
   int ib = ctl->ib, lb = ctl->lb, n = ctl->n;
@@ -394,13 +421,17 @@ __global__ __launch_bounds__(256) void k_res_after_lag(ResCtl* __restrict__ ctl,
     ctl->lag1 = lag1;
   }
 }
+__global__ __launch_bounds__(256) void k_res_after_lag(ResCtl* __restrict__ ctl, double* __restrict__ imu, double* __restrict__ lid, int freq_cut) {
+  d_res_after_lag(ctl, imu, lid, freq_cut);
+}
 
 // IMU_time_compensate(time_lag_2, false) and acc_interpolate, out of place: the stage 1/2 view stays as it is (lii_li_init_resident_fetch),
 // the stage-3 sequences are written from index 0 of imu3 / lid3 and copied into the handle's calibration buffers.
 constexpr int kAccTile = 512;
-__global__ __launch_bounds__(256) void k_res_stage3_prep(ResCtl* __restrict__ ctl, const ResOut* __restrict__ ro, const double* __restrict__ imu,
-                                                         const double* __restrict__ lid, double* __restrict__ imu3, double* __restrict__ lid3,
-                                                         double* __restrict__ cal_imu, double* __restrict__ cal_lid) {
+template <bool CAL>  // CAL: the copies into the handle's calibration buffers (the batched form leaves them alone)
+__device__ __forceinline__ void d_res_stage3_prep(ResCtl* __restrict__ ctl, const ResOut* __restrict__ ro, const double* __restrict__ imu,
+                                                  const double* __restrict__ lid, double* __restrict__ imu3, double* __restrict__ lid3,
+                                                  double* __restrict__ cal_imu, double* __restrict__ cal_lid) {
   __shared__ int s_first;
   __shared__ double s_ti[kAccTile + 1], s_tl[kAccTile], s_acc[3][kAccTile + 1];
   __shared__ double s_s[kAccTile], s_nt[kAccTile], s_v[3][kAccTile], s_prev[4];
@@ -483,11 +514,17 @@ __global__ __launch_bounds__(256) void k_res_stage3_prep(ResCtl* __restrict__ ct
     }
     __syncthreads();
   }
-  for (int e = threadIdx.x; e < n * 22; e += 256) {
-    cal_imu[e] = imu3[e];
-    cal_lid[e] = lid3[e];
-  }
+  if (CAL)
+    for (int e = threadIdx.x; e < n * 22; e += 256) {
+      cal_imu[e] = imu3[e];
+      cal_lid[e] = lid3[e];
+    }
   if (threadIdx.x == 0) ctl->n3 = n;
+}
+__global__ __launch_bounds__(256) void k_res_stage3_prep(ResCtl* __restrict__ ctl, const ResOut* __restrict__ ro, const double* __restrict__ imu,
+                                                         const double* __restrict__ lid, double* __restrict__ imu3, double* __restrict__ lid3,
+                                                         double* __restrict__ cal_imu, double* __restrict__ cal_lid) {
+  d_res_stage3_prep<true>(ctl, ro, imu, lid, imu3, lid3, cal_imu, cal_lid);
 }
 
 // ------------------------------------------------------------------------------------------------ the Levenberg-Marquardt of lii_calib.cpp
@@ -718,8 +755,8 @@ __device__ int lm_advance(LmWork& w, const double* out, double* params) {
 // mode 0: n records from index 0 of imu / lidar (lii_calib_solve_stage_dev); mode 1: the stage 1/2 view of the control block;
 // mode 2: ctl->n3 records from index 0 (the stage-3 copies).
 template <int STAGE>
-__global__ __launch_bounds__(256) void k_calib_lm(const ResCtl* __restrict__ ctl, int mode, const double* __restrict__ imu,
-                                                  const double* __restrict__ lidar, int n, ResOut* __restrict__ ro) {
+__device__ __forceinline__ void d_calib_lm(const ResCtl* __restrict__ ctl, int mode, const double* __restrict__ imu,
+                                           const double* __restrict__ lidar, int n, ResOut* __restrict__ ro) {
   constexpr int DOF = STAGE == 1 ? 3 : (STAGE == 2 ? 7 : 9);
   constexpr int NOUT = DOF * DOF + DOF + 1;
   constexpr int kMaxEvals = 51;  // the start point and one candidate per iteration (max_iterations = 50)
@@ -793,6 +830,11 @@ __global__ __launch_bounds__(256) void k_calib_lm(const ResCtl* __restrict__ ctl
     }
   }
 }
+template <int STAGE>
+__global__ __launch_bounds__(256) void k_calib_lm(const ResCtl* __restrict__ ctl, int mode, const double* __restrict__ imu,
+                                                  const double* __restrict__ lidar, int n, ResOut* __restrict__ ro) {
+  d_calib_lm<STAGE>(ctl, mode, imu, lidar, n, ro);
+}
 
 void launch_calib_lm(int stage, const ResCtl* ctl, int mode, const double* imu, const double* lidar, int n, ResOut* ro, hipStream_t s) {
   if (stage == 1) hipLaunchKernelGGL(k_calib_lm<1>, dim3(1), dim3(256), 0, s, ctl, mode, imu, lidar, n, ro);
@@ -813,6 +855,126 @@ struct SeqLayout {
     found = reinterpret_cast<int*>(raw_lid + 22 * c);
   }
 };
+
+// ------------------------------------------------------------------------------------------------ K windows of one upload
+// lii_li_init_windows: window w = blockIdx.y runs the chain above on its slice of the upload, in areas of its own - its control and
+// result block, a WinLayout sized by the longest window and, in the raw form, its filtered accelerations and stamps.  Every launch
+// calls the device function the single form's kernel calls, on the window's pointers: same operations in the same order, and every
+// order of addition depends on the window's own lengths alone.  Nothing is shared between windows but the read-only upload.
+struct WinLayout {  // SeqLayout without the raw LiDAR copy (the upload is read in place)
+  double *imu, *lid, *imu3, *lid3, *tmp, *a, *b, *corr;
+  int* found;
+  __host__ __device__ static size_t doubles(size_t c) { return c * (22 * 4 + 24 + 2 + 2) + c / 2 + 8; }
+  __host__ __device__ WinLayout(double* d, size_t c) {
+    imu = d; lid = imu + 22 * c; imu3 = lid + 22 * c; lid3 = imu3 + 22 * c; tmp = lid3 + 22 * c;
+    a = tmp + 24 * c; b = a + c; corr = b + c;
+    found = reinterpret_cast<int*>(corr + 2 * c);
+  }
+};
+struct WinArgs {
+  const lii_li_init_window* win;  // K descriptors
+  double* small;                  // K x kSmallDoubles: ResCtl | ResOut
+  double* seq;                    // K x WinLayout::doubles(cap)
+  double* fts;                    // raw form: K x 4 cap_raw (facc: 3 per state, then ts)
+  const double *src_imu, *src_lid;  // the upload
+  int cap, cap_raw, interpolate, freq_cut;
+};
+struct Win {
+  lii_li_init_window d;
+  ResCtl* ctl;
+  ResOut* ro;
+  WinLayout L;
+  double *facc, *ts;
+  const double *raw, *raw_lid;
+  __device__ Win(const WinArgs& A, int w)
+      : d(A.win[w]), ctl(reinterpret_cast<ResCtl*>(A.small + (size_t)w * kSmallDoubles)),
+        ro(reinterpret_cast<ResOut*>(A.small + (size_t)w * kSmallDoubles + sizeof(ResCtl) / 8)),
+        L(A.seq + (size_t)w * WinLayout::doubles(size_t(A.cap)), size_t(A.cap)),
+        facc(A.fts ? A.fts + (size_t)w * 4 * A.cap_raw : nullptr), ts(A.fts ? facc + (size_t)3 * A.cap_raw : nullptr),
+        raw(A.src_imu + (size_t)d.imu_begin * 22), raw_lid(A.src_lid + (size_t)d.lidar_begin * 22) {}
+};
+// aligned form: the window's slice of the upload -> its own sequences (the chain works in place); grid: 22 * cap elements x K
+__global__ __launch_bounds__(256) void k_win_gather(WinArgs A) {
+  if (A.interpolate) return;
+  const Win W(A, blockIdx.y);
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= W.d.lidar_count * 22) return;
+  W.L.imu[e] = W.raw[e];
+  W.L.lid[e] = W.raw_lid[e];
+}
+// the three kernels of more than one workgroup: the grid is the longest window's, a workgroup beyond its own window's returns
+__global__ __launch_bounds__(256) void k_win_interp_filter(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  if ((int)blockIdx.x * 256 >= max(W.d.imu_count, 1)) return;
+  d_res_interp_filter(W.ctl, A.interpolate, W.raw, W.d.imu_count, W.raw_lid, W.d.lidar_count, W.d.move_start_time, W.facc, W.ts, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_win_interp_search(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  if ((int)blockIdx.x >= W.d.lidar_count) return;
+  d_res_interp_search(W.ctl, A.interpolate, W.ts, W.d.imu_count, W.raw_lid, W.L.found, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void k_win_xcorr(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  if ((int)blockIdx.x * 256 >= 2 * W.d.lidar_count - 1 || W.ctl->status) return;
+  xcorr_lane(W.L.a, W.L.b, W.ctl->means, W.ctl->n, W.L.corr, blockIdx.x * 256 + threadIdx.x);
+}
+// the kernels of one workgroup: 1 x K
+__global__ __launch_bounds__(256) void k_win_interp_compact(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  d_res_interp_compact(W.ctl, A.interpolate, W.raw, W.facc, W.raw_lid, W.L.found, W.d.lidar_count, W.L.imu, W.L.lid);
+}
+__global__ __launch_bounds__(256) void k_win_head(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  d_res_head(W.ctl, A.interpolate, W.d.lidar_count, W.L.imu, W.L.lid);
+}
+__global__ __launch_bounds__(256) void k_win_zero_phase(WinArgs A, unsigned int mask) {
+  const Win W(A, blockIdx.y);
+  d_res_zero_phase(W.ctl, W.L.imu, W.L.lid, W.L.tmp, mask);
+}
+__global__ __launch_bounds__(256) void k_win_mid(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  d_res_mid(W.ctl, W.L.imu, W.L.lid, W.L.a, W.L.b);
+}
+__global__ __launch_bounds__(256) void k_win_argmax(WinArgs A) {
+  __shared__ double s_v[256];
+  __shared__ int s_k[256];
+  const Win W(A, blockIdx.y);
+  if (W.ctl->status) return;
+  xcorr_argmax_block(W.L.corr, W.ctl->n, &W.ctl->lag, s_v, s_k);
+}
+__global__ __launch_bounds__(256) void k_win_after_lag(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  d_res_after_lag(W.ctl, W.L.imu, W.L.lid, A.freq_cut);
+}
+__global__ __launch_bounds__(256) void k_win_stage3_prep(WinArgs A) {  // the stage-3 sequences stay in the window's area
+  const Win W(A, blockIdx.y);
+  d_res_stage3_prep<false>(W.ctl, W.ro, W.L.imu, W.L.lid, W.L.imu3, W.L.lid3, nullptr, nullptr);
+}
+template <int STAGE>
+__global__ __launch_bounds__(256) void k_win_calib_lm(WinArgs A) {
+  const Win W(A, blockIdx.y);
+  if (STAGE == 3) d_calib_lm<STAGE>(W.ctl, 2, W.L.imu3, W.L.lid3, 0, W.ro);
+  else d_calib_lm<STAGE>(W.ctl, 1, W.L.imu, W.L.lid, 0, W.ro);
+}
+constexpr int kWindowsLaunches = 15;
+constexpr int kWindowsMax = 4096;
+constexpr size_t kWindowsScratchMax = size_t(4) << 30;  // bytes of device scratch one call may ask for
+static_assert(kSmallDoubles == 113, "liinit_hip.h states the per-window bytes");
+static_assert(sizeof(lii_li_init_window) == 24, "lii_li_init_window layout");
+static_assert(kResFilter61 == LII_WIN_FILTER61 && kResAligned200 == LII_WIN_ALIGNED200 && kResRaw6 == LII_WIN_RAW6 &&
+              kResAlign == LII_WIN_NO_OVERLAP, "lii_li_init_window_result::status is the ResStatus");
+
+// what lii_li_init_resident reports of a run that ended with status kResOk (launches / host_waits are the caller's)
+void fill_report(const ResCtl& c, const ResOut& o, lii_li_init_report* rep) {
+  rep->n_aligned = c.n_aligned;
+  rep->n_stage12 = c.n12;
+  rep->n_stage3 = c.n3;
+  rep->lag_samples = c.lag;
+  for (int k = 0; k < 3; k++) rep->termination[k] = o.termination[k];
+  rep->time_lag_1 = c.lag1;
+  rep->total_time_lag = c.lag1 + o.res.time_lag_2;
+  std::memcpy(rep->params, o.params, sizeof(o.params));
+}
 
 int ensure_small(lii_handle h) {
   auto& r = h->cal.res;
@@ -923,18 +1085,120 @@ int lii_li_init_resident(lii_handle h, const lii_li_init_job* job, lii_calib_res
   r.have_run = true;
   r.ib12 = c.ib12; r.lb12 = c.lb12; r.n12 = c.n12; r.n3 = c.n3;
   if (rep) {
-    rep->n_aligned = c.n_aligned;
-    rep->n_stage12 = c.n12;
-    rep->n_stage3 = c.n3;
-    rep->lag_samples = c.lag;
+    fill_report(c, o, rep);
     rep->launches = launches;
     rep->host_waits = 1;
-    for (int k = 0; k < 3; k++) rep->termination[k] = o.termination[k];
-    rep->time_lag_1 = c.lag1;
-    rep->total_time_lag = c.lag1 + o.res.time_lag_2;
-    std::memcpy(rep->params, o.params, sizeof(o.params));
   }
   static_assert(kResidentLaunches == 14, "lii_li_init_report::launches");
+  return LII_OK;
+}
+
+int lii_li_init_windows(lii_handle h, const lii_li_init_job* job, const lii_li_init_window* windows, int32_t n_windows,
+                        lii_li_init_window_result* out, uint32_t out_stride) {
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (!h || !job || !windows || !out) return fail(h, LII_ERR_INVALID, "lii_li_init_windows: NULL argument");
+  if (job->struct_size != sizeof(lii_li_init_job) || out_stride != sizeof(lii_li_init_window_result))
+    return fail(h, LII_ERR_INVALID, "lii_li_init_windows: bad struct_size or out_stride");
+  if (job->interpolate != 0 && job->interpolate != 1) return fail(h, LII_ERR_INVALID, "lii_li_init_windows: interpolate must be 0 or 1");
+  if (!job->imu || !job->lidar || job->n_imu < 1 || job->n_lidar < 1 || job->orig_odom_freq < 1 || job->cut_frame_num < 1)
+    return fail(h, LII_ERR_INVALID, "lii_li_init_windows: bad arguments");
+  if (n_windows < 1 || n_windows > kWindowsMax) return fail(h, LII_ERR_INVALID, "lii_li_init_windows: n_windows must be 1 .. 4096");
+  const int itp = job->interpolate, K = n_windows;
+  int cap = 0, cap_raw = 0;
+  for (int w = 0; w < K; w++) {
+    const lii_li_init_window& d = windows[w];
+    if (d.imu_begin < 0 || d.imu_count < 0 || d.lidar_begin < 0 || d.lidar_count < 0 || d.imu_count > job->n_imu - d.imu_begin ||
+        d.lidar_count > job->n_lidar - d.lidar_begin)
+      return fail(h, LII_ERR_INVALID, "lii_li_init_windows: a window lies outside the job's sequences");
+    if (!itp && (d.imu_begin != d.lidar_begin || d.imu_count != d.lidar_count || d.lidar_count < 200))
+      return fail(h, LII_ERR_INVALID, "lii_li_init_windows: an aligned window takes imu range == lidar range, 200 states or more");
+    if (itp && (d.imu_count < 6 || d.lidar_count < 1))
+      return fail(h, LII_ERR_INVALID, "lii_li_init_windows: a raw window takes imu_count >= 6 and lidar_count >= 1");
+    cap = std::max(cap, d.lidar_count);
+    if (itp) cap_raw = std::max(cap_raw, d.imu_count);
+  }
+  if (lii_internal_in_wait_hook(h)) return fail(h, LII_ERR_STATE, "lii_li_init_windows: not from inside lii_scan_job::while_waiting");
+  const size_t n_src = (size_t(job->n_imu) + size_t(job->n_lidar)) * 22;
+  const size_t n_seq = size_t(K) * WinLayout::doubles(size_t(cap)), n_fts = size_t(K) * 4 * size_t(cap_raw);
+  const size_t n_small = size_t(K) * kSmallDoubles;
+  const size_t bytes = 8 * (n_src + n_seq + n_fts + n_small) + sizeof(lii_li_init_window) * size_t(K);
+  if (bytes > kWindowsScratchMax) return fail(h, LII_ERR_CAPACITY, "lii_li_init_windows: the windows' scratch would exceed 4 GiB");
+  // buffers: geometric growth (never beyond the limit), nothing released in the steady state
+  auto& r = h->cal.win;
+  auto room = [&](auto& buf, size_t n, size_t elem) -> hipError_t {
+    if (n <= buf.size()) return hipSuccess;
+    r.allocations++;
+    return buf.grow(std::max(n, std::min(2 * buf.size(), kWindowsScratchMax / elem)));
+  };
+  HIPCHK(h, room(r.d_src, n_src, 8));
+  HIPCHK(h, room(r.d_seq, n_seq, 8));
+  HIPCHK(h, room(r.d_fts, n_fts, 8));
+  HIPCHK(h, room(r.d_small, n_small, 8));
+  HIPCHK(h, room(r.d_win, size_t(K), sizeof(lii_li_init_window)));
+  if (n_small > r.h_back.size()) {
+    r.allocations++;
+    HIPCHK(h, r.h_back.at_least(n_small, hipHostMallocDefault));
+  }
+  hipStream_t s = h->stream;
+  double* src_imu = r.d_src;
+  double* src_lid = src_imu + size_t(job->n_imu) * 22;
+  // the one upload
+  HIPCHK(h, hipMemsetAsync(r.d_small, 0, sizeof(double) * n_small, s));
+  HIPCHK(h, hipMemcpyAsync(src_imu, job->imu, sizeof(lii_calib_state) * size_t(job->n_imu), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(src_lid, job->lidar, sizeof(lii_calib_state) * size_t(job->n_lidar), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(r.d_win, windows, sizeof(lii_li_init_window) * size_t(K), hipMemcpyHostToDevice, s));
+  WinArgs A;
+  A.win = r.d_win; A.small = r.d_small; A.seq = r.d_seq; A.fts = itp ? r.d_fts.get() : nullptr;
+  A.src_imu = src_imu; A.src_lid = src_lid;
+  A.cap = cap; A.cap_raw = cap_raw; A.interpolate = itp; A.freq_cut = job->orig_odom_freq * job->cut_frame_num;
+  const unsigned int uk = (unsigned int)K;
+  const dim3 one(1, uk), wg(256);
+  const unsigned int all_channels = 0xFFFFFFu;
+  const unsigned int second_filter = (7u << 6) | (7u << 18) | (7u << 21);  // IMU ang_acc; LiDAR ang_acc, linear_acc
+  int launches = 0;
+  hipLaunchKernelGGL(k_win_gather, dim3(itp ? 1 : (cap * 22 + 255) / 256, uk), wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_interp_filter, dim3(std::max(1, (cap_raw + 255) / 256), uk), wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_interp_search, dim3(itp ? cap : 1, uk), wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_interp_compact, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_head, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_zero_phase, one, wg, 0, s, A, all_channels); launches++;
+  hipLaunchKernelGGL(k_win_mid, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_xcorr, dim3((2 * cap - 1 + 255) / 256, uk), wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_argmax, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_after_lag, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_zero_phase, one, wg, 0, s, A, second_filter); launches++;
+  hipLaunchKernelGGL(k_win_calib_lm<1>, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_calib_lm<2>, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_stage3_prep, one, wg, 0, s, A); launches++;
+  hipLaunchKernelGGL(k_win_calib_lm<3>, one, wg, 0, s, A); launches++;
+  double* back = r.h_back;
+  HIPCHK(h, hipMemcpyAsync(back, r.d_small, sizeof(double) * n_small, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));  // the one wait
+  HIPCHK(h, hipGetLastError());
+  static_assert(kWindowsLaunches == 15, "lii_li_init_window_result::rep.launches");
+  for (int w = 0; w < K; w++) {
+    ResCtl c;
+    ResOut o;
+    std::memcpy(&c, back + size_t(w) * kSmallDoubles, sizeof(c));
+    std::memcpy(&o, back + size_t(w) * kSmallDoubles + sizeof(ResCtl) / 8, sizeof(o));
+    lii_li_init_window_result& q = out[w];
+    std::memset(&q, 0, sizeof(q));
+    q.status = c.status;
+    if (c.status != kResOk) continue;
+    q.res = o.res;
+    q.rep.struct_size = sizeof(lii_li_init_report);
+    fill_report(c, o, &q.rep);
+    q.rep.launches = launches;
+    q.rep.host_waits = 1;
+  }
+  return LII_OK;
+}
+
+int lii_li_init_windows_scratch(lii_handle h, uint64_t* bytes, int64_t* allocations) {
+  if (!h) return fail(h, LII_ERR_INVALID, "lii_li_init_windows_scratch: NULL handle");
+  const auto& r = h->cal.win;
+  if (bytes) *bytes = 8 * uint64_t(r.d_src.size() + r.d_seq.size() + r.d_fts.size() + r.d_small.size()) + sizeof(lii_li_init_window) * uint64_t(r.d_win.size());
+  if (allocations) *allocations = r.allocations;
   return LII_OK;
 }
 
