@@ -297,6 +297,60 @@ int lii_map_radius(lii_handle h, const void* xyz, int32_t n, int32_t stride_byte
 int lii_map_radius_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, int32_t flags,
                        int64_t* offsets_dev /* n + 1 */, float* pts_dev, float* d2_dev, int64_t capacity,
                        int64_t* total_dev /* one word */);
+/* ---- the surface the map holds at a point: normal, curvature, covariance spectrum of a ball (no counterpart in the reference: PCL's
+ * NormalEstimation - computePointNormal, flipNormalTowardsViewpoint, curvature = "surface variation" - and the mean map entropy / mean
+ * plane variance of the LiDAR calibration literature are the models).  LII_ABI_VERSION stays 9: everything below is new.
+ * Query i (float xyz every stride_bytes, as for lii_map_radius) is answered from EXACTLY the points of its lii_map_radius segment at the
+ * same max_dist (a SQUARED distance; float32 calc_dist against it, inclusive): `count` is that segment's length.  The ball is reduced on
+ * the device, one wavefront per query, in double and relative to the query:
+ *   d = (double)m - (double)q per axis,  s1 = sum d,  s2_ab = sum d_a d_b,
+ *   mean_rel = s1 / n,   C_ab = s2_ab / n - mean_rel_a * mean_rel_b          (formed exactly so, no FMA)
+ * and C is decomposed by lii_sym3_eigen's routine.  A query's record is the SAME BITS alone or in any batch, in the host or the device
+ * form, on every call, for a given map state (fixed-order sums, no atomics).
+ * Sign of the normal: viewpoint == NULL - the component of largest magnitude is positive (on a tie the lowest index decides); viewpoint
+ * (3 doubles, map coordinates; a HOST pointer in both forms) - normal . (viewpoint - mean) >= 0.
+ * The contract is lii_map_radius's: any finite max_dist >= 0; LII_ERR_INVALID with nothing written for max_dist NaN, infinite or negative,
+ * sqrt(max_dist) > 32 map_cell_size, a bad stride, n < 0, NULL queries or out with n > 0; no map: LII_ERR_STATE; from inside
+ * lii_scan_job::while_waiting: LII_ERR_STATE; n == 0: LII_OK.  A query with a NaN coordinate, or one whose ball reaches no addressable
+ * cell, gets count 0, valid 0.  OBSERVERS in the sense of lii_map_nearest: they end a pre-armed launch and join a map update in flight
+ * first, write nothing of the registration state, work with a communicator attached and under LII_TEST=host_solve.
+ *   lii_map_surface      host queries, host records, synchronous: chunks of 65 536 queries through the staging of lii_map_nearest.
+ *   lii_map_surface_dev  queries and records in device memory of the caller: enqueued on the handle's stream, returns without waiting. */
+struct lii_surface {  /* 88 bytes, no padding */
+  int32_t count;      /* live map points with d2 <= max_dist: lii_map_radius's count, exactly */
+  int32_t valid;      /* 1 when count >= 3, else 0: eig, normal and curvature are zeros then */
+  double  mean[3];    /* centroid of the ball in map coordinates (q + s1/n); zeros when count == 0 */
+  double  eig[3];     /* eigenvalues of C, ascending, negative rounding residue clamped to 0 */
+  double  normal[3];  /* unit eigenvector of eig[0] */
+  double  curvature;  /* eig[0] / (eig[0] + eig[1] + eig[2]) (PCL's surface variation); 0 when the sum is 0 */
+};
+int lii_map_surface(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist,
+                    const double* viewpoint /* NULL or 3 */, struct lii_surface* out /* n */);
+int lii_map_surface_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist,
+                        const double* viewpoint /* NULL or 3, host */, struct lii_surface* out_dev);
+/* lii_map_crispness: the whole map's figures - how crisp is the map a calibration produced?  The queries are the map's own live points,
+ * enumerated on the device as lii_map_download enumerates them (nothing is downloaded); a point is SELECTED when mix(x, y, z) % every == 0
+ * with, over the points' float bits in uint32 arithmetic,
+ *   h = bx * 0x9E3779B1u ^ by * 0x85EBCA77u ^ bz * 0xC2B2AE3Du;  h ^= h >> 15
+ * - a property of the point, not of where it is stored: two handles that hold the same multiset of points select the same points.  Each
+ * point's ball contains the point itself.  A selected point is SPARSE when count < min_count, else DEGENERATE when
+ * eig[0] <= 1e-12 * eig[2], else USED: n_selected = n_used + n_sparse + n_degenerate.
+ * The surface kernel writes one 24-byte term per selected point into scratch of the handle (created by the first call, grown geometrically,
+ * released with the handle; the selection runs through scratch of the map build), and a second launch adds the terms in a fixed order,
+ * in double, without atomics: the figures are the same bits on every call for a given map state.
+ * LII_ERR_INVALID: min_count < 4, every < 1, NULL out, max_dist as for lii_map_surface.  No map / while_waiting: LII_ERR_STATE.  Observer
+ * as lii_map_surface.  An empty selection or n_used == 0: mme = mpv = mean_count = 0. */
+struct lii_map_crispness {  /* 56 bytes */
+  int64_t n_selected, n_used, n_sparse /* count < min_count */, n_degenerate /* eig[0] <= 1e-12 * eig[2] */;
+  double  mme;        /* mean over the used points of 0.5 * (3 ln(2 pi e) + ln eig0 + ln eig1 + ln eig2) */
+  double  mpv;        /* mean over the used points of eig[0] */
+  double  mean_count; /* mean ball population of the used points */
+};
+int lii_map_crispness(lii_handle h, double max_dist, int32_t min_count /* >= 4 */, int32_t every /* >= 1 */,
+                      struct lii_map_crispness* out);
+/* The eigen-solver of the surface statistics, handle-free and on the host (lii_eig3.h: the same source runs on the device): cyclic Jacobi
+ * in double, a fixed number of sweeps.  m: xx, xy, xz, yy, yz, zz.  LII_ERR_INVALID: a NULL argument or a non-finite entry. */
+int lii_sym3_eigen(const double m[6], double eig[3] /* ascending */, double vec[9] /* row k = eigenvector of eig[k] */);
 /* ---- candidate poses scored against the map in one call: the ranking step of a re-localisation (restart in a saved map, flg_reset -
  * src/laserMapping.cpp:895-900 -, recovery after drift), where the caller holds no pose inside the update's convergence basin.
  * For pose k the figures of ONE pass of src/laserMapping.cpp:957-1020, run with nearest_search_en on an all-true selection at the state

@@ -109,6 +109,20 @@ POSE_REFINED_DTYPE = np.dtype([("pose", "<f8", (12,)), ("cov", "<f8", (6, 6)), (
                                ("iterations", "<i4"), ("searches", "<i4"), ("flags", "<i4")])
 LII_REFINE_CONVERGED, LII_REFINE_BAD_POSE = 1, 2
 
+
+class lii_surface(C.Structure):  # 88 bytes
+    _fields_ = [("count", C.c_int32), ("valid", C.c_int32), ("mean", C.c_double * 3), ("eig", C.c_double * 3), ("normal", C.c_double * 3),
+                ("curvature", C.c_double)]
+
+
+class lii_map_crispness(C.Structure):  # 56 bytes
+    _fields_ = [("n_selected", C.c_int64), ("n_used", C.c_int64), ("n_sparse", C.c_int64), ("n_degenerate", C.c_int64), ("mme", C.c_double),
+                ("mpv", C.c_double), ("mean_count", C.c_double)]
+
+
+# struct lii_surface as a numpy record
+SURFACE_DTYPE = np.dtype([("count", "<i4"), ("valid", "<i4"), ("mean", "<f8", (3,)), ("eig", "<f8", (3,)), ("normal", "<f8", (3,)), ("curvature", "<f8")])
+
 PUB_DENSE, PUB_DOWN, PUB_EFFECT, PUB_BODY = 1, 2, 4, 8  # lii_publish_opts::clouds
 PUB_INTENSITY = 16  # ... the intensities of the DENSE / DOWN / BODY clouds beside them (publish_fetch_intensity)
 
@@ -226,6 +240,10 @@ _DECLS = {
     "lii_pose_refine_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lii_map_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lii_map_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "lii_map_surface_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "lii_map_crispness": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.POINTER(lii_map_crispness)]),
+    "lii_sym3_eigen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lii_map_radius_xyzi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_map_radius_xyzi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lii_scan_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
@@ -419,6 +437,17 @@ def data_sufficiency(omg, data_accum_length):
     if rc != 0:
         raise LIIError(rc, "lii_data_sufficiency")
     return ev, rp, bool(ok.value)
+
+
+def sym3_eigen(m6):
+    """lii_sym3_eigen (host function of the library; the device runs the same source): m6 = xx, xy, xz, yy, yz, zz of a symmetric
+    3 x 3 matrix.  Returns (eig (3,) ascending, vec (3, 3): row k = the unit eigenvector of eig[k])."""
+    m = np.ascontiguousarray(m6, np.float64).reshape(6)
+    eig, vec = np.zeros(3), np.zeros((3, 3))
+    rc = load_library().lii_sym3_eigen(_ptr(m), _ptr(eig), _ptr(vec))
+    if rc != 0:
+        raise LIIError(rc, "lii_sym3_eigen")
+    return eig, vec
 
 
 class State:
@@ -1086,6 +1115,36 @@ class Registrar:
         self._check(self.L.lii_map_radius_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), float(max_dist),
                                               LII_RADIUS_SORTED if sorted else 0, _dev_address(offsets_dev), _dev_address(pts_dev),
                                               _dev_address(d2_dev), int(capacity), _dev_address(total_dev)))
+
+    def map_surface(self, q, max_dist, viewpoint=None):
+        """The surface the map holds at the points q (n, >= 3) float: for each, the ball of map_radius(q, max_dist) reduced on the
+        device to a record of SURFACE_DTYPE - count (the ball's population), valid (count >= 3), mean (the ball's centroid), eig (the
+        covariance's eigenvalues, ascending), normal (unit, of eig[0]) and curvature (eig[0] / sum).  viewpoint (3,): the normals look at
+        it; None: their largest component is positive.  Leaves everything of a registration alone."""
+        q = np.asarray(q, np.float32)
+        if q.ndim != 2 or q.shape[1] < 3 or not q.flags.c_contiguous:
+            q = np.ascontiguousarray(q.reshape(-1, q.shape[-1])[:, :3] if q.ndim >= 2 else q.reshape(-1, 3))
+        n = len(q)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+        out = np.zeros(n, SURFACE_DTYPE)
+        self._check(self.L.lii_map_surface(self.h, _ptr(q) if n else None, n, q.strides[0] if n else 12, float(max_dist),
+                                           None if vp is None else _ptr(vp), _ptr(out) if n else None))
+        return out
+
+    def map_surface_dev(self, q_dev, n, max_dist, out_dev, viewpoint=None, stride_bytes=12):
+        """map_surface with queries and the n 88-byte records in device memory the caller owns (raw addresses or objects with
+        __cuda_array_interface__); viewpoint stays a host array.  Enqueued on the handle's stream."""
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+        self._check(self.L.lii_map_surface_dev(self.h, _dev_address(q_dev), int(n), int(stride_bytes), float(max_dist),
+                                               None if vp is None else _ptr(vp), _dev_address(out_dev)))
+
+    def map_crispness(self, max_dist, min_count=5, every=1):
+        """How crisp is the map?  Mean map entropy (mme), mean plane variance (mpv) and mean ball population (mean_count) over the
+        map's own points with hash % every == 0 whose ball of squared radius max_dist holds >= min_count points and is not degenerate;
+        n_selected = n_used + n_sparse + n_degenerate.  Computed on the device, nothing is downloaded.  Returns a dict."""
+        out = lii_map_crispness()
+        self._check(self.L.lii_map_crispness(self.h, float(max_dist), int(min_count), int(every), C.byref(out)))
+        return {name: getattr(out, name) for name, _ in lii_map_crispness._fields_}
 
     def map_radius_xyzi(self, q, max_dist, sorted=False, points=True):
         """map_radius with 4 floats a row: (offsets, pts (total, 4) = x, y, z, intensity, d2 (total,))."""

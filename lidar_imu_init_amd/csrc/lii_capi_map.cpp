@@ -1587,6 +1587,130 @@ int lii_map_radius_xyzi(lii_handle h, const void* xyz, int32_t n, int32_t stride
   return map_radius(h, "lii_map_radius_xyzi", xyz, n, stride_bytes, max_dist, flags, offsets_out, pts_out, d2_out, capacity, total, 4);
 }
 
+// ---- surface statistics (kernels: lii_surface.hip): the ball of lii_map_radius reduced to count, centroid, covariance spectrum, normal
+namespace {
+static_assert(sizeof(struct lii_surface) == sizeof(lii::SurfaceRecord) && sizeof(struct lii_surface) == 88, "lii_surface is the kernels' record");
+static_assert(sizeof(struct lii_map_crispness) == sizeof(lii::CrispnessSums) && sizeof(struct lii_map_crispness) == 56, "lii_map_crispness is the kernels' record");
+static_assert(sizeof(lii::SurfaceTerm) == 24, "24 bytes of scratch per selected point");
+
+// The argument rules both forms share: lii_map_radius's, as far as they apply.  Nothing has been touched when this fails.
+int surface_plan(lii_handle h, const char* who, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, const void* out, NearestPlan* plan) {
+  if (!h) return LII_ERR_INVALID;
+  if (h->in_wait_hook) return fail(h, LII_ERR_STATE, std::string(who) + ": a registration is under way (lii_scan_job::while_waiting)");  // (before anything touches the stream)
+  if ((!xyz && n > 0) || n < 0 || stride_bytes < 12 || stride_bytes % 4 || (!out && n > 0))
+    return fail(h, LII_ERR_INVALID, std::string(who) + ": bad arguments (queries, n >= 0, stride a multiple of 4 and >= 12, out)");
+  if (!(max_dist >= 0.0) || !std::isfinite(max_dist)) return fail(h, LII_ERR_INVALID, std::string(who) + ": max_dist must be finite and >= 0 (it bounds the SQUARED distance)");
+  const double reach = 32.0 * double(h->cell_size);  // (as radius_plan decides it: exact in a double)
+  if (max_dist > reach * reach) return refuse_reach(h, who, max_dist);
+  plan->max_d2 = max_d2_of(max_dist);
+  plan->r_max = std::min(int(std::ceil(std::sqrt(max_dist) / double(h->cell_size))) + 1, 34);
+  return LII_OK;
+}
+}  // namespace
+
+int lii_map_surface_dev(lii_handle h, const void* xyz_dev, int32_t n, int32_t stride_bytes, double max_dist, const double* viewpoint, struct lii_surface* out_dev) {
+  NearestPlan plan;
+  int rc = surface_plan(h, "lii_map_surface_dev", xyz_dev, n, stride_bytes, max_dist, out_dev, &plan);
+  if (rc != LII_OK) return rc;
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (n == 0) return LII_OK;
+  rc = nearest_map(h, "lii_map_surface_dev");
+  if (rc != LII_OK) return rc;
+  const RadiusView v = radius_view(h);
+  launch_map_surface(v.g, v.entries, v.pts_cap, xyz_dev, n, stride_bytes, plan.max_d2, plan.r_max, viewpoint, reinterpret_cast<lii::SurfaceRecord*>(out_dev), h->stream);
+  HIPCHK(h, hipGetLastError());
+  return LII_OK;
+}
+
+int lii_map_surface(lii_handle h, const void* xyz, int32_t n, int32_t stride_bytes, double max_dist, const double* viewpoint, struct lii_surface* out) {
+  NearestPlan plan;
+  int rc = surface_plan(h, "lii_map_surface", xyz, n, stride_bytes, max_dist, out, &plan);
+  if (rc != LII_OK) return rc;
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  if (n == 0) return LII_OK;
+  rc = nearest_map(h, "lii_map_surface");
+  if (rc != LII_OK) return rc;
+  using MQ = lii_context::MapQuery;
+  const size_t rec = sizeof(struct lii_surface);
+  // a chunk: at most kQueriesMax queries; its records lie in the rows' area of the staging (88 bytes each: 5.5 rows of 16)
+  const size_t chunk = std::min<size_t>(size_t(n), MQ::kQueriesMax);
+  rc = query_staging(h, (chunk * rec + 15) / 16);
+  if (rc != LII_OK) return rc;
+  const size_t off_rec = 16 * std::min(h->mq.rows, MQ::kQueriesMax);
+  unsigned char *hb = h->mq.h_buf, *db = h->mq.d_buf;
+  hipStream_t s = h->stream;
+  const char* src = static_cast<const char*>(xyz);
+  const RadiusView v = radius_view(h);
+  for (size_t at = 0; at < size_t(n); at += chunk) {
+    const size_t m = std::min(chunk, size_t(n) - at);
+    float* hq = reinterpret_cast<float*>(hb);
+    for (size_t i = 0; i < m; i++) std::memcpy(hq + 3 * i, src + (at + i) * size_t(stride_bytes), 12);
+    HIPCHK(h, hipMemcpyAsync(db, hb, 12 * m, hipMemcpyHostToDevice, s));
+    launch_map_surface(v.g, v.entries, v.pts_cap, db, int(m), 12, plan.max_d2, plan.r_max, viewpoint, reinterpret_cast<lii::SurfaceRecord*>(db + off_rec), s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hb + off_rec, db + off_rec, rec * m, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    std::memcpy(out + at, hb + off_rec, rec * m);
+  }
+  return LII_OK;
+}
+
+int lii_map_crispness(lii_handle h, double max_dist, int32_t min_count, int32_t every, struct lii_map_crispness* out) {
+  const char* who = "lii_map_crispness";
+  NearestPlan plan;
+  static const float no_query[3] = {0.f, 0.f, 0.f};  // (the queries are the map's own points: surface_plan sees a list that is there)
+  int rc = surface_plan(h, who, no_query, 1, 12, max_dist, out, &plan);
+  if (rc != LII_OK) return rc;
+  if (min_count < 4 || every < 1) return fail(h, LII_ERR_INVALID, std::string(who) + ": min_count must be >= 4 and every >= 1");
+  lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)
+  rc = nearest_map(h, who);
+  if (rc != LII_OK) return rc;
+  rc = map_counters(h);  // (the gather below walks n_blocks cell tables: the host's copy must be current)
+  if (rc != LII_OK) return rc;
+  hipStream_t s = h->stream;
+  lii_context::MapSurface& S = h->msf;
+  if (!S.d_sums) HIPCHK(h, S.d_sums.alloc(1));
+  // the live points, cell by cell, as lii_map_download enumerates them; the selected ones end to end in d_map
+  int cnt = 0;
+  if (h->n_map > 0) {
+    rc = map_gather(h, &cnt);
+    if (rc != LII_OK) return rc;
+  }
+  unsigned int n_sel = 0;
+  if (cnt > 0) {
+    launch_surface_select(h->d_map_unsorted, cnt, (unsigned int)every, h->d_idx_a, s);
+    HIPCHK(h, hipGetLastError());
+    inclusive_scan_u32(h->d_sort_temp, h->d_sort_temp.size(), h->d_idx_a, h->d_idx_b, cnt, s);
+    HIPCHK(h, hipGetLastError());
+    launch_surface_compact(h->d_map_unsorted, h->d_idx_a, h->d_idx_b, cnt, h->d_map, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&h->h_small->gather_count, h->d_idx_b + (cnt - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    n_sel = std::min<unsigned int>(h->h_small->gather_count, (unsigned int)cnt);
+  }
+  if (n_sel > 0) {
+    HIPCHK(h, radius_room(S.d_terms, size_t(n_sel)));
+    const RadiusView v = radius_view(h);
+    launch_map_surface_terms(v.g, v.entries, v.pts_cap, h->d_map, int(n_sel), int(sizeof(float4)), plan.max_d2, plan.r_max, min_count, S.d_terms, s);
+    HIPCHK(h, hipGetLastError());
+  }
+  launch_crispness_reduce(S.d_terms, int(n_sel), S.d_sums, s);
+  HIPCHK(h, hipGetLastError());
+  lii::CrispnessSums sums;
+  HIPCHK(h, hipMemcpyAsync(&sums, S.d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  std::memcpy(out, &sums, sizeof(sums));
+  return LII_OK;
+}
+
+int lii_sym3_eigen(const double m[6], double eig[3], double vec[9]) {
+  if (!m || !eig || !vec) return LII_ERR_INVALID;
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(m[i])) return LII_ERR_INVALID;
+  lii::sym3_eigen_host(m, eig, vec);
+  return LII_OK;
+}
+
 
 int lii_map_incremental(lii_handle h, const lii_state* state, int32_t* n_add, int32_t* n_no_downsample) {
   lii_internal_prearm_cancel(h);  // (a pre-armed de-skew launch waiting on the stream is told to end: this entry point uses the stream)

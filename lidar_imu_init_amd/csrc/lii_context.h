@@ -147,6 +147,13 @@ struct lii_context {
     DevBuf<unsigned long long> d_key_a, d_key_b;  // LII_RADIUS_SORTED: (query << 32 | d2 bits) per row, before and behind the sort
     DevBuf<unsigned int> d_slot_a, d_slot_b;      // ... and the row's slot in the point array
   } mr;
+  // lii_map_crispness: one term per selected point and the figures of the reduction.  Nothing here exists before the first such call;
+  // d_terms grows geometrically and goes with the handle.  (The selection itself runs through scratch of the map build - d_idx_a,
+  // d_idx_b, d_map - which is free between two builds; lii_map_surface needs nothing beyond mq.)
+  struct MapSurface {
+    DevBuf<lii::SurfaceTerm> d_terms;
+    DevBuf<lii::CrispnessSums> d_sums;
+  } msf;
   // lii_pose_score / lii_pose_score_dev (kernels: lii_score.hip).  Nothing here exists before the first such call; every buffer grows
   // geometrically and goes with the handle.  d_part serves both forms; the others stage one chunk of poses of the host form.
   struct PoseScore {

@@ -65,6 +65,25 @@ void launch_map_radius_gather(const GridView& g, unsigned int pts_cap, const uns
                               long long base, long long capacity, float* pts_out, float* d2_out, hipStream_t s, int row_floats = 3);
 // row_floats (the three launches above): 3 - x, y, z a row of pts_out - or 4: the stored fourth word, the point's intensity, behind them
 // (lii_map_nearest_xyzi / lii_map_radius_xyzi; instantiations of their own)
+// surface statistics (lii_surface.hip): the ball of lii_map_radius reduced to its moments, one wavefront per query.
+//   mean_rel = s1 / n,  C_ab = s2_ab / n - mean_rel_a * mean_rel_b   with s1, s2 the sums of d and d_a d_b, d = (double)m - (double)q,
+// formed exactly so (no FMA); eig / normal: lii_eig3.h.  SurfaceRecord is lii_surface's layout, CrispnessSums lii_map_crispness's.
+// viewpoint: a HOST pointer to 3 doubles, or nullptr (it travels in the kernel's arguments).
+struct SurfaceRecord { int count, valid; double mean[3], eig[3], normal[3], curvature; };
+enum { kSurfaceUsed = 0, kSurfaceSparse = 1, kSurfaceDegenerate = 2 };
+struct SurfaceTerm { double h, eig0; int count, kind; };  // one selected point of lii_map_crispness: its entropy, eig[0], ball population, kSurface*
+struct CrispnessSums { long long n_selected, n_used, n_sparse, n_degenerate; double mme, mpv, mean_count; };
+void sym3_eigen_host(const double m[6], double eig[3], double vec[9]);  // lii_eig3.h's routine, compiled for the host in the unit that runs it on the device
+void launch_map_surface(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2, int r_max,
+                        const double* viewpoint, SurfaceRecord* out, hipStream_t s);
+// ... the aggregate: terms[i] of query i (a sparse ball: count < min_count; a degenerate one: eig[0] <= 1e-12 eig[2]) instead of the record;
+// _select: flags[i] = mix(point i) % every == 0; _compact: behind the inclusive scan of the flags, the selected points end to end;
+// _reduce: one workgroup, a fixed order of additions - out[0] from the n terms (n == 0: zeros)
+void launch_map_surface_terms(const GridView& g, unsigned int n_entries, unsigned int pts_cap, const void* queries, int n, int stride_bytes, float max_d2,
+                              int r_max, int min_count, SurfaceTerm* terms, hipStream_t s);
+void launch_surface_select(const float4* pts, int n, unsigned int every, unsigned int* flags, hipStream_t s);
+void launch_surface_compact(const float4* pts, const unsigned int* flags, const unsigned int* ranks, int n, float4* dst, hipStream_t s);
+void launch_crispness_reduce(const SurfaceTerm* terms, int n, CrispnessSums* out, hipStream_t s);
 // pose scoring (lii_score.hip): the figures of one search pass (src/laserMapping.cpp:957-1020, all-true selection) at each of n_poses
 // poses - 12 doubles each in device memory: rot_end row-major, pos_end; the extrinsic is `base`'s - over the n points of `body`.
 // ScorePartial is lii_pose_score's layout: scores[k] receives pose k's figures, partials (pose_score_partials(n, n_poses) records of

@@ -72,8 +72,9 @@ void launch_map_nearest(const GridView& g, unsigned int n_entries, unsigned int 
 // ------------------------------------------------------------------------------------------------ the ball query
 // KD_TREE::Radius_Search of upstream ikd-Tree - in the reference's copy of the tree Nearest_Search(point, k, ..., max_dist) with k above
 // the ball's population - (lii_map_radius / lii_map_radius_dev): EVERY live point with d2 <= max_dist, however many there are.
-// ONE WAVEFRONT PER QUERY, and a query walks its cells TWICE, by the walk of k_map_nearest: Chebyshev rings, one cell per lane,
-// cell_range_checked, the per-cell gap bound against max_d2 alone, the wave-wide prefix over 64 cells, 64 points at a time.  The count
+// ONE WAVEFRONT PER QUERY, and a query walks its cells TWICE, by ball_walk (lii_ringwalk.h; the surface statistics of lii_surface.hip
+// reduce a ball on the same walk): Chebyshev rings, one cell per lane, cell_range_checked, the per-cell gap bound against max_d2 alone,
+// the wave-wide prefix over 64 cells, 64 points at a time.  The count
 // pass leaves the sum of the ballots' popcounts; an exclusive scan of the counts (lii_sort.hip) makes them offsets; the fill pass
 // repeats the identical walk and stores an accepted point at offsets[i] + (points accepted so far) + (popcount of the ballot below the
 // lane): the segments are dense and in the walk's order, and no atomic touches the output.  There is no k-th distance to stop on: ring
@@ -93,88 +94,35 @@ __global__ __launch_bounds__(kBlock) void k_map_radius(GridView g, unsigned int 
   if (qi >= n) return;  // (the whole wavefront)
   const float* qp = reinterpret_cast<const float*>(queries + (size_t)qi * (size_t)stride_bytes);
   const float qx = qp[0], qy = qp[1], qz = qp[2];
-  const int cx = query_cell(qx, g.inv_cs), cy = query_cell(qy, g.inv_cs), cz = query_cell(qz, g.inv_cs);
-  const float eps = 1e-6f * (fabsf(qx) + fabsf(qy) + fabsf(qz) + 8.f);
-  // a NaN coordinate: an empty segment; a ball that reaches no addressable cell: one as well
-  const int reach = kCellBias + r_max;
-  bool searchable = qx == qx && qy == qy && qz == qz && abs(cx) <= reach && abs(cy) <= reach && abs(cz) <= reach;
+  // (a NaN coordinate: an empty segment; a ball that reaches no addressable cell: one as well - ball_walk makes no trip then)
+  bool wanted = true;
   long long seg_first = 0;
   unsigned int seg_len = 0u;
   if (kFill) {
     const long long o0 = offsets[qi], o1 = offsets[qi + 1];
     seg_first = o0 - base;
     seg_len = (unsigned int)min(max(o1 - o0, 0ll), (long long)pts_cap);  // (a ball holds no more points than the array has slots)
-    searchable = searchable && seg_len > 0u && seg_first >= 0 && seg_first < capacity;  // (an empty segment, or one beyond the rows: no walk)
+    wanted = seg_len > 0u && seg_first >= 0 && seg_first < capacity;  // (an empty segment, or one beyond the rows: no walk)
   }
   const unsigned long long below = (1ull << lane) - 1ull;
   unsigned int accepted = 0u;
-  const int rings = searchable ? r_max : -1;
-  for (int r = 0; r <= rings; r++) {
-    const int s = 2 * r + 1;
-    const int n_cells = r == 0 ? 1 : s * s * s - (s - 2) * (s - 2) * (s - 2);
-    for (int t0 = 0; t0 < n_cells; t0 += 64) {
-      const int t = t0 + lane;
-      unsigned int first = 0u, cnt = 0u;
-      if (t < n_cells) {
-        int dx = 0, dy = 0, dz = 0;
-        if (r > 0) ring_cell(r, t, dx, dy, dz);
-        const int ix = cx + dx, iy = cy + dy, iz = cz + dz;
-        // (a cell outside the addressable grid holds no map point: the ball's cell range is clamped to the grid)
-        const bool in_grid = (unsigned)(ix + kCellBias) < 2u * kCellBias && (unsigned)(iy + kCellBias) < 2u * kCellBias && (unsigned)(iz + kCellBias) < 2u * kCellBias;
-        if (in_grid) {
-          const float gx = axis_gap(qx, ix, g.cs, eps), gy = axis_gap(qy, iy, g.cs, eps), gz = axis_gap(qz, iz, g.cs, eps);
-          const float gap2 = (gx * gx + gy * gy + gz * gz) * kBoundSlack;
-          if (!(gap2 > max_d2)) {
-            const uint2 rg = cell_range_checked(g, n_entries, pts_cap, ix, iy, iz);
-            first = rg.x;
-            cnt = min(rg.y - rg.x, 1u << 25);  // (as in k_map_nearest: the sum over 64 cells stays inside 32 bits whatever the tables say)
-          }
-        }
-      }
-      // the 64 ranges end to end: incl = points up to and including this lane's cell
-      unsigned int incl = cnt;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      const unsigned int total = __shfl(incl, 63);
-      const unsigned int cell_base = first - (incl - cnt);  // slot of point p of the sequence, p in this lane's cell: cell_base + p
-      for (unsigned int p0 = 0; p0 < total; p0 += 64) {
-        const unsigned int p = p0 + (unsigned)lane;
-        const bool have = p < total;
-        int j = 0;  // the first cell whose inclusive count exceeds p
-#pragma unroll
-        for (int step = 32; step >= 1; step >>= 1) {
-          const unsigned int v = __shfl(incl, j + step - 1);
-          if (v <= p) j += step;
-        }
-        const unsigned int slot = __shfl(cell_base, j) + p;
-        float d = INFINITY, mx = 0.f, my = 0.f, mz = 0.f;
-        if (have) {
-          const F3 m = load_xyz(g.pts, slot);
-          mx = m.x; my = m.y; mz = m.z;
-          d = dist2_ref(qx, qy, qz, mx, my, mz);
-        }
-        const bool in_ball = have && d <= max_d2;
-        const unsigned long long hits = __ballot(in_ball);
-        if (kFill) {
-          const unsigned int at = accepted + (unsigned int)__popcll(hits & below);
-          const long long row = seg_first + (long long)at;
-          if (in_ball && at < seg_len && row < capacity) {
-            if (pts_out) {
-              pts_out[W * row] = mx; pts_out[W * row + 1] = my; pts_out[W * row + 2] = mz;
-              if (W == 4) pts_out[W * row + 3] = g.pts[slot].w;
-            }
-            if (d2_out) d2_out[row] = d;
-            if (key_out) key_out[row] = ((unsigned long long)qi << 32) | (unsigned long long)__float_as_uint(d);
-            if (slot_out) slot_out[row] = slot;
-          }
-        }
-        accepted += (unsigned int)__popcll(hits);
-      }
-    }
-  }
+  ball_walk(g, n_entries, pts_cap, qx, qy, qz, max_d2, r_max, wanted,
+            [&](unsigned int slot, bool, bool in_ball, unsigned long long hits, float mx, float my, float mz, float d) {
+              if (kFill) {
+                const unsigned int at = accepted + (unsigned int)__popcll(hits & below);
+                const long long row = seg_first + (long long)at;
+                if (in_ball && at < seg_len && row < capacity) {
+                  if (pts_out) {
+                    pts_out[W * row] = mx; pts_out[W * row + 1] = my; pts_out[W * row + 2] = mz;
+                    if (W == 4) pts_out[W * row + 3] = g.pts[slot].w;
+                  }
+                  if (d2_out) d2_out[row] = d;
+                  if (key_out) key_out[row] = ((unsigned long long)qi << 32) | (unsigned long long)__float_as_uint(d);
+                  if (slot_out) slot_out[row] = slot;
+                }
+              }
+              accepted += (unsigned int)__popcll(hits);
+            });
   if (!kFill && lane == 0) count_out[qi] = (long long)accepted;
 }
 
